@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the SLIC -> descriptors -> GraphCut hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--inflight M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--inflight M] [--dump-outputs DIR] [--full]
 
 What one STEP is ("image resident in host numpy" -> "`segm` resident in host numpy"):
 
@@ -17,9 +17,15 @@ What one STEP is ("image resident in host numpy" -> "`segm` r
   config 5  one 64 x 4096 x 4096 float32 volume through `pipe_gray3d_slic_features_model_graphcut` (model fit
             included, as the reference function does): `--config 5`
 
-Without `--config` the line of config 2 carries `other_configs`: configs 3, 4 and a reduced config 5 (the 32 x 512 x 512 volume
-the reference itself was run on) timed in the same invocation with a few steps each, every one with its own equality keys
-against the reference's run at that size (tests/golden/reference_c{3,4,5}.npz, tests/golden/make_golden_configs.py).
+A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (milliseconds of one timed step) and the configuration.  `--dump-outputs DIR` then also writes what the last
+timed step returned (the class map(s), float32) to DIR; the inputs are seeded, so two builds can be compared map for map.
+
+`--full` adds everything else, as separate passes after the timed steps: without `--config` the line of config 2 carries
+`other_configs` -- configs 3, 4 and a reduced config 5 (the 32 x 512 x 512 volume the reference itself was run on) timed in the
+same invocation with a few steps each, every one with its own equality keys against the reference's run at that size
+(tests/golden/reference_c{3,4,5}.npz, tests/golden/make_golden_configs.py) --, and every configuration its roofline, stage
+figures, latency, host link, fit-inclusive line, CPU baseline and checks against the reference's runs.
 
 `value` = pixels (voxels) of all timed steps of all ranks / wall time, host to host.  M images are kept in flight per
 GPU (worker threads with one HIP stream and one recycled session each; a thread spends a step inside a handful of C
@@ -27,7 +33,7 @@ calls, outside the interpreter lock) -- the reference maps a pool of worker proc
 taken in STEADY STATE: W + K + M steps are issued back to back between two barriers + device synchronisations, and
 the clock runs from the completion of step W to the completion of step W + K, so exactly K steps are timed and the
 figure does not depend on the fill and drain of the pipeline (`ms_per_step_incl_fill_drain` is reported next to it).
-Separate keys carry the device-resident rate of the same pipeline (image already in HBM, result left in HBM:
+With `--full`, separate keys carry the device-resident rate of the same pipeline (image already in HBM, result left in HBM:
 `device_resident`), the extra cost of fetching `segm_soft` (`soft_d2h_ms`), and a single image end to end with
 nothing else in flight (`latency_ms`).
 
@@ -35,8 +41,8 @@ nothing else in flight (`latency_ms`).
 by a HIP event pair attached to its dispatch).  N > 1: one process per GPU -- ranks from the launcher's environment, or,
 when `--gpus N` is given without one, N ranks spawned by this script itself -- every rank segments its own image(s) (weak
 scaling, no data-path collective) and the label maps of every round of M steps are gathered in rank 0's HBM with one
-grouped RCCL send / recv (pyimsegm_amd.distributed, ctypes on librccl); rank 0 checks the CRC of EVERY gathered map of a
-verification round against the reference's run.
+grouped RCCL send / recv (pyimsegm_amd.distributed, ctypes on librccl); with `--full`, rank 0 checks the CRC of EVERY
+gathered map of a verification round against the reference's run.
 
 Prints ONE JSON line on rank 0.
 """
@@ -88,7 +94,35 @@ def parse_args(argv=None):
                                                                'runtime (default off: measured slower on one GPU)')
     ap.add_argument('--probe-seconds', type=float, default=1.0, help='N > 1, --input-ring -1: length of each of the two input-staging probes')
     ap.add_argument('--no-full-volume', action='store_true', help='leave BASELINE configs[4] at its full 64x4096x4096 out of `other_configs`')
+    ap.add_argument('--full', action='store_true', help='everything beyond the headline: `other_configs`, roofline and stage figures, '
+                                                        'latency, host link, fit-inclusive line, CPU baseline, checks against the '
+                                                        "reference's runs (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)')
     return ap.parse_args(argv)
+
+
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: voxels of a larger class map written as a fixed, seeded sample (16 MB with its index)
+DUMP_WHOLE_MAX = 1 << 23       # ... maps of at most this many elements are written whole (32 MB as float32)
+
+
+def keep_for_dump(segm):
+    """what --dump-outputs keeps of the class map of the last timed step, inside that step: the array itself (a reference, no
+    copy), or -- a map of more than DUMP_WHOLE_MAX elements -- DUMP_SAMPLE entries at positions drawn from a fixed seed, so that
+    two runs pick the same voxels and the map's page-locked block goes back to the pool at once"""
+    segm = np.asarray(segm)
+    if segm.size <= DUMP_WHOLE_MAX:
+        return {'segm': segm}
+    index = np.unique(np.random.default_rng(0).integers(0, segm.size, size=DUMP_SAMPLE, dtype=np.int64))
+    return {'segm_sample': segm.reshape(-1)[index], 'segm_sample_index': index}
+
+
+def dump_outputs(path, kept):
+    """--dump-outputs: what keep_for_dump kept, as DIR/<name>.npy -- labels as float32 (small integers: exact), sample positions
+    (flat C-order index) as float64 (exact below 2^53)"""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in kept.items():
+        np.save(os.path.join(path, name + '.npy'), np.asarray(arr).astype(np.float64 if name.endswith('_index') else np.float32))
 
 
 def crc32(arr, dtype=np.int32):
@@ -854,6 +888,8 @@ def bench_color2d(args, group, cfg, quick=False):
     from pyimsegm_amd.utilities.synthetic import voronoi_image
 
     world, rank = group.world, group.rank
+    full = args.full                                  # (the quick runs of `other_configs` happen under --full only)
+    dump = args.dump_outputs if not quick else None
     golden4 = load_golden('reference_c4.npz') if cfg == 4 else None
     if cfg == 4:
         (height, width), sp_size, per_step = C4_SHAPE, C4_SP_SIZE, C4_PER_STEP
@@ -957,8 +993,16 @@ def bench_color2d(args, group, cfg, quick=False):
                 return got
         return [one_image(image, stage=stage, k=k) for k, image in enumerate(step_images)]
 
+    last_output = []
+
+    def timed_step(state, index, stage):
+        got = do_step(state, index, stage)
+        if index == warmup + steps - 1:               # (references to the step's own result arrays: nothing is copied in the timed region)
+            last_output.append(got)
+        return got
+
     rank_links = None
-    if group.distributed and world > 1:
+    if full and group.distributed and world > 1:
         # what the host link of every rank moves with all ranks copying at once (a slow socket or a shared switch shows here)
         link = None
         try:
@@ -983,13 +1027,24 @@ def bench_color2d(args, group, cfg, quick=False):
         staging['on'] = probe['ring'] > 1.03 * probe['pageable']
         staging['chosen_by'] = 'probe on this rank with all %d ranks running (Mpixels/s: %r)' % (world, probe)
         staging['probe'] = probe
-    runner = SteadyRun(group, inflight, make_state, do_step, gather_item_bytes=height * width * 4, items_per_step=per_step)
+    if dump:
+        # spare page-locked result blocks in the pool: the maps of the last timed step stay alive for the dump, and a cool-down step
+        # must not allocate a fresh block (hipHostMalloc) while the last timed steps are in flight
+        spare = [_hip.pinned_empty((height, width), np.int32) for _ in range(min(16, (inflight + 1) * per_step))]
+        del spare
+    runner = SteadyRun(group, inflight, make_state, timed_step if dump else do_step, gather_item_bytes=height * width * 4,
+                       items_per_step=per_step)
     elapsed, cold = runner.run(warmup, steps)
+    if dump and rank == 0:
+        maps = [np.asarray(m) for m in last_output[0]]
+        dump_outputs(dump, keep_for_dump(maps[0] if len(maps) == 1 else np.stack(maps)))
+        del maps
+    del last_output[:]
     rank_rings = group.gather_objects({'input_ring': bool(staging['on']), 'chosen_by': staging['chosen_by']}) if (group.distributed and world > 1) else None
 
     # ---- every gathered label map against the reference's run (N > 1: the first multi-GPU run validates the RCCL gather)
     verdict = {}
-    if cfg != 4 and group.distributed:
+    if full and cfg != 4 and group.distributed:
         # configs 2 / 3 at N > 1: every rank works on its own image (seed 1 + rank), so what rank 0 received is checked
         # against the CRC of the map the SENDING rank holds in its own host memory (host control plane): the device
         # gather is validated end to end by the first multi-GPU run
@@ -1005,7 +1060,7 @@ def bench_color2d(args, group, cfg, quick=False):
             verdict['gathered_maps_equal_senders_own'] = bool(got == list(sent))
             if got != list(sent):
                 verdict['gathered_maps_different_ranks'] = [r for r in range(world) if got[r] != sent[r]][:16]
-    if cfg == 4 and golden4 is not None:
+    if full and cfg == 4 and golden4 is not None:
         want = {int(s): int(c) for s, c in zip(golden4['seeds'], golden4['segm_crc'])}
         if group.distributed:
             maps = runner.verify_round(make_state(), do_step)
@@ -1056,7 +1111,7 @@ def bench_color2d(args, group, cfg, quick=False):
 
     # ---- separate figures: device-resident rate, soft D2H, single-image latency (un-timed for `value`)
     extras = {}
-    if rank == 0:
+    if rank == 0 and full:
         from pyimsegm_amd.superpixels import _open_session
         t = time.perf_counter()
         for _ in range(3):
@@ -1096,7 +1151,7 @@ def bench_color2d(args, group, cfg, quick=False):
             # stream -- on the boxes of this pool the two directions share ~55 GB/s (tools/xfer_concurrent.py: more threads or
             # copying both ways at once moves no more), so this is a ceiling of the host -> host rate, whatever the kernels do
 
-    if rank == 0:
+    if rank == 0 and full:
         # what the host link allows: the bytes of one image (pixels up, int32 segmentation down) copied back to back on one
         # stream -- on the boxes of this pool the two directions share ~55 GB/s (tools/xfer_concurrent.py: more threads or
         # copying both ways at once moves no more), so this is a ceiling of the host -> host rate, whatever the kernels do.
@@ -1111,21 +1166,22 @@ def bench_color2d(args, group, cfg, quick=False):
 
     # ---- kernel-level figures: un-overlapped pass on one stream with HIP events around every stage
     prof_steps = 3 if cfg == 3 else 5
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    for _ in range(prof_steps):
-        if batched:
-            do_step(None, -1, None)                   # (the launch chain of the timed steps: per_step images per launch)
-        else:
-            one_image(images[0])
-    ctx.synchronize()
-    stage_ms = {g: ctx.profile_get(g) for g in _hip.PROFILE_GROUPS}
-    ctx.profile_enable(False)
+    if full:
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        for _ in range(prof_steps):
+            if batched:
+                do_step(None, -1, None)                   # (the launch chain of the timed steps: per_step images per launch)
+            else:
+                one_image(images[0])
+        ctx.synchronize()
+        stage_ms = {g: ctx.profile_get(g) for g in _hip.PROFILE_GROUPS}
+        ctx.profile_enable(False)
 
     out = None
-    if rank == 0:
-        value = world * steps * npx_step / elapsed / 1e6
-        npx = height * width
+    value = world * steps * npx_step / elapsed / 1e6
+    npx = height * width
+    if rank == 0 and full:
         if cfg == 3:
             tex_ms, tex_n = stage_ms['texture']
             flops = 2.0 * 1089 * 76 * 3 * npx                      # 2 * 33^2 taps * 76 kernels * 3 channels per pixel
@@ -1174,6 +1230,7 @@ def bench_color2d(args, group, cfg, quick=False):
                         'avg_kernel_us': round(avg_s * 1e6, 3), 'launches': assign_n, 'sweeps_per_launch': sweeps,
                         'images_per_launch': per_launch,
                         'algorithmic_bytes_per_launch': ASSIGN_BYTES_PER_PX * npx * per_launch * sweeps}
+    if rank == 0:
         workload = {
             2: 'single %dx%d RGB uint8 per GPU, SLIC(sp_size=46, K=2025, 10 sweeps) + colour mean/std/energy + 3-class '
                'alpha-expansion GC (gc_regul=2.0, edge=model), pre-fitted GMM, host numpy in -> segm int32 in host numpy '
@@ -1216,16 +1273,17 @@ def bench_color2d(args, group, cfg, quick=False):
                                     * steps / sec / 1e9, 4) for sec, rr in zip(runner_rank_seconds, rank_rings or [None] * world)]}
                          if (group.distributed and world > 1) else None),
             'rccl_error': getattr(group, 'rccl_error', None),
-            'roofline': roofline,
-            'stage_ms_per_step': {g: round(ms / prof_steps, 4) for g, (ms, n) in stage_ms.items()},
-            'stage_note': 'stage and roofline figures: separate pass of %d un-overlapped host-to-host %s on one stream'
-                          % (prof_steps, 'steps (batches of %d images in one launch chain)' % per_step if batched else 'images'),
         }
+        if full:
+            out['roofline'] = roofline
+            out['stage_ms_per_step'] = {g: round(ms / prof_steps, 4) for g, (ms, n) in stage_ms.items()}
+            out['stage_note'] = ('stage and roofline figures: separate pass of %d un-overlapped host-to-host %s on one stream'
+                                 % (prof_steps, 'steps (batches of %d images in one launch chain)' % per_step if batched else 'images'))
         out.update(extras)
         out.update(verdict)
         if isinstance(out.get('host_link'), dict) and out['host_link'].get('ceiling_mpixels_per_s'):
             out['host_link']['fraction_of_ceiling'] = round(value / world / out['host_link']['ceiling_mpixels_per_s'], 3)
-        if world == 1:
+        if full and world == 1:
             try:      # the fit-inclusive form of the same step (its own line item; `value` stays the pre-fitted form)
                 n_fit = {2: 3, 3: 1, 4: 1}[cfg] if quick else {2: 5, 3: 2, 4: 1}[cfg]
                 inc = fit_inclusive_line(pipe, [np.asarray(im) for im in images], features, sp_size, n_fit)
@@ -1234,7 +1292,7 @@ def bench_color2d(args, group, cfg, quick=False):
                 out['ms_per_step_including_fit'] = round(inc['ms_per_image_including_fit'] * per_step, 3)
             except Exception as ex:
                 out['fit_inclusive'] = {'error': repr(ex)}
-        if world == 1 and not args.no_cpu_baseline and cfg == 2 and not quick:
+        if full and world == 1 and not args.no_cpu_baseline and cfg == 2 and not quick:
             try:
                 base, segm_cpu, slic_real = cpu_baseline_color2d(np.asarray(images[0]), model, sp_size, SP_REGUL)
                 out['cpu_baseline'] = base
@@ -1247,13 +1305,13 @@ def bench_color2d(args, group, cfg, quick=False):
                     res.close()
             except Exception as ex:   # the baseline is a reported extra, never a reason to lose the line
                 out['cpu_baseline'] = {'error': repr(ex)}
-        if world == 1 and not args.no_cpu_baseline and cfg == 3 and (height, width) == (HEIGHT, WIDTH):
+        if full and world == 1 and not args.no_cpu_baseline and cfg == 3 and (height, width) == (HEIGHT, WIDTH):
             try:
                 out['cpu_baseline'] = cpu_baseline_texture(np.asarray(images[0]), sp_size, SP_REGUL, budget_s=12.0 if quick else 20.0)
                 out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 1)
             except Exception as ex:
                 out['cpu_baseline'] = {'error': repr(ex)}
-        if world == 1 and not args.no_cpu_baseline and cfg == 4:
+        if full and world == 1 and not args.no_cpu_baseline and cfg == 4:
             try:
                 arrays = {k: np.array(golden4[k]) for k in ('scaler_mean', 'scaler_scale', 'gmm_weights', 'gmm_means', 'gmm_covariances',
                                                             'gmm_precisions_cholesky')} if golden4 is not None else None
@@ -1262,7 +1320,7 @@ def bench_color2d(args, group, cfg, quick=False):
                     out['speedup_vs_cpu_baseline'] = round(value / out['cpu_baseline']['value'], 2)
             except Exception as ex:
                 out['cpu_baseline'] = {'error': repr(ex)}
-        if world == 1 and (height, width) == (HEIGHT, WIDTH) and cfg in (2, 3):
+        if full and world == 1 and (height, width) == (HEIGHT, WIDTH) and cfg in (2, 3):
             try:      # the reference's own run on this very image (build container, tests/golden/make_golden_*.py)
                 verdict = (compare_config2 if cfg == 2 else compare_config3)(np.asarray(images[0]), pipe)
                 if verdict is not None:
@@ -1333,36 +1391,46 @@ def bench_volume(args, group, shape=None, quick=False):
                 inflight -= 1
         except Exception:
             inflight = 1
-    # one volume alone first (warm-up + one timed call on this thread): the latency of the call and the share of the fit in it
-    step()
-    ctx.synchronize()
-    latency_ms, latency_fit_ms = float('inf'), 0.0
-    segm = None
-    for _ in range(2):                          # (the faster of two)
-        fit_seconds[0] = 0.0
-        t_lat = time.perf_counter()
-        segm = step()
-        if (time.perf_counter() - t_lat) * 1e3 < latency_ms:
-            latency_ms, latency_fit_ms = (time.perf_counter() - t_lat) * 1e3, fit_seconds[0] * 1e3
-    classes_found = int(len(np.unique(segm[::4, ::16, ::16])))
-    del segm
-    # the stage figures: one more un-overlapped volume on the session the latency was measured on, HERE -- behind the run with volumes
-    # in flight this thread's session is gone and its 90 GB are allocated again between the stage's events (seconds, once)
-    ctx.profile_enable(True)
-    ctx.profile_reset()
-    step()
-    stage_ms = {g: ctx.profile_get(g) for g in _hip.PROFILE_GROUPS}
-    ctx.profile_enable(False)
-    if inflight > 1:
-        ctx.close_idle_sessions()               # (the worker threads bring their own resident volumes)
+    full = args.full                            # (the quick runs of `other_configs` happen under --full only)
+    dump = args.dump_outputs if not quick else None
+    if full:
+        # one volume alone first (warm-up + one timed call on this thread): the latency of the call and the share of the fit in it
+        step()
+        ctx.synchronize()
+        latency_ms, latency_fit_ms = float('inf'), 0.0
+        segm = None
+        for _ in range(2):                          # (the faster of two)
+            fit_seconds[0] = 0.0
+            t_lat = time.perf_counter()
+            segm = step()
+            if (time.perf_counter() - t_lat) * 1e3 < latency_ms:
+                latency_ms, latency_fit_ms = (time.perf_counter() - t_lat) * 1e3, fit_seconds[0] * 1e3
+        classes_found = int(len(np.unique(segm[::4, ::16, ::16])))
+        del segm
+        # the stage figures: one more un-overlapped volume on the session the latency was measured on, HERE -- behind the run with
+        # volumes in flight this thread's session is gone and its 90 GB are allocated again between the stage's events (seconds, once)
+        ctx.profile_enable(True)
+        ctx.profile_reset()
+        step()
+        stage_ms = {g: ctx.profile_get(g) for g in _hip.PROFILE_GROUPS}
+        ctx.profile_enable(False)
+        if inflight > 1:
+            ctx.close_idle_sessions()               # (the worker threads bring their own resident volumes)
+    last_output = []
+
     def do_step(state, index, stage):
-        step()                                  # (the class map goes back to the pool of page-locked result arrays at once)
+        segm = step()                           # (the class map goes back to the pool of page-locked result arrays at once ...)
+        if dump and index == warmup + steps - 1:
+            last_output.append(keep_for_dump(segm))     # (... but what --dump-outputs needs of that of the last timed step)
     if inflight > 1 and (args.steps is None or quick):
         steps, warmup = max(steps, 2 * inflight), max(warmup, inflight)
     runner = SteadyRun(group, inflight, lambda: {'ctx': _hip.default_context()}, do_step)
     fit_seconds[0] = 0.0
     elapsed, cold = runner.run(warmup, steps)
     runner.close()
+    if dump and group.rank == 0:
+        dump_outputs(dump, last_output[0])
+    del last_output[:]
     if inflight > 1:
         _hip.reap_contexts()                    # (the resident volumes of the worker threads that have just ended)
     # (the clock of the fit: its share of the timed steps only -- SteadyRun runs first-use, warm-up, timed and cool-down steps)
@@ -1379,36 +1447,37 @@ def bench_volume(args, group, shape=None, quick=False):
     if group.rank != 0:
         return None
     nvox = int(np.prod(shape))
-    assign_ms, assign_n = stage_ms['slic_assign']
-    slic_ms = stage_ms['slic'][0]
-    if assign_n:           # the assignment kernel itself (HIP events on its dispatches), 8 B/voxel/sweep
-        avg_s = assign_ms / assign_n / 1e3
-        roofline = {'bound': 'hbm', 'kernel': 'k_vol_assign_f32 (3-D assignment, all sweeps)',
-                    'achieved': round(VOL_ASSIGN_BYTES_PER_VOXEL * nvox / avg_s / 1e9, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                    'frac': round(VOL_ASSIGN_BYTES_PER_VOXEL * nvox / avg_s / 1e9 / HBM_PEAK_GBS, 5), 'traffic': None,
-                    'avg_kernel_us': round(avg_s * 1e6, 1), 'launches': assign_n,
-                    'algorithmic_bytes_per_launch': VOL_ASSIGN_BYTES_PER_VOXEL * nvox}
-        try:
-            # HBM bytes and instruction counts of the kernel from the committed rocprofv3 PMC passes (tools/c5_pmc.sh, a quarter
-            # volume with the same bricks and windows: per voxel, scaled to this volume).  HBM is not what bounds this kernel:
-            # ~60 search windows cover a voxel, a wave of 256 voxels issues ~1 350 vector + ~1 180 scalar instructions -- the floor
-            # of the vector unit (4 cycles per wave64 instruction at 2.4 GHz, 1 024 SIMDs) is quoted beside the HBM one.
-            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic_cfg5_r06.json')) as fp:
-                pmc = json.load(fp)
-            roofline['traffic'] = int(pmc['hbm_bytes_per_voxel'] * nvox)
-            roofline['traffic_source'] = 'profiles/pmc_traffic_cfg5_r06.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, per voxel x voxels)'
-            issue_s = (nvox / 256.0 / 1024.0) * pmc['valu_per_wave'] * 4.0 / 2.4e9
-            roofline['valu_issue_floor'] = {'valu_per_wave': round(pmc['valu_per_wave'], 1), 'salu_per_wave': round(pmc['salu_per_wave'], 1),
-                                            'floor_us': round(issue_s * 1e6, 1), 'frac_of_floor': round(issue_s / avg_s, 3),
-                                            'note': 'waves per SIMD x vector instructions per wave x 4 cycles / 2.4 GHz: what the vector unit '
-                                                    'alone needs for the instructions this kernel issues'}
-        except Exception:
-            pass
-    else:
-        achieved = 10 * VOL_ASSIGN_BYTES_PER_VOXEL * nvox / (slic_ms / 1e3) / 1e9 if slic_ms else 0.0
-        roofline = {'bound': 'hbm', 'kernel': 'whole 3-D SLIC stage (pre-processing, 10 x [scatter, k_vol_assign_f32, k_vol_update_f32], connectivity)',
-                    'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 5),
-                    'traffic': None, 'algorithmic_bytes': 10 * VOL_ASSIGN_BYTES_PER_VOXEL * nvox, 'stage_ms': round(slic_ms, 2)}
+    if full:
+        assign_ms, assign_n = stage_ms['slic_assign']
+        slic_ms = stage_ms['slic'][0]
+        if assign_n:           # the assignment kernel itself (HIP events on its dispatches), 8 B/voxel/sweep
+            avg_s = assign_ms / assign_n / 1e3
+            roofline = {'bound': 'hbm', 'kernel': 'k_vol_assign_f32 (3-D assignment, all sweeps)',
+                        'achieved': round(VOL_ASSIGN_BYTES_PER_VOXEL * nvox / avg_s / 1e9, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': round(VOL_ASSIGN_BYTES_PER_VOXEL * nvox / avg_s / 1e9 / HBM_PEAK_GBS, 5), 'traffic': None,
+                        'avg_kernel_us': round(avg_s * 1e6, 1), 'launches': assign_n,
+                        'algorithmic_bytes_per_launch': VOL_ASSIGN_BYTES_PER_VOXEL * nvox}
+            try:
+                # HBM bytes and instruction counts of the kernel from the committed rocprofv3 PMC passes (tools/c5_pmc.sh, a quarter
+                # volume with the same bricks and windows: per voxel, scaled to this volume).  HBM is not what bounds this kernel:
+                # ~60 search windows cover a voxel, a wave of 256 voxels issues ~1 350 vector + ~1 180 scalar instructions -- the floor
+                # of the vector unit (4 cycles per wave64 instruction at 2.4 GHz, 1 024 SIMDs) is quoted beside the HBM one.
+                with open(os.path.join(ROOT, 'profiles', 'pmc_traffic_cfg5_r06.json')) as fp:
+                    pmc = json.load(fp)
+                roofline['traffic'] = int(pmc['hbm_bytes_per_voxel'] * nvox)
+                roofline['traffic_source'] = 'profiles/pmc_traffic_cfg5_r06.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, per voxel x voxels)'
+                issue_s = (nvox / 256.0 / 1024.0) * pmc['valu_per_wave'] * 4.0 / 2.4e9
+                roofline['valu_issue_floor'] = {'valu_per_wave': round(pmc['valu_per_wave'], 1), 'salu_per_wave': round(pmc['salu_per_wave'], 1),
+                                                'floor_us': round(issue_s * 1e6, 1), 'frac_of_floor': round(issue_s / avg_s, 3),
+                                                'note': 'waves per SIMD x vector instructions per wave x 4 cycles / 2.4 GHz: what the vector unit '
+                                                        'alone needs for the instructions this kernel issues'}
+            except Exception:
+                pass
+        else:
+            achieved = 10 * VOL_ASSIGN_BYTES_PER_VOXEL * nvox / (slic_ms / 1e3) / 1e9 if slic_ms else 0.0
+            roofline = {'bound': 'hbm', 'kernel': 'whole 3-D SLIC stage (pre-processing, 10 x [scatter, k_vol_assign_f32, k_vol_update_f32], connectivity)',
+                        'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 5),
+                        'traffic': None, 'algorithmic_bytes': 10 * VOL_ASSIGN_BYTES_PER_VOXEL * nvox, 'stage_ms': round(slic_ms, 2)}
     out = {
         'metric': METRIC,
         'value': round(group.world * steps * nvox / elapsed / 1e6, 3), 'unit': 'Mpixels/s', 'n_gpus': group.world, 'steps': steps,
@@ -1420,21 +1489,24 @@ def bench_volume(args, group, shape=None, quick=False):
                    'volumes_in_flight_per_gpu': inflight,
                    'timing': 'steady state: %d warm-up + %d timed + %d cool-down volumes back to back on %d worker thread(s), clock from the '
                              'completion of step W to the completion of step W+K; latency_ms = one volume alone' % (warmup, steps, inflight, inflight),
-                   'bench_config': 5, 'classes_found': classes_found},
-        'roofline': roofline,
-        'stage_ms_per_step': {g: round(ms, 3) for g, (ms, n) in stage_ms.items()},
-        # (one volume alone: the whole call, its host-side fit, and the rest -- with volumes in flight the fit of one runs under the
-        # device work of the next, so `ms_per_step` is NOT their sum)
-        'host_model_fit_ms_per_step': round(latency_fit_ms, 1), 'ms_per_step_excluding_fit': round(latency_ms - latency_fit_ms, 1),
+                   'bench_config': 5},
         'host_model_fit_ms_in_flight': round(fit_ms, 1),      # (per step of the timed run, waiting for the other volume's fit included)
-        'volumes_in_flight': inflight, 'latency_ms': round(latency_ms, 1), 'latency_host_model_fit_ms': round(latency_fit_ms, 1),
+        'volumes_in_flight': inflight,
         'ms_per_step_incl_fill_drain': round(cold * 1e3, 1),
         'host_model_fit_threads': fit_threads,
         'host_model_fit': 'scikit-learn GaussianMixture(full, n_init=9) as graph_cuts.py:73-163 configures it; the restarts of its EM loop '
                           'run side by side (graph_cuts.fit_mixture_restarts: same random stream, same calls, parameters bit for bit '
                           'those of mixture.fit -- tests/test_class_models.py), %d worker threads' % __import__('pyimsegm_amd.graph_cuts', fromlist=['x'])._fit_workers(),
     }
-    if group.world == 1:
+    if full:
+        out['config']['classes_found'] = classes_found
+        out['roofline'] = roofline
+        out['stage_ms_per_step'] = {g: round(ms, 3) for g, (ms, n) in stage_ms.items()}
+        # (one volume alone: the whole call, its host-side fit, and the rest -- with volumes in flight the fit of one runs under the
+        # device work of the next, so `ms_per_step` is NOT their sum)
+        out.update({'host_model_fit_ms_per_step': round(latency_fit_ms, 1), 'ms_per_step_excluding_fit': round(latency_ms - latency_fit_ms, 1),
+                    'latency_ms': round(latency_ms, 1), 'latency_host_model_fit_ms': round(latency_fit_ms, 1)})
+    if full and group.world == 1:
         try:
             verdict = compare_config5(shape, pipe, vol=vol if group.rank == 0 else None)
             if verdict is not None:
@@ -1501,7 +1573,7 @@ def main():
     try:
         cfg = args.config or 2
         out = bench_volume(args, group) if cfg == 5 else bench_color2d(args, group, cfg)
-        if args.config is None and not args.no_other_configs and args.size is None:
+        if args.full and args.config is None and not args.no_other_configs and args.size is None:
             # the other BASELINE configurations, driver-timed in the same invocation (a few seconds each): config 4 at any N (the
             # configuration that shards over the GPUs), configs 3 and the reduced 5 on one GPU
             others = {}

@@ -31,7 +31,7 @@ def run_bench(nproc, steps, port, extra=(), launcher=False, size=('--size', '192
 def test_bench_control_flow_two_ranks_under_the_launcher():
     import pytest
     pytest.importorskip('torch')
-    d = run_bench(2, 9, 29631, launcher=True)
+    d = run_bench(2, 9, 29631, extra=['--full'], launcher=True)
     assert d['n_gpus'] == 2 and d['steps'] == 9 and d['warmup'] == 1 and d['scaling'] == 'weak'
     assert d['higher_is_better'] is True and d['vs_baseline'] is None and d['value'] > 0
     assert abs(d['value'] - 2 * 9 * 192 * 192 / (d['ms_per_step'] * 9 / 1e3) / 1e6) / d['value'] < 1e-3      # whole-job aggregate
@@ -51,7 +51,7 @@ def test_bench_batch_config_two_self_spawned_ranks():
     """`--gpus 2` without a launcher: bench.py starts its own ranks; config 4 with the group model of the reference's run, and
     rank 0 checks the CRC of EVERY gathered label map against that run (the oracle stands in for the kernels here, and it
     reproduces the reference's maps bit for bit)"""
-    d = run_bench(2, 3, 29633, extra=['--config', '4', '--input-ring', '1'], size=())
+    d = run_bench(2, 3, 29633, extra=['--config', '4', '--input-ring', '1', '--full'], size=())
     assert d['n_gpus'] == 2 and d['config']['bench_config'] == 4 and d['config']['images_per_step_per_gpu'] == 8
     assert abs(d['value'] - 2 * 3 * 8 * 647 * 1024 / (d['ms_per_step'] * 3 / 1e3) / 1e6) / d['value'] < 1e-3
     assert d['gathered_maps_checked'] == 16 and d['gathered_maps_equal_reference_run'] is True, d
@@ -70,7 +70,7 @@ def test_bench_eight_self_spawned_ranks_on_a_host_with_as_many_cpus():
     threads of a rank are cut to the CPUs it has, the hub serves eight connections, the input-staging probe runs on every rank at
     once): ONE JSON line, whole-job aggregate, every rank's own rate, staging choice and host-memory traffic in it, every gathered
     map checked against the map its sender holds"""
-    d = run_bench(8, 4, 29651, size=('--size', '128'), extra=['--probe-seconds', '0.2'])
+    d = run_bench(8, 4, 29651, size=('--size', '128'), extra=['--probe-seconds', '0.2', '--full'])
     assert d['n_gpus'] == 8 and d['steps'] == 4 and d['scaling'] == 'weak' and d['value'] > 0
     assert abs(d['value'] - 8 * 4 * 128 * 128 / (d['ms_per_step'] * 4 / 1e3) / 1e6) / d['value'] < 1e-3
     per_rank = d['per_rank']
@@ -79,3 +79,23 @@ def test_bench_eight_self_spawned_ranks_on_a_host_with_as_many_cpus():
     assert len(per_rank['host_memory_traffic_gb_per_s']) == 8 and all(v > 0 for v in per_rank['host_memory_traffic_gb_per_s'])
     assert d['gathered_maps_checked'] == 8 and d['gathered_maps_equal_senders_own'] is True
     assert 'cpu_baseline' not in d and 'other_configs' not in d or d.get('other_configs') is not None
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline of the timed steps and nothing measured apart (roofline, latency, baselines,
+    other configurations); --dump-outputs writes the class map of the last timed step as float32, the same map in every run"""
+    import numpy as np
+    maps = []
+    for k, steps in enumerate((5, 3)):
+        d = run_bench(1, steps, 0, extra=['--dump-outputs', str(tmp_path / str(k))])
+        assert d['n_gpus'] == 1 and d['steps'] == steps and d['warmup'] == 1 and d['unit'] == 'Mpixels/s' and d['dtype'] == 'f64'
+        assert d['higher_is_better'] is True and d['metric'] and d['ms_per_step'] > 0
+        assert abs(d['value'] - 192 * 192 / (d['ms_per_step'] / 1e3) / 1e6) / d['value'] < 1e-3
+        for key in ('other_configs', 'roofline', 'stage_ms_per_step', 'latency_ms', 'host_link', 'fit_inclusive', 'cpu_baseline',
+                    'gpu_equals_reference_run'):
+            assert key not in d, key
+        assert sorted(os.listdir(str(tmp_path / str(k)))) == ['segm.npy']
+        segm = np.load(str(tmp_path / str(k) / 'segm.npy'))
+        assert segm.dtype == np.float32 and segm.shape == (192, 192) and set(np.unique(segm)) <= {0., 1., 2.}
+        maps.append(segm)
+    assert np.array_equal(maps[0], maps[1])

@@ -138,7 +138,7 @@ def test_eight_rank_host_plane(tmp_path):
     assert 'RANK0_OK' in outs[0][0]
 
 
-def test_control_plane_rejects_stray_connections(tmp_path):
+def test_control_plane_rejects_stray_connections(tmp_path, monkeypatch):
     """a connection that announces a rank outside 1..world-1 (or one that is taken) is dropped, the job still forms"""
     import socket
     import struct
@@ -146,7 +146,9 @@ def test_control_plane_rejects_stray_connections(tmp_path):
     import time
     sys.path.insert(0, ROOT)
     from pyimsegm_amd.distributed import _Star
-    path = str(tmp_path / 'hub.sock')
+    # (a name relative to tmp_path: a Unix socket's path is limited to ~108 bytes, and tmp_path can be longer than that)
+    monkeypatch.chdir(tmp_path)
+    path = 'hub.sock'
     os.environ['IMSEGM_COMM_SOCKET'] = path
     try:
         hub = {}

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out/prof_r06
 rm -rf $OUT && mkdir -p $OUT
 cd $REPO
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err; echo "bench (driver's arguments) rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err; echo "bench (driver's arguments) rc=$?"
 python - <<'P'
 import json
 d=json.loads(open('/root/repo/gpurun_out/prof_r06/bench_driver_args.json').read().strip().splitlines()[-1])
