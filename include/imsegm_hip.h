@@ -111,7 +111,8 @@ IMSEGM_API int imsegm_image2d_slic(imsegm_image2d *img, int minmax_normalize, in
 /* copy the current label map to the host as int64 (dtype leaked by skimage, superpixels.py:69) */
 IMSEGM_API int imsegm_image2d_get_labels(imsegm_image2d *img, int64_t *labels_out);
 /* install an arbitrary label map (int32, values in [0, n_labels)) -- stage-level entry for the
- * descriptor / graph functions that take a user segmentation */
+ * descriptor / graph functions that take a user segmentation.  The range is not checked here (the kernels index per-label
+ * tables with the labels): callers check it (pyimsegm_amd._hip.Image2D.set_labels raises ValueError) */
 IMSEGM_API int imsegm_image2d_set_labels(imsegm_image2d *img, const int32_t *labels, int n_labels);
 /* Diagnostic (no reference counterpart): how many 2-D connectivity passes of this process could not be finished by the
  * tile path of csrc/connectivity.hip and were redone by the general one (results are identical; tests use it to make sure
@@ -348,7 +349,8 @@ IMSEGM_API int imsegm_batch2d_run_color(imsegm_batch2d *batch, int n_images, con
                                         int max_iter, int start_label, int feature_mask, const imsegm_gmm *gmm, int n_classes,
                                         const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
                                         const int32_t *classes_lut, int32_t *const *segm_out, int *n_labels_out);
-/* device address of a result of image `image` of the last batch: which = 0 label map, 1 segmentation (int32 H x W each) */
+/* device address of a result of image `image` of the last batch: which = 0 label map, 1 segmentation (int32 H x W each),
+ * 2 feature table (float64, n_labels_out[image] rows of 3 x (number of feature_mask bits) columns: mean | std | energy) */
 IMSEGM_API int imsegm_batch2d_device_ptr(imsegm_batch2d *batch, int image, int which, void **ptr_out);
 
 /* The 'median' and 'meanGrad' statistics of compute_image2d_color_statistic / compute_image3d_gray_statistic

@@ -667,6 +667,9 @@ class Image2D(object):
             raise ValueError('labels must be non-negative')
         if n_labels is None:
             n_labels = int(labels.max()) + 1
+        elif labels.size and int(labels.max()) >= n_labels:
+            # (the per-label tables of the kernels have n_labels rows: a larger label would write past them)
+            raise ValueError('label %d is out of range for n_labels = %d' % (int(labels.max()), n_labels))
         _check(load_library().imsegm_image2d_set_labels(self._h, _ptr(labels), int(n_labels)))
         self.n_labels = int(n_labels)
         return self
@@ -1136,6 +1139,7 @@ class Batch2D(object):
             dst, counts))
         self.n_labels = list(counts)
         self.n_images = n
+        self._feature_columns = 3 * bin(mask).count('1')
         self._uploaded = images         # page-locked sources are read asynchronously (the call ends with a synchronisation)
         return segm
 
@@ -1151,6 +1155,16 @@ class Batch2D(object):
     def labels_device_array(self, image):
         """the superpixel map of image ``image`` of the last batch (int32 H x W) as a device array"""
         return self._device_array(image, 0)
+
+    def get_features(self, image):
+        """feature table of image ``image`` of the last batch on the host (float64 n_labels x F, columns mean | std | energy as
+        ``feature_flags`` asked for)"""
+        ptr = _vp()
+        _check(load_library().imsegm_batch2d_device_ptr(self._h, int(image), 2, C.byref(ptr)))
+        out = np.empty((self.n_labels[image], self._feature_columns), dtype=np.float64)
+        if out.size:
+            self.ctx.copy(out.ctypes.data, ptr.value, out.nbytes, synchronize=True)
+        return out
 
     def get_labels(self, image):
         """superpixel map of image ``image`` of the last batch on the host (int64, the dtype scikit-image leaks)"""

@@ -179,7 +179,8 @@ int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *
     float *d_mean32 = reinterpret_cast<float *>(b);
     int sp = ctx->begin(PG_STATS);
     int rc;
-    if (im->is_volume)      // the gray plane read as all three channels (plane stride 0), the volume as a (D*H) x W image
+    if (im->is_volume)      // the one-channel kernel on the gray plane (plane stride 0), the volume as a (D*H) x W image; its
+                            // finalisation copies the gray statistics into all three channels: [m m m | s s s | e e e]
         rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->D * im->H, im->W, K, maxabs, (feature_mask & 2) != 0,
                                 acc, d_mean, d_energy, d_var, d_mean32, st, 1, 0, 1.0, 1.0, 0);
     else

@@ -185,8 +185,8 @@ int imsegm_image2d_lm_features_sep(imsegm_image2d *im, const double *weights, co
         for (int j = 0; j < cnt; ++j)
             if (!(fused_ssq && has_sep[j]) && launch_response_sumsq(resp + (size_t)j * 3 * n, 3 * n, partial, d_ssq + b0 + j, st)) return -1;
         ctx->end(spx);
-        // |r| <= norm  =>  |r * mul / div| <= mul = log(1 + norm) / 0.03 < 2^15 for every finite norm: the bound the fixed-point
-        // scales are chosen for, without the norm coming to the host (prescale 2: the kernels derive mul and div from *ssq)
+        // |r| <= norm  =>  |r * mul / div| <= mul = log(1 + norm) / 0.03: the bound the fixed-point scales follow, without the norm
+        // coming to the host (prescale 2: the kernels derive mul, div and the scales from *ssq; the 32768 > mul below is unused)
         int sps = ctx->begin(PG_STATS);
         for (int j = 0; j < cnt; ++j) {
             const int b = b0 + j;

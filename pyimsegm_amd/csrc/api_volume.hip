@@ -230,8 +230,7 @@ int imsegm_volume_gray_stats(imsegm_image2d *im, double *mean_out, double *energ
         maxabs = std::max(fabs(mm[0]), fabs(mm[1]));
         if (!(maxabs < 1e300)) maxabs = 1e300;
     }
-    // the colour kernel with the single gray plane read as all three channels (plane stride 0), the
-    // volume seen as a (D*H) x W image
+    // the one-channel kernel on the single gray plane (plane stride 0), the volume seen as a (D*H) x W image
     const int K = im->n_labels;
     std::vector<double> m((size_t)K * 3), e((size_t)K * 3), v((size_t)K * 3);
     const int H2 = im->D * im->H;

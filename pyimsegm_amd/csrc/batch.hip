@@ -169,8 +169,9 @@ int imsegm_batch2d_device_ptr(imsegm_batch2d *bt, int image, int which, void **p
     unsigned char *base = bt->arena.as<unsigned char>() + (size_t)image * bt->slice;
     if (which == 0) *ptr_out = base + L.labels;
     else if (which == 1) *ptr_out = base + L.segm_out;
+    else if (which == 2) *ptr_out = base + L.featK;
     else {
-        set_error("batch2d_device_ptr: which = 0 (label map) or 1 (segmentation)");
+        set_error("batch2d_device_ptr: which = 0 (label map), 1 (segmentation) or 2 (feature table)");
         return -1;
     }
     return 0;
@@ -349,21 +350,16 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
         double *d_energy = reinterpret_cast<double *>(fb); fb += (size_t)L.Kb * 3 * 8;
         double *d_var = reinterpret_cast<double *>(fb); fb += (size_t)L.Kb * 3 * 8;
         float *d_mean32 = reinterpret_cast<float *>(fb);
-        double maxabs = 255.0;
+        const double *mm_dev = nullptr;
         if (dtype != IMSEGM_U8) {
-            // float images: the fixed-point scale of the sums follows the largest magnitude over the batch
+            // float images: the fixed-point scale of the sums follows each image's own largest magnitude (its min / max on the
+            // device, read by the statistics kernels of that image: a dim image next to a bright one keeps its precision)
             if (launch_minmax(base + L.img, dtype, n * 3, keys, minmax, st, nullptr, zb)) return -1;
-            if (launch_copy_rows(stage_dev, 16, minmax, slice, 16, n_images, st)) return -1;
-            std::vector<double> mm((size_t)2 * n_images);
-            HIP_TRY(hipMemcpyAsync(mm.data(), stage_dev, (size_t)16 * n_images, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            maxabs = 0.0;
-            for (double v : mm) maxabs = std::max(maxabs, fabs(v));
-            if (!(maxabs < 1e300)) maxabs = 1e300;
+            mm_dev = minmax;
         }
         const int sps = ctx->begin(PG_STATS);
-        if (launch_color_stats(base + L.img, dtype, labels, H, W, K_cap, maxabs, (feature_mask & 2) != 0, acc, d_mean, d_energy, d_var,
-                               d_mean32, st, 0, 0, 1.0, 1.0, -1, nullptr, zb))
+        if (launch_color_stats(base + L.img, dtype, labels, H, W, K_cap, 255.0, (feature_mask & 2) != 0, acc, d_mean, d_energy, d_var,
+                               d_mean32, st, 0, 0, 1.0, 1.0, -1, nullptr, zb, mm_dev))
             return -1;
         if (launch_features_assemble(d_mean, d_energy, d_var, K_cap, feature_mask, reinterpret_cast<double *>(base + L.featK), st, 0, 0, zb))
             return -1;

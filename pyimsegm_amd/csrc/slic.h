@@ -194,7 +194,8 @@ int launch_label_hist(const int32_t *labels, const int32_t *annot, size_t n, int
 int launch_color_stats(const void *img, int dtype, const int32_t *labels, int H, int W, int K, double maxabs,
                        int want_var, long long *acc, double *mean_out, double *energy_out, double *var_out,
                        float *mean32_scratch, hipStream_t st, int planar = 0, int prescale = 0, double mul = 1.0,
-                       double div = 1.0, long plane_stride = -1, const double *ssq_dev = nullptr, ZBatch zb = ZBatch());
+                       double div = 1.0, long plane_stride = -1, const double *ssq_dev = nullptr, ZBatch zb = ZBatch(),
+                       const double *minmax_dev = nullptr);
 
 // texture.hip -------------------------------------------------------------------------------------
 // the separable kernels of one battery: `groups` kernels of `rank` components (per component the x taps then the y taps of the

@@ -6,11 +6,18 @@
 // (descriptors.py:233,261,293), `val * val` and `(img - mean)^2` are evaluated in float32 and
 // accumulated in 64-bit; labels without pixels keep 0.
 //
-// The reference adds in raster order into an fp64 scalar.  Here every float32 term is converted to
-// an exact two-limb fixed-point integer and summed with integer adds (associative), so the result
-// does not depend on the reduction tree or on atomic ordering; it equals the exactly rounded sum,
-// which differs from the reference's running fp64 sum by at most a few ulp (bit-identical whenever
-// the terms are integers, e.g. uint8 images: mean and energy).
+// The reference adds in raster order into an fp64 scalar.  Here every float32 term t is cut to a two-limb fixed-point integer,
+// t * 2^sh = hi + lo * 2^-32 (both limbs truncated toward zero), and summed with integer adds (associative), so the result does
+// not depend on the reduction tree or on atomic ordering.  Precision contract (pow2_scale picks sh per image from the pixel count
+// N < 2^e_n and the largest magnitude M < 2^e_m of the terms: M = maxabs for the value sums, 4 maxabs^2 for the squared and the
+// deviation sums; sh = min(62 - e_n - e_m, 44 - e_m)):
+//   - a term of magnitude >= 2^-(sh+9) lies on the grid 2^-(sh+32) and is taken exactly; when every term of a label is, the
+//     per-label result is the exact sum rounded to fp64 and divided by the count (bit-identical to the reference whenever the
+//     terms are integers, e.g. uint8 images: mean and energy);
+//   - otherwise the absolute error of a label's mean / energy / variance is below B = 2^-(sh+32), which is at most 2^-70 M for
+//     images of <= 2^22 pixels (N < 2^23 -> sh >= 39 - e_m, and 2^(e_m - 1) <= M).
+// The grid follows M up AND down (no clamp of M to 1): the statistics of a dim image are as precise, relative to its values,
+// as those of a bright one.  A batch (ZBatch) picks sh per image from that image's own min / max.
 #include "slic.h"
 
 namespace imsegm {
@@ -42,7 +49,44 @@ struct StatParams {
     double mul, div;              //    (descriptors.py:1094 `(response * (log(1 + norm) / 0.03)) / norm`)
     const double *ssq_dev;        // prescale == 2: norm = sqrt(*ssq_dev) on the device, mul and div derived from it (0 / inf norm: all values 0)
     size_t zs;                    // several images per launch (ZBatch): image blockIdx.z, every buffer zs bytes further on per image
+    const double *minmax;         // non-null: (min, max) of the image's values (per image, zs further on), the scales derived from it
 };
+
+// largest power of two 2^sh with n_pixels * maxabs * 2^sh < 2^62 (int64 accumulators) and 256 * maxabs * 2^sh < 2^52 (exact fp64
+// sums of the 256 terms of a 16-lane row); follows frexp(maxabs) in both directions (maxabs = 0: any scale holds, that of 1).
+// No further cap: the uint8 product toti * scale of the integer block sums is < 2^52 by the second bound (toti <= 256 * maxabs)
+__host__ __device__ inline double pow2_scale(double n_pixels, double maxabs)
+{
+    int e_n, e_m;
+    frexp(n_pixels, &e_n);
+    frexp(maxabs > 0.0 ? maxabs : 1.0, &e_m);
+    int sh = 62 - e_n - e_m;
+    if (sh > 44 - e_m) sh = 44 - e_m;
+    return ldexp(1.0, sh);
+}
+
+__host__ __device__ inline void stat_scales(double n_pixels, double maxabs, double &scale_v, double &scale_e)
+{
+    if (!(maxabs < 1e300)) maxabs = 1e300;
+    scale_v = pow2_scale(n_pixels, maxabs);
+    scale_e = pow2_scale(n_pixels, 4.0 * maxabs * maxabs);
+}
+
+// the scales of this image (blockIdx.z; sp.minmax and sp.ssq_dev already shifted to it): its own min / max when the launch
+// carries them; with the L2 norm on the device (prescale 2) the bound |value| <= mul = log(1 + norm) / 0.03 of that norm; else
+// the launch's
+__device__ __forceinline__ void image_scales(const StatParams &sp, double &scale_v, double &scale_e)
+{
+    scale_v = sp.scale_v;
+    scale_e = sp.scale_e;
+    if (sp.minmax) {
+        stat_scales((double)sp.n_pixels, fmax(fabs(sp.minmax[0]), fabs(sp.minmax[1])), scale_v, scale_e);
+    } else if (sp.prescale == 2) {
+        const double norm = sqrt(*sp.ssq_dev);
+        const bool dead = !(norm > 0.0) || norm > DBL_MAX;
+        stat_scales((double)sp.n_pixels, dead ? 0.0 : fabs(log(1.0 + norm) / 0.03), scale_v, scale_e);
+    }
+}
 
 // PASS 1 -> n + 3 x (v, v*v); PASS 2 -> 3 x (v - m)^2.
 // One pixel column per lane and ST_ROWS rows; every 16-lane row of the wave (a 16 x 16 pixel block, two to
@@ -65,6 +109,9 @@ k_color_stats(const T *__restrict__ img, const int32_t *__restrict__ labels, Sta
 {
     constexpr int RW = StatRows<T, NC, PASS>::value;
     ZSHIFT(img, sp.zs); ZSHIFT(labels, sp.zs); ZSHIFT(mean32, sp.zs); ZSHIFT(acc, sp.zs); ZSHIFT(sp.ssq_dev, sp.zs);
+    ZSHIFT(sp.minmax, sp.zs);
+    double scale_v, scale_e;
+    image_scales(sp, scale_v, scale_e);
     constexpr int NQ = (PASS == 1) ? 13 : 6;
     __shared__ int keys[ST_SLOTS];
     __shared__ long long lacc[ST_SLOTS][13];
@@ -118,8 +165,8 @@ k_color_stats(const T *__restrict__ img, const int32_t *__restrict__ labels, Sta
         for (int r = 0; r < RW; ++r) {
             const float val = v[r][0];
             const float term = __fmul_rn(val, val);
-            const double t = (double)term * sp.scale_e, h = trunc(t);
-            const double tv = (double)val * sp.scale_v, hv = trunc(tv);
+            const double t = (double)term * scale_e, h = trunc(t);
+            const double tv = (double)val * scale_v, hv = trunc(tv);
             limb[r][0] = hv;
             limb[r][1] = trunc((tv - hv) * 4294967296.0);
             limb[r][2] = h;
@@ -164,7 +211,7 @@ k_color_stats(const T *__restrict__ img, const int32_t *__restrict__ labels, Sta
                 // accumulator columns: [0] count, [1 + 2c] high limb of the value sums, [7 + 2c] of the squared sums
                 const int col = j == 0 ? 0 : (j < 4 ? 1 + 2 * (j - 1) : 7 + 2 * (j - 4));
                 const long long tot = j == 0 ? (long long)toti
-                                             : (long long)toti * (long long)(j < 4 ? sp.scale_v : sp.scale_e);
+                                             : (long long)toti * (long long)(j < 4 ? scale_v : scale_e);
                 if (slot >= 0) atomic_add_i64(&lacc[slot][col], tot);
                 else atomic_add_i64(acc + (size_t)k * 13 + col, tot);
             }
@@ -208,7 +255,7 @@ k_color_stats(const T *__restrict__ img, const int32_t *__restrict__ labels, Sta
                     const float d = __fsub_rn(v[r][0], m32);
                     float term = __fmul_rn(d, d);
                     asm volatile("" : "+v"(term));
-                    const double t = (double)term * sp.scale_e, h = trunc(t);
+                    const double t = (double)term * scale_e, h = trunc(t);
                     q[0] += h;
                     q[1] += trunc((t - h) * 4294967296.0);
                 }
@@ -252,7 +299,7 @@ k_color_stats(const T *__restrict__ img, const int32_t *__restrict__ labels, Sta
                     // (the limbs are formed HERE, per label pass: hoisted out of the pass loop as loop invariants -- what the
                     // optimiser does when it can see through -- they are 4 x 3 x RW doubles, 400+ registers, one wave per SIMD)
                     asm volatile("" : "+v"(term));
-                    const double t = (double)term * ((PASS == 1 && round == 0) ? sp.scale_v : sp.scale_e), h = trunc(t);
+                    const double t = (double)term * ((PASS == 1 && round == 0) ? scale_v : scale_e), h = trunc(t);
                     q[2 * c] += h;
                     q[2 * c + 1] += trunc((t - h) * 4294967296.0);
                 }
@@ -304,13 +351,18 @@ __global__ void k_stats_finalize1(long long *__restrict__ acc, StatParams sp, do
                                   float *mean32)
 {
     ZSHIFT(acc, sp.zs); ZSHIFT(mean_out, sp.zs); ZSHIFT(energy_out, sp.zs); ZSHIFT(mean32, sp.zs);
+    ZSHIFT(sp.ssq_dev, sp.zs); ZSHIFT(sp.minmax, sp.zs);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= sp.K) return;
+    double scale_v, scale_e;
+    image_scales(sp, scale_v, scale_e);
     long long *a = acc + (size_t)k * 13;
     long long n = a[0];
+    const bool gray = sp.planar && sp.plane_stride == 0 && !sp.prescale;   // one gray plane: channel 0, replicated into 1 and 2
     for (int c = 0; c < 3; ++c) {
-        double sv = (i64_to_double(a[1 + 2 * c]) + i64_to_double(a[2 + 2 * c]) * (1.0 / 4294967296.0)) / sp.scale_v;
-        double se = (i64_to_double(a[7 + 2 * c]) + i64_to_double(a[8 + 2 * c]) * (1.0 / 4294967296.0)) / sp.scale_e;
+        const int s = gray ? 0 : c;
+        double sv = (i64_to_double(a[1 + 2 * s]) + i64_to_double(a[2 + 2 * s]) * (1.0 / 4294967296.0)) / scale_v;
+        double se = (i64_to_double(a[7 + 2 * s]) + i64_to_double(a[8 + 2 * s]) * (1.0 / 4294967296.0)) / scale_e;
         double m = n > 0 ? sv / (double)n : 0.0;
         double e = n > 0 ? se / (double)n : 0.0;
         if (mean_out) mean_out[3 * k + c] = m;
@@ -322,13 +374,17 @@ __global__ void k_stats_finalize1(long long *__restrict__ acc, StatParams sp, do
 
 __global__ void k_stats_finalize2(const long long *__restrict__ acc, StatParams sp, double *var_out)
 {
-    ZSHIFT(acc, sp.zs); ZSHIFT(var_out, sp.zs);
+    ZSHIFT(acc, sp.zs); ZSHIFT(var_out, sp.zs); ZSHIFT(sp.ssq_dev, sp.zs); ZSHIFT(sp.minmax, sp.zs);
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= sp.K) return;
+    double scale_v, scale_e;
+    image_scales(sp, scale_v, scale_e);
     const long long *a = acc + (size_t)k * 13;
     long long n = a[0];
+    const bool gray = sp.planar && sp.plane_stride == 0 && !sp.prescale;
     for (int c = 0; c < 3; ++c) {
-        double s = (i64_to_double(a[7 + 2 * c]) + i64_to_double(a[8 + 2 * c]) * (1.0 / 4294967296.0)) / sp.scale_e;
+        const int j = gray ? 0 : c;
+        double s = (i64_to_double(a[7 + 2 * j]) + i64_to_double(a[8 + 2 * j]) * (1.0 / 4294967296.0)) / scale_e;
         var_out[3 * k + c] = n > 0 ? s / (double)n : 0.0;
     }
 }
@@ -352,23 +408,10 @@ static void launch_pass(int pass, const T *img, const int32_t *labels, StatParam
         hipLaunchKernelGGL((k_color_stats<T, 2, false>), grid, 256, 0, st, img, labels, sp, mean32, acc);
 }
 
-static double pow2_scale(double n_pixels, double maxabs)
-{
-    // largest power of two with n_pixels * maxabs * scale < 2^62 (int64 accumulators) and
-    // 256 * maxabs * scale < 2^52 (exact fp64 sums inside one wave), capped at 2^30
-    int e_n, e_m;
-    frexp(n_pixels, &e_n);
-    frexp(maxabs > 1.0 ? maxabs : 1.0, &e_m);
-    int sh = 62 - e_n - e_m;
-    if (sh > 44 - e_m) sh = 44 - e_m;
-    if (sh > 30) sh = 30;
-    return ldexp(1.0, sh);
-}
-
 int launch_color_stats(const void *img, int dtype, const int32_t *labels, int H, int W, int K, double maxabs,
                        int want_var, long long *acc, double *mean_out, double *energy_out, double *var_out,
                        float *mean32_scratch, hipStream_t st, int planar, int prescale, double mul, double div,
-                       long plane_stride, const double *ssq_dev, ZBatch zb)
+                       long plane_stride, const double *ssq_dev, ZBatch zb, const double *minmax_dev)
 {
     StatParams sp;
     sp.zs = zb.zs;
@@ -377,8 +420,8 @@ int launch_color_stats(const void *img, int dtype, const int32_t *labels, int H,
     sp.n_pixels = (size_t)H * W;
     sp.planar = planar; sp.prescale = prescale; sp.mul = mul; sp.div = div; sp.ssq_dev = ssq_dev;
     sp.plane_stride = plane_stride >= 0 ? (size_t)plane_stride : (size_t)H * W;
-    sp.scale_v = pow2_scale((double)H * W, maxabs);
-    sp.scale_e = pow2_scale((double)H * W, 4.0 * maxabs * maxabs);
+    sp.minmax = minmax_dev;
+    stat_scales((double)H * W, maxabs, sp.scale_v, sp.scale_e);
     sp.u8_int = (dtype == DT_U8 && !prescale && sp.scale_v >= 1.0 && sp.scale_e >= 1.0) ? 1 : 0;
     const dim3 kgrid(cdiv(K, 256), 1, nz);
     hipLaunchKernelGGL(k_stats_clear, kgrid, 256, 0, st, acc, K, 0, 13, zb.zs);

@@ -213,6 +213,24 @@ def test_texture_on_device_matches_scipy(shape, bank, dtype):
     assert np.max(np.abs(fts - ref)) < 1e-5 * max(scale, 1.0), np.max(np.abs(fts - ref))
 
 
+@pytest.mark.parametrize('k', [0, 10, 20])
+def test_texture_at_low_contrast(k):
+    """img * 2^-k: the responses (and their statistics) shrink with the contrast, the fixed-point grid of the statistics has to
+    follow them -- per column, error <= 1e-6 of the column's largest magnitude at every k"""
+    from pyimsegm_amd import descriptors as D
+    rng = np.random.default_rng(21)
+    img = rng.random((70, 90, 3)) * 2.0 ** -k
+    seg = (np.arange(70)[:, None] // 14) * 4 + np.arange(90)[None, :] // 25
+    flags = ['mean', 'std', 'energy']
+    fts, _ = D.compute_texture_desc_lm_img2d_clr(img, seg, flags, bank_type='short')
+    ref = _lm_host_reference(img, seg, flags, 'short')
+    assert fts.shape == ref.shape
+    scale = np.abs(ref).max(axis=0)
+    assert np.all(scale > 0)
+    err = np.abs(fts - ref).max(axis=0)
+    assert np.all(err <= 1e-6 * scale), (np.argmax(err / scale), np.max(err / scale))
+
+
 @pytest.mark.parametrize('flags', [('mean', 'std', 'energy'), ('std', ), ('energy', 'mean')])
 def test_texture_one_call_equals_battery_by_battery(flags, monkeypatch):
     """imsegm_image2d_lm_features (all batteries in one call, the L2 norm of a battery stays on the device) against the

@@ -96,6 +96,30 @@ def test_batch_of_float64_images(hip):
     assert all(np.array_equal(x, y) for x, y in zip(both, single))
 
 
+def test_batch_of_images_of_very_different_magnitude(hip):
+    """[img, img * 2^-30, img * 2^20]: the fixed-point scale of the statistics is each image's own, so every image's feature
+    table (imsegm_batch2d_device_ptr which = 2) equals its single-image table bit for bit, and so does its segmentation"""
+    from pyimsegm_amd import pipelines as pipe
+    from pyimsegm_amd.descriptors import FEATURES_SET_COLOR
+    from pyimsegm_amd.utilities.synthetic import voronoi_image
+    img = voronoi_image(120, 160, seed=5).astype(np.float64) / 255.
+    images = [img, img * 2.0 ** -30, img * 2.0 ** 20]
+    model = _model(images[:1], 14, 0.25)
+    single, tables = [], []
+    for im in images:
+        got = pipe._segment_color2d_one_call(im, model, FEATURES_SET_COLOR, 14, 0.25, 2.0, 'model', want_soft=False,
+                                             with_session=lambda s: tables.append(s.get_features(9)))
+        single.append(np.array(got[0]))
+    batched = []
+    both = _batched(images, model, 14, 0.25, keep=lambda b: batched.extend(b.get_features(i) for i in range(len(images))))
+    for i in range(len(images)):
+        assert batched[i].shape == tables[i].shape and tables[i].shape[1] == 9, i
+        assert np.array_equal(batched[i], tables[i]), i
+        assert np.array_equal(both[i], single[i]), i
+    # (the three label maps agree: SLIC normalises by min / max, so the tables differ by the power of two alone)
+    assert np.array_equal(tables[1][:, :3], tables[0][:, :3] * 2.0 ** -30)
+
+
 def test_batch_with_a_map_that_leaves_the_tile_path(hip):
     """one image of the batch is noise under a weak regularisation: its k-means assignment falls into more local components per
     64 x 32 tile than the tile path of the connectivity stage has slots for, so THAT image goes through the general path alone

@@ -78,6 +78,39 @@ def test_color2d_matches_reference_pyx(oracle, ref_cython, shape, K, dtype):
     assert np.array_equal(oracle.color2d_variance(img, seg, mean_ref.astype(np.float32)), var_ref)
 
 
+def _mixed_range_image(rng, shape):
+    """regions at 1, 2^-16 and 2^-40 and a near-constant region whose deviations are a few float32 ulp"""
+    img = rng.uniform(0.5, 1.0, shape + (3,))
+    h = shape[0] // 4
+    img[h:2 * h] *= 2.0 ** -16
+    img[2 * h:3 * h] *= 2.0 ** -40
+    img[3 * h:] = 0.75 + rng.integers(-3, 4, img[3 * h:].shape) * 2.0 ** -24
+    return img.astype(np.float32)
+
+
+@pytest.mark.parametrize('k', [-30, -20, -12, -4, 0, 4, 12, 20, 40, 60, 'mixed'])
+def test_color2d_matches_reference_pyx_across_scales(oracle, ref_cython, k):
+    """the oracle the GPU statistics are checked against stays bit-exact with the reference's native code for values far
+    from 1 (2^k, signed and unsigned) and for one image mixing such magnitudes"""
+    if ref_cython is None:
+        pytest.skip('oracle/_ref not built (reference tree absent)')
+    rng = np.random.default_rng(5)
+    shape = (61, 47)
+    seg = rng.integers(0, 23, (shape[0] // 4 + 1, shape[1] // 4 + 1)).repeat(4, 0).repeat(4, 1)[:shape[0], :shape[1]]
+    seg = seg.astype(np.int32)
+    if k == 'mixed':
+        images = [_mixed_range_image(rng, shape)]
+    else:
+        signed = rng.uniform(2.0 ** -20, 1.0, shape + (3,)) * rng.choice([-1.0, 1.0], shape + (3,))
+        images = [(rng.uniform(0.5, 1.0, shape + (3,)) * 2.0 ** k).astype(np.float32), (signed * 2.0 ** k).astype(np.float32)]
+    for img in images:
+        mean_ref = np.array(ref_cython.computeColorImage2dMean(img, seg))
+        m32 = mean_ref.astype(np.float32)
+        assert np.array_equal(oracle.color2d_mean(img, seg), mean_ref)
+        assert np.array_equal(oracle.color2d_energy(img, seg), np.array(ref_cython.computeColorImage2dEnergy(img, seg)))
+        assert np.array_equal(oracle.color2d_variance(img, seg, m32), np.array(ref_cython.computeColorImage2dVariance(img, seg, m32)))
+
+
 def test_gray3d_matches_reference_pyx(oracle, ref_cython):
     if ref_cython is None:
         pytest.skip('oracle/_ref not built (reference tree absent)')
