@@ -208,6 +208,13 @@ IMSEGM_API int imsegm_image2d_lm_battery(imsegm_image2d *img, const double *weig
                                          double clip, double *sum_squares_out);
 IMSEGM_API int imsegm_image2d_response_stats(imsegm_image2d *img, double mul, double div, double *mean_out,
                                              double *energy_out, double *var_out);
+/* response_median / response_mean_gradient: per superpixel (K x 3; a volume: K) the median of (response * mul) / div (NaN for
+ *   a label without pixels) and the mean of np.sum(np.gradient(plane), axis=0) of that normalised response per channel plane
+ *   (a volume: per slice), float32 staging as the other means -- the 'median' / 'meanGrad' columns of :1096 on the device.
+ *   mul >= 0, div > 0; the gradient needs H, W >= 2.  Neither changes the prepared planes, the response, the uploaded image,
+ *   the resident feature table or a prepared graph: the next lm_battery runs without another lm_prepare. */
+IMSEGM_API int imsegm_image2d_response_median(imsegm_image2d *img, double mul, double div, double *median_out);
+IMSEGM_API int imsegm_image2d_response_mean_gradient(imsegm_image2d *img, double mul, double div, double *mean_out);
 /* inspection for the parity tests: the current filter response as [3][H][W] planes */
 IMSEGM_API int imsegm_image2d_get_response(imsegm_image2d *img, double *planes_out);
 

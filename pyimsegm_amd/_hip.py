@@ -129,6 +129,8 @@ _SIGNATURES = {
     'imsegm_image2d_lm_features_sep': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
     'imsegm_image2d_lm_battery': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     'imsegm_image2d_response_stats': (C.c_int, [_vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    'imsegm_image2d_response_median': (C.c_int, [_vp, C.c_double, C.c_double, _vp]),
+    'imsegm_image2d_response_mean_gradient': (C.c_int, [_vp, C.c_double, C.c_double, _vp]),
     'imsegm_image2d_get_response': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_device_ptr': (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     'imsegm_volume_create': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
@@ -901,6 +903,18 @@ class Image2D(object):
         _check(load_library().imsegm_image2d_response_stats(self._h, float(mul), float(div), _ptr(m), _ptr(e), _ptr(v)))
         return m, e, v
 
+    def response_median(self, mul, div):
+        """per-label median of the normalised response (response * mul) / div: K x 3 (NaN for a label without pixels)"""
+        out = np.empty((self.n_labels, 3), dtype=np.float64)
+        _check(load_library().imsegm_image2d_response_median(self._h, float(mul), float(div), _ptr(out)))
+        return out
+
+    def response_mean_gradient(self, mul, div):
+        """per-label mean of ``np.sum(np.gradient(plane), axis=0)`` of the normalised response, per channel: K x 3"""
+        out = np.empty((self.n_labels, 3), dtype=np.float64)
+        _check(load_library().imsegm_image2d_response_mean_gradient(self._h, float(mul), float(div), _ptr(out)))
+        return out
+
     def get_response(self):
         out = np.empty((3, ) + self.shape, dtype=np.float64)
         _check(load_library().imsegm_image2d_get_response(self._h, _ptr(out)))
@@ -1062,6 +1076,18 @@ class Volume3D(Image2D):
         v = np.empty(k, dtype=np.float64) if var else None
         _check(load_library().imsegm_image2d_response_stats(self._h, float(mul), float(div), _ptr(m), _ptr(e), _ptr(v)))
         return m, e, v
+
+    def response_median(self, mul, div):
+        """per-supervoxel median of the normalised response (response * mul) / div: K (NaN for a label without voxels)"""
+        out = np.empty(self.n_labels, dtype=np.float64)
+        _check(load_library().imsegm_image2d_response_median(self._h, float(mul), float(div), _ptr(out)))
+        return out
+
+    def response_mean_gradient(self, mul, div):
+        """per-supervoxel mean of ``np.sum(np.gradient(slice), axis=0)`` of the normalised response (never along z): K"""
+        out = np.empty(self.n_labels, dtype=np.float64)
+        _check(load_library().imsegm_image2d_response_mean_gradient(self._h, float(mul), float(div), _ptr(out)))
+        return out
 
     def get_response(self):
         out = np.empty(self.shape, dtype=np.float64)

@@ -148,7 +148,9 @@ int imsegm_image2d_median(imsegm_image2d *im, double *median_out)
     im->tex_ready = false;
     double *d_out = im->tex_resp.as<double>();
     unsigned char *scratch = im->tex_resp.as<unsigned char>() + ((ob + 255) & ~(size_t)255);
-    if (launch_segment_median(im->img.p, im->dtype, C, im->n, im->labels.as<int32_t>(), K, scratch, sb, d_out, st)) return -1;
+    if (launch_segment_median(im->img.p, im->dtype, C, C, 1, im->n, im->labels.as<int32_t>(), K, MedianNorm{ 0, 1.0, 1.0 }, scratch, sb,
+                              d_out, st))
+        return -1;
     HIP_TRY(hipMemcpyAsync(median_out, d_out, ob, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;

@@ -240,6 +240,76 @@ int imsegm_image2d_response_stats(imsegm_image2d *im, double mul, double div, do
     return 0;
 }
 
+// the response of the last lm_battery for the statistics below: [3][H][W] planes (a volume: its D slices, one plane of D * H * W);
+// the median and the gradient borrow tex_aux only -- tex_planes and tex_resp stay, the next lm_battery needs no lm_prepare
+static int response_for_stats(imsegm_image2d *im, double mul, double div, const double *out, const char *what)
+{
+    if (!im->tex_ready || !im->have_labels || im->tex_resp.cap < (im->is_volume ? im->n : 3 * im->n) * 8 || !out) {
+        set_error(std::string(what) + " needs a filter response, a label map and an output");
+        return -1;
+    }
+    if (!(div > 0.0) || !(mul >= 0.0)) {          // (r * mul) / div is monotone in r: the median ranks the raw response
+        set_error(std::string(what) + ": needs mul >= 0 and a positive norm div");
+        return -1;
+    }
+    return 0;
+}
+
+int imsegm_image2d_response_median(imsegm_image2d *im, double mul, double div, double *median_out)
+{
+    if (!im || bind(im->ctx)) return -1;
+    if (response_for_stats(im, mul, div, median_out, "response_median")) return -1;
+    hipStream_t st = im->ctx->stream;
+    const int K = im->n_labels, C = im->is_volume ? 1 : 3;
+    const size_t n = im->n, sb = median_scratch_bytes(n, K), ob = (size_t)K * C * 8, o_pad = (ob + 255) & ~(size_t)255;
+    if (im->tex_aux.ensure(o_pad + sb)) return -1;
+    double *d_out = im->tex_aux.as<double>();
+    int sps = im->ctx->begin(PG_STATS);
+    if (launch_segment_median(im->tex_resp.p, IMSEGM_F64, C, 1, n, n, im->labels.as<int32_t>(), K, MedianNorm{ 1, mul, div },
+                              im->tex_aux.as<unsigned char>() + o_pad, sb, d_out, st))
+        return -1;
+    im->ctx->end(sps);
+    HIP_TRY(hipMemcpyAsync(median_out, d_out, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int imsegm_image2d_response_mean_gradient(imsegm_image2d *im, double mul, double div, double *mean_out)
+{
+    if (!im || bind(im->ctx)) return -1;
+    if (response_for_stats(im, mul, div, mean_out, "response_mean_gradient")) return -1;
+    if (im->H < 2 || im->W < 2) {
+        set_error("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements are required.");
+        return -1;
+    }
+    hipStream_t st = im->ctx->stream;
+    const int K = im->n_labels;
+    const size_t nv = im->is_volume ? im->n : 3 * im->n;
+    if (im->tex_aux.ensure(nv * 8 + 64)) return -1;
+    int sps = im->ctx->begin(PG_STATS);
+    // every plane (channel / slice) on its own, never across them
+    if (launch_gradient_image(im->tex_resp.p, im->tex_aux.p, IMSEGM_F64, im->is_volume ? im->D : 3, im->H, im->W, 1, st,
+                              MedianNorm{ 1, mul, div }))
+        return -1;
+    im->ctx->end(sps);
+    // |v| <= mul (|r| <= norm = div)  =>  |gradient along y + along x| <= 2 mul; 4 mul leaves room for the rounding
+    const double maxabs = 4.0 * mul;
+    std::vector<double> m((size_t)K * 3);
+    int rc;
+    if (im->is_volume) {
+        const int keepH = im->H;
+        im->H = im->D * keepH;
+        rc = stats_run(im, im->tex_aux.p, IMSEGM_F64, maxabs, 1, 0, 1.0, 1.0, m.data(), nullptr, nullptr, 0);
+        im->H = keepH;
+        if (!rc)
+            for (int k = 0; k < K; ++k) mean_out[k] = m[(size_t)k * 3];
+    } else {
+        rc = stats_run(im, im->tex_aux.p, IMSEGM_F64, maxabs, 1, 0, 1.0, 1.0, m.data(), nullptr, nullptr);
+        if (!rc) memcpy(mean_out, m.data(), (size_t)K * 3 * 8);
+    }
+    return rc;
+}
+
 int imsegm_image2d_get_response(imsegm_image2d *im, double *planes_out)
 {
     if (!im || bind(im->ctx)) return -1;

@@ -6,6 +6,8 @@
 // Median: the pixels of a channel are ordered by (label, value) with two stable radix sorts (hipCUB: value bits first,
 // then the label), the per-label counts give the segment offsets, one thread per label picks the middle element(s).
 // Exact: no arithmetic but the mean of the two middle values, formed in the image's precision as np.median does.
+// Both also serve the Leung-Malik texture statistics (descriptors.py:1094-1096): the median and the gradient of the normalised
+// filter response (value * mul) / div, read from the planar response buffer (MedianNorm).
 #include "slic.h"
 
 #include <hipcub/hipcub.hpp>
@@ -23,24 +25,28 @@ __device__ __forceinline__ double key_value(unsigned long long k)
     return __longlong_as_double((long long)b);
 }
 
+// element (pixel i, channel c) of the source at src[i * pix_stride + c * chan_stride]: an interleaved image (C, 1) or planes
+// (1, plane size -- the filter responses of the texture path)
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_median_keys(const T *__restrict__ img, int C, int c, size_t n, const int32_t *__restrict__ labels, int K,
+k_median_keys(const T *__restrict__ img, size_t pix_stride, size_t chan_off, size_t n, const int32_t *__restrict__ labels, int K,
               unsigned long long *__restrict__ keys, int32_t *__restrict__ lab_out, unsigned int *__restrict__ counts)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int l = labels[i];
     if (l < 0 || l >= K) l = K;                                   // out-of-range labels sort behind everything
-    keys[i] = order_key((double)img[i * C + c]);                  // uint8 / float32 -> double is exact and monotone
+    keys[i] = order_key((double)img[i * pix_stride + chan_off]);  // uint8 / float32 -> double is exact and monotone
     lab_out[i] = l;
     if (counts && l < K) atomicAdd(&counts[l], 1u);
 }
 
-// dtype: DT_U8 / DT_F64 -> mean of the two middle values in float64, DT_F32 -> in float32 (np.mean of a float32 pair)
+// dtype: DT_U8 / DT_F64 -> mean of the two middle values in float64, DT_F32 -> in float32 (np.mean of a float32 pair).
+// norm.on (float64 sources): the median of (value * mul) / div -- monotone in the value for mul, div > 0, so the keys are ranked
+// raw and only the one or two middle values are normalised, by the operations of descriptors.py:1094, before their mean
 __global__ void __launch_bounds__(256)
 k_median_pick(const unsigned long long *__restrict__ keys, const unsigned int *__restrict__ offsets,
-              const unsigned int *__restrict__ counts, int K, int C, int c, int dtype, double *__restrict__ out)
+              const unsigned int *__restrict__ counts, int K, int C, int c, int dtype, MedianNorm norm, double *__restrict__ out)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= K) return;
@@ -50,8 +56,13 @@ k_median_pick(const unsigned long long *__restrict__ keys, const unsigned int *_
         m = __longlong_as_double(0x7ff8000000000000LL);           // np.median([]) is nan
     } else if (n & 1u) {
         m = key_value(keys[o + n / 2]);
+        if (norm.on) m = (m * norm.mul) / norm.div;
     } else {
-        const double a = key_value(keys[o + n / 2 - 1]), b = key_value(keys[o + n / 2]);
+        double a = key_value(keys[o + n / 2 - 1]), b = key_value(keys[o + n / 2]);
+        if (norm.on) {
+            a = (a * norm.mul) / norm.div;
+            b = (b * norm.mul) / norm.div;
+        }
         if (dtype == DT_F32) m = (double)(((float)a + (float)b) / 2.0f);
         else m = (a + b) / 2.0;
     }
@@ -64,38 +75,43 @@ k_median_pick(const unsigned long long *__restrict__ keys, const unsigned int *_
 template <typename T> struct GradT { typedef double type; };
 template <> struct GradT<float> { typedef float type; };
 
+// norm.on (float64 sources -- the filter responses): every value is normalised on load, (value * mul) / div as descriptors.py:1094,
+// before it is differenced -- np.gradient of the normalised response, not the normalised gradient
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_gradient_image(const T *__restrict__ src, T *__restrict__ dst, int S, int H, int W, int C)
+k_gradient_image(const T *__restrict__ src, T *__restrict__ dst, int S, int H, int W, int C, MedianNorm norm)
 {
     typedef typename GradT<T>::type F;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t total = (size_t)S * H * W * C;
     if (i >= total) return;
-    const int c = (int)(i % C);
     const size_t px = i / C;
     const int x = (int)(px % W), y = (int)((px / W) % H);
     const size_t row = (size_t)W * C, col = (size_t)C;
+    auto ld = [&](size_t j) -> F { return norm.on ? (F)(((double)src[j] * norm.mul) / norm.div) : (F)src[j]; };
     F gy, gx;
-    if (y == 0) gy = ((F)src[i + row] - (F)src[i]) / (F)1;
-    else if (y == H - 1) gy = ((F)src[i] - (F)src[i - row]) / (F)1;
-    else gy = ((F)src[i + row] - (F)src[i - row]) / (F)2;
-    if (x == 0) gx = ((F)src[i + col] - (F)src[i]) / (F)1;
-    else if (x == W - 1) gx = ((F)src[i] - (F)src[i - col]) / (F)1;
-    else gx = ((F)src[i + col] - (F)src[i - col]) / (F)2;
+    if (y == 0) gy = (ld(i + row) - ld(i)) / (F)1;
+    else if (y == H - 1) gy = (ld(i) - ld(i - row)) / (F)1;
+    else gy = (ld(i + row) - ld(i - row)) / (F)2;
+    if (x == 0) gx = (ld(i + col) - ld(i)) / (F)1;
+    else if (x == W - 1) gx = (ld(i) - ld(i - col)) / (F)1;
+    else gx = (ld(i + col) - ld(i - col)) / (F)2;
     const F g = gy + gx;
     if (sizeof(T) == 1) dst[i] = (T)(unsigned char)(int)g;        // float64 -> uint8 as the x86 cast: truncate, wrap
     else dst[i] = (T)g;
-    (void)c;
 }
 
-int launch_gradient_image(const void *src, void *dst, int dtype, int S, int H, int W, int C, hipStream_t st)
+int launch_gradient_image(const void *src, void *dst, int dtype, int S, int H, int W, int C, hipStream_t st, MedianNorm norm)
 {
+    if (norm.on && dtype != DT_F64) {
+        set_error("gradient: normalisation on load needs a float64 source");
+        return -1;
+    }
     const size_t total = (size_t)S * H * W * C;
     const int grid = cdiv((long)total, 256);
-    if (dtype == DT_U8) hipLaunchKernelGGL(k_gradient_image<uint8_t>, grid, 256, 0, st, (const uint8_t *)src, (uint8_t *)dst, S, H, W, C);
-    else if (dtype == DT_F32) hipLaunchKernelGGL(k_gradient_image<float>, grid, 256, 0, st, (const float *)src, (float *)dst, S, H, W, C);
-    else hipLaunchKernelGGL(k_gradient_image<double>, grid, 256, 0, st, (const double *)src, (double *)dst, S, H, W, C);
+    if (dtype == DT_U8) hipLaunchKernelGGL(k_gradient_image<uint8_t>, grid, 256, 0, st, (const uint8_t *)src, (uint8_t *)dst, S, H, W, C, norm);
+    else if (dtype == DT_F32) hipLaunchKernelGGL(k_gradient_image<float>, grid, 256, 0, st, (const float *)src, (float *)dst, S, H, W, C, norm);
+    else hipLaunchKernelGGL(k_gradient_image<double>, grid, 256, 0, st, (const double *)src, (double *)dst, S, H, W, C, norm);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -112,12 +128,21 @@ size_t median_scratch_bytes(size_t n, int K)
     return 2 * n * 8 + 2 * n * 4 + 2 * ((size_t)K + 64) * 4 + tmp + 1024;
 }
 
-// out: [K][C] medians on the device; scratch: median_scratch_bytes(n, K)
-int launch_segment_median(const void *img, int dtype, int C, size_t n, const int32_t *labels, int K, void *scratch, size_t scratch_bytes,
-                          double *out, hipStream_t st)
+// out: [K][C] medians on the device; element (pixel i, channel c) of `img` at img[i * pix_stride + c * chan_stride]; norm: see
+// k_median_pick; scratch: median_scratch_bytes(n, K), the caller's
+int launch_segment_median(const void *img, int dtype, int C, size_t pix_stride, size_t chan_stride, size_t n, const int32_t *labels,
+                          int K, MedianNorm norm, void *scratch, size_t scratch_bytes, double *out, hipStream_t st)
 {
     if (n > 0x7fffffffULL) {
         set_error("median: more than 2^31 elements");
+        return -1;
+    }
+    if (norm.on && dtype != DT_F64) {
+        set_error("median: normalisation at the pick needs a float64 source");
+        return -1;
+    }
+    if (scratch_bytes < median_scratch_bytes(n, K)) {
+        set_error("median: scratch too small");
         return -1;
     }
     unsigned char *b = static_cast<unsigned char *>(scratch);
@@ -135,9 +160,10 @@ int launch_segment_median(const void *img, int dtype, int C, size_t n, const int
     for (int c = 0; c < C; ++c) {
         unsigned int *cnt = c == 0 ? counts : nullptr;
         if (c == 0) HIP_TRY(hipMemsetAsync(counts, 0, ((size_t)K + 1) * 4, st));
-        if (dtype == DT_U8) hipLaunchKernelGGL(k_median_keys<uint8_t>, grid, 256, 0, st, (const uint8_t *)img, C, c, n, labels, K, keyA, labA, cnt);
-        else if (dtype == DT_F32) hipLaunchKernelGGL(k_median_keys<float>, grid, 256, 0, st, (const float *)img, C, c, n, labels, K, keyA, labA, cnt);
-        else hipLaunchKernelGGL(k_median_keys<double>, grid, 256, 0, st, (const double *)img, C, c, n, labels, K, keyA, labA, cnt);
+        const size_t co = (size_t)c * chan_stride;
+        if (dtype == DT_U8) hipLaunchKernelGGL(k_median_keys<uint8_t>, grid, 256, 0, st, (const uint8_t *)img, pix_stride, co, n, labels, K, keyA, labA, cnt);
+        else if (dtype == DT_F32) hipLaunchKernelGGL(k_median_keys<float>, grid, 256, 0, st, (const float *)img, pix_stride, co, n, labels, K, keyA, labA, cnt);
+        else hipLaunchKernelGGL(k_median_keys<double>, grid, 256, 0, st, (const double *)img, pix_stride, co, n, labels, K, keyA, labA, cnt);
         if (c == 0) {
             size_t t = tmp_bytes;
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(b, t, counts, offsets, K, st));
@@ -146,7 +172,7 @@ int launch_segment_median(const void *img, int dtype, int C, size_t n, const int
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(b, t, keyA, keyB, labA, labB, (int)n, 0, 64, st));
         t = tmp_bytes;
         HIP_TRY(hipcub::DeviceRadixSort::SortPairs(b, t, labB, labA, keyB, keyA, (int)n, 0, label_bits, st));
-        hipLaunchKernelGGL(k_median_pick, cdiv(K, 256), 256, 0, st, keyA, offsets, counts, K, C, c, dtype, out);
+        hipLaunchKernelGGL(k_median_pick, cdiv(K, 256), 256, 0, st, keyA, offsets, counts, K, C, c, dtype, norm, out);
     }
     HIP_TRY(hipGetLastError());
     return 0;

@@ -158,8 +158,9 @@ struct imsegm_image2d {
     bool tex_ready = false;
     bool is_volume = false;
     double vol_off = 0.0, vol_scale = 1.0;      // intensity seen by the volume SLIC = (v + off) * scale
+    // tex_aux: scratch of the statistics of a Leung-Malik response (median, gradient) -- tex_planes / tex_resp stay as they are
     DevBuf img, labA, labB, nearest, labels, conn_i32, conn_u8, small, cent, tiles, feat, graph, gather_lut, gather_out_i, gather_out_f,
-        tex_planes, tex_resp, tex_small, vol_cent, annot, hist, featK, seg, gseg, narrow;
+        tex_planes, tex_resp, tex_small, tex_aux, vol_cent, annot, hist, featK, seg, gseg, narrow;
     GraphPlan gplan;                            // the graph imsegm_image2d_graph_prepare has enqueued into `gseg` ...
     bool graph_ready = false;                   // ... for the current label map (any call that changes the labels clears this)
     int *slic_fail_host = nullptr;              // page-locked word the centroid update inside the assignment kernel raises when it hands the image back

@@ -254,10 +254,13 @@ int launch_narrow_soft_f32(const double *src, float *dst, size_t n, hipStream_t 
 int launch_count_nonfinite(const void *src, int dtype, size_t n, unsigned int *count_dev, hipStream_t st);
 
 // median.hip -------------------------------------------------------------------------------------
-int launch_gradient_image(const void *src, void *dst, int dtype, int S, int H, int W, int C, hipStream_t st);
+// on: a float64 source is read as (value * mul) / div (a Leung-Malik response normalised as descriptors.py:1094)
+struct MedianNorm { int on; double mul, div; };
+int launch_gradient_image(const void *src, void *dst, int dtype, int S, int H, int W, int C, hipStream_t st,
+                          MedianNorm norm = MedianNorm{ 0, 1.0, 1.0 });
 size_t median_scratch_bytes(size_t n, int K);
-int launch_segment_median(const void *img, int dtype, int C, size_t n, const int32_t *labels, int K, void *scratch, size_t scratch_bytes,
-                          double *out, hipStream_t st);
+int launch_segment_median(const void *img, int dtype, int C, size_t pix_stride, size_t chan_stride, size_t n, const int32_t *labels,
+                          int K, MedianNorm norm, void *scratch, size_t scratch_bytes, double *out, hipStream_t st);
 
 // natives.hip ------------------------------------------------------------------------------------
 int launch_label_hist2d(const int16_t *segm, int H, int W, const int32_t *windows, int P, const int16_t *selem, int SH, int SW,

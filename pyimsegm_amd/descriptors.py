@@ -6,10 +6,10 @@ reductions the reference delegates to ``imsegm/features_cython.pyx`` run as HIP 
 (``csrc/stats.hip``); the function names ``cython_*`` are kept so that callers of the reference do
 not change, ``hip_*`` are the same functions under an honest name.
 
-Host (numpy / scipy) code remains where the reference itself is numpy / scipy: the ``numpy_*``
-alternatives, the median / mean-gradient statistics and the Leung-Malik filter responses
-(``scipy.ndimage`` convolutions, exactly as ``descriptors.py:903-1106``) -- those are not yet on the
-HIP path ("what runs where").
+Host (numpy / scipy) code remains where the reference itself is numpy / scipy and the device does not
+take the input: the ``numpy_*`` alternatives, the median / mean gradient of dtypes a device session does
+not hold, and the Leung-Malik filter responses of batteries of more than 8 kernels (``scipy.ndimage``
+convolutions, exactly as ``descriptors.py:903-1106``; see DESIGN.md, "what runs where").
 """
 import functools
 import itertools
@@ -447,7 +447,7 @@ def compute_texture_desc_lm_img3d_val(img, seg, feature_flags, bank_type='normal
     _same_shape(img, seg)
     logging.debug('compute texture descriptors using Leung-Malik')
     filters, fl_names = _select_bank(bank_type)
-    if set(feature_flags) <= {'mean', 'std', 'energy'} and all(len(f) <= 8 for f in filters):
+    if _texture_on_device(feature_flags, filters):
         return _texture_desc_lm_device3d(img, seg, feature_flags, filters, fl_names)
     img = image_subtract_gauss_smooth(img, 150)
     features, names = [], []
@@ -468,7 +468,7 @@ def compute_texture_desc_lm_img2d_clr(img, seg, feature_flags, bank_type='normal
     filters, fl_names = _select_bank(bank_type)
     if _texture_on_device(feature_flags, filters):
         return _texture_desc_lm_device(img, seg, feature_flags, filters, fl_names)
-    # host path (median / meanGrad need the response on the host): scipy as the reference
+    # host path (batteries of more than 8 kernels, unknown statistic names): scipy as the reference
     # scalar sigma on all three axes, channel axis included (descriptors.py:1078)
     img = img - ndimage.gaussian_filter(img.astype(float), 150)
     img_roll = np.rollaxis(img, -1, 0)
@@ -486,8 +486,9 @@ def compute_texture_desc_lm_img2d_clr(img, seg, feature_flags, bank_type='normal
 
 
 def _texture_on_device(feature_flags, filters):
-    """the statistics the device forms of a filter response, and batteries it takes (at most 8 kernels)"""
-    return set(feature_flags) <= {'mean', 'std', 'energy'} and all(len(f) <= 8 for f in filters)
+    """the statistics the device forms of a filter response (all five of NAMES_FEATURE_FLAGS), and batteries it takes (at most
+    8 kernels)"""
+    return set(feature_flags) <= set(NAMES_FEATURE_FLAGS) and all(len(f) <= 8 for f in filters)
 
 
 def resident_feature_groups(feature_flags):
@@ -539,17 +540,23 @@ def _finish_texture(blocks, names):
     return _finished(np.nan_to_num(np.concatenate(tuple(blocks), axis=1)), ['tLM_' + name for name in names])
 
 
-def _battery_blocks(sess, battery, sums):
-    """mean | std | energy (those in ``sums``) of the response of ONE battery on a session that holds the high-passed planes,
-    with the norm of the response brought to the host in between (descriptors.py:1088-1094: a response of norm 0 or inf counts
-    as all zeros)"""
+def _battery_blocks(sess, battery, feature_flags):
+    """the statistics of ``feature_flags`` (mean, std, energy, median, meanGrad; in that order) of the normalised response of ONE
+    battery on a session that holds the high-passed planes, with the norm of the response brought to the host in between
+    (descriptors.py:1088-1096: a response of norm 0 or inf counts as all zeros).  The median and the mean gradient leave the
+    prepared planes as they are: the next battery needs no lm_prepare."""
     norm = sess.lm_battery(battery, MAX_SIGNAL_RESPONSE)
+    flags = set(feature_flags)
     if not 0 < abs(norm) < np.inf:
-        mean = energy = var = np.zeros(sess.n_labels if isinstance(sess, _hip.Volume3D) else (sess.n_labels, 3))
-    else:
-        mean, energy, var = sess.response_stats(np.log(1 + norm) / 0.03, norm, mean='mean' in sums, energy='energy' in sums,
-                                                var='std' in sums)
-    return _ordered_columns({'mean': lambda: mean, 'std': lambda: np.sqrt(var), 'energy': lambda: energy}, sums)
+        zeros = np.zeros(sess.n_labels if isinstance(sess, _hip.Volume3D) else (sess.n_labels, 3))
+        return _ordered_columns(dict.fromkeys(NAMES_FEATURE_FLAGS, lambda: zeros), flags)
+    mul = np.log(1 + norm) / 0.03
+    mean = energy = var = None
+    if flags & {'mean', 'std', 'energy'}:
+        mean, energy, var = sess.response_stats(mul, norm, mean='mean' in flags, energy='energy' in flags, var='std' in flags)
+    return _ordered_columns({'mean': lambda: mean, 'std': lambda: np.sqrt(var), 'energy': lambda: energy,
+                             'median': lambda: sess.response_median(mul, norm),
+                             'meanGrad': lambda: sess.response_mean_gradient(mul, norm)}, flags)
 
 
 def _texture_desc_lm_device(img, seg, feature_flags, filters, fl_names, sess=None):
@@ -561,11 +568,13 @@ def _texture_desc_lm_device(img, seg, feature_flags, filters, fl_names, sess=Non
     try:
         sess.lm_prepare(150.)
         sums = {'mean', 'std', 'energy'} & set(feature_flags)
-        if sums and len({np.shape(f)[1:] for f in filters}) == 1 and hasattr(sess, 'lm_features'):
+        fused = sums and not {'median', 'meanGrad'} & set(feature_flags)
+        if fused and len({np.shape(f)[1:] for f in filters}) == 1 and hasattr(sess, 'lm_features'):
             # all batteries in one call: the norm of a battery never comes to the host (60 synchronisations per image less)
             blocks = [sess.lm_features(filters, MAX_SIGNAL_RESPONSE, mean='mean' in sums, std='std' in sums, energy='energy' in sums)]
-        else:
-            blocks = [_finished(np.nan_to_num(np.hstack(_battery_blocks(sess, battery, sums))), None)[0] for battery in filters]
+        else:       # battery by battery (the median and the mean gradient are formed of one response at a time)
+            blocks = [_finished(np.nan_to_num(np.hstack(_battery_blocks(sess, battery, feature_flags))), None)[0]
+                      for battery in filters]
     finally:
         if not borrowed:
             sess.close()
@@ -581,8 +590,7 @@ def _texture_desc_lm_device3d(img, seg, feature_flags, filters, fl_names):
     sess = _hip.Volume3D(*seg.shape).upload(np.nan_to_num(img)).set_labels(seg)
     try:
         sess.lm_prepare(150.)
-        sums = {'mean', 'std', 'energy'} & set(feature_flags)
-        blocks = [_finished(np.nan_to_num(np.array(_battery_blocks(sess, battery, sums))).T, None)[0] for battery in filters]
+        blocks = [_finished(np.nan_to_num(np.array(_battery_blocks(sess, battery, feature_flags))).T, None)[0] for battery in filters]
     finally:
         sess.close()
     names = ['%s_%s' % (name, flag) for name in fl_names for flag in NAMES_FEATURE_FLAGS if flag in feature_flags]
