@@ -1,7 +1,29 @@
 // api_fused.hip -- C ABI of the back half: the general graph cut, the resident feature table, the prepared graph and the fused segment call, the one-call colour pipeline
 // (one of the files api.hip was split into in round 6: the C ABI of include/imsegm_hip.h by stage; the helpers they share are
 // declared in session.h)
-#include "session.h"
+#include "backhalf.h"
+
+// the placement of imsegm_image2d_features_place, consumed by the descriptor call that follows it: `own_F` columns at *col0 of a
+// table *table_F wide (without a placement: the block is the table)
+int imsegm::take_placement(imsegm_image2d *im, int own_F, bool to_host, int *table_F, int *col0)
+{
+    *table_F = own_F;
+    *col0 = 0;
+    if (im->place_F <= 0) return 0;
+    const int total = im->place_F, column = im->place_col;
+    im->place_F = 0;
+    if (column + own_F > total) {
+        set_error("features_place: the columns of this descriptor group do not fit the table");
+        return -1;
+    }
+    if (to_host && own_F != total) {
+        set_error("features_place: a group placed into a wider table stays on the device (imsegm_image2d_get_features reads the table)");
+        return -1;
+    }
+    *table_F = total;
+    *col0 = column;
+    return 0;
+}
 
 extern "C" {
 
@@ -22,12 +44,7 @@ int imsegm_cut_general_graph(imsegm_ctx *ctx, const int32_t *edges, int n_edges,
             return -1;
         }
     }
-    for (int a = 0; a < C; ++a)
-        for (int b = 0; b < C; ++b)
-            if (pairwise_cost[a * C + b] != pairwise_cost[b * C + a]) {
-                set_error("Cost matrix not square or not symmetric");
-                return -1;
-            }
+    if (check_pairwise(pairwise_cost, C)) return -1;
     // device layout: [work | unary | w | smooth | edges | arc_start | arc_to | arc_rev | edge_arc | labels | energy | status];
     // the upload part (unary .. edge_arc) is assembled in ONE pinned host block with the same offsets
     hipStream_t st = ctx->stream;
@@ -106,11 +123,8 @@ int imsegm_cut_general_graph(imsegm_ctx *ctx, const int32_t *edges, int n_edges,
     HIP_TRY(hipStreamSynchronize(st));
     memcpy(labels_out, host + o_lab, (size_t)K * 4);
     long long energy = *reinterpret_cast<long long *>(host + o_en);
-    int32_t status = *reinterpret_cast<int32_t *>(host + o_st);
-    if (status != 0) {
-        set_error("alpha_expansion: max-flow did not converge");
-        return -1;
-    }
+    const int32_t misc[4] = { K, E, 0, *reinterpret_cast<int32_t *>(host + o_st) };      // (the cut's own status word)
+    if (backhalf_status(misc, 1)) return -1;
     if (energy_out) *energy_out = energy;
     return 0;
 }
@@ -120,28 +134,6 @@ int imsegm_cut_general_graph(imsegm_ctx *ctx, const int32_t *edges, int n_edges,
 // fused back half of the pipeline: statistics -> feature table -> graph -> class model -> graph-cut terms ->
 // alpha-expansion -> gathers, enqueued on the session's stream without a host round trip
 // ---------------------------------------------------------------------------------------------------
-// the placement of imsegm_image2d_features_place, consumed by the descriptor call that follows it: `own_F` columns at *col0 of a
-// table *table_F wide (without a placement: the block is the table)
-int take_placement(imsegm_image2d *im, int own_F, bool to_host, int *table_F, int *col0)
-{
-    *table_F = own_F;
-    *col0 = 0;
-    if (im->place_F <= 0) return 0;
-    const int total = im->place_F, column = im->place_col;
-    im->place_F = 0;
-    if (column + own_F > total) {
-        set_error("features_place: the columns of this descriptor group do not fit the table");
-        return -1;
-    }
-    if (to_host && own_F != total) {
-        set_error("features_place: a group placed into a wider table stays on the device (imsegm_image2d_get_features reads the table)");
-        return -1;
-    }
-    *table_F = total;
-    *col0 = column;
-    return 0;
-}
-
 int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *features_out)
 {
     if (!im || bind(im->ctx)) return -1;
@@ -169,30 +161,23 @@ int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *
         if (!(maxabs < 1e300)) maxabs = 1e300;
     }
     // statistics without the D2H of stats_run
-    size_t fb = (size_t)K * (13 * 8 + 3 * 3 * 8 + 3 * 4) + 256;
-    if (im->feat.ensure(fb)) return -1;
-    unsigned char *b = im->feat.as<unsigned char>();
-    long long *acc = reinterpret_cast<long long *>(b); b += (size_t)K * 13 * 8;
-    double *d_mean = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    double *d_energy = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    double *d_var = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    float *d_mean32 = reinterpret_cast<float *>(b);
+    if (im->feat.ensure(stats_scratch_bytes(K))) return -1;
+    const StatsScratch ss = stats_scratch_at(im->feat.p, K);
     int sp = ctx->begin(PG_STATS);
     int rc;
     if (im->is_volume)      // the one-channel kernel on the gray plane (plane stride 0), the volume as a (D*H) x W image; its
                             // finalisation copies the gray statistics into all three channels: [m m m | s s s | e e e]
         rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->D * im->H, im->W, K, maxabs, (feature_mask & 2) != 0,
-                                acc, d_mean, d_energy, d_var, d_mean32, st, 1, 0, 1.0, 1.0, 0);
+                                ss.acc, ss.mean, ss.energy, ss.var, ss.mean32, st, 1, 0, 1.0, 1.0, 0);
     else
-        rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, (feature_mask & 2) != 0, acc,
-                                d_mean, d_energy, d_var, d_mean32, st, 0, 0, 1.0, 1.0, -1);
+        rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, (feature_mask & 2) != 0, ss.acc,
+                                ss.mean, ss.energy, ss.var, ss.mean32, st, 0, 0, 1.0, 1.0, -1);
     if (rc) return -1;
-    const int nflags = ((feature_mask & 1) != 0) + ((feature_mask & 2) != 0) + ((feature_mask & 4) != 0);
-    const int F = 3 * nflags;
+    const int F = color_feature_columns(feature_mask);
     int table_F = F, col0 = 0;
     if (take_placement(im, F, features_out != nullptr, &table_F, &col0)) return -1;
     if (im->featK.ensure((size_t)K * table_F * 8 + 64)) return -1;
-    if (launch_features_assemble(d_mean, d_energy, d_var, K, feature_mask, im->featK.as<double>(), st, table_F, col0)) return -1;
+    if (launch_features_assemble(ss.mean, ss.energy, ss.var, K, feature_mask, im->featK.as<double>(), st, table_F, col0)) return -1;
     ctx->end(sp);
     im->feat_mask = table_F == F ? feature_mask : 8;          // (8: a table of several descriptor groups)
     im->feat_F = table_F;
@@ -230,29 +215,6 @@ int imsegm_image2d_get_features(imsegm_image2d *im, double *features_out, int ca
     HIP_TRY(hipMemcpyAsync(features_out, im->featK.p, (size_t)im->n_labels * im->feat_F * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
-}
-
-// `edge_capacity` 0: sized for a planar adjacency graph (every superpixel connected); *edges_found: edges of the graph, also
-// when the table was too small for them (return value -2: the caller retries with that many)
-static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double *proba, int n_classes,
-                        const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
-                        const int32_t *classes_lut, int32_t *segm_out, double *soft_out, int32_t *graph_labels_out,
-                        double *proba_out, imsegm_terms_debug *debug_out, int edge_capacity, int *edges_found);
-
-int imsegm_image2d_segment(imsegm_image2d *im, const imsegm_gmm *gmm, const double *proba, int n_classes,
-                           const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
-                           const int32_t *classes_lut, int32_t *segm_out, double *soft_out, int32_t *graph_labels_out,
-                           double *proba_out, imsegm_terms_debug *debug_out)
-{
-    int found = 0;
-    int rc = segment_impl(im, gmm, proba, n_classes, pairwise, edge_type, edge_cost, use_graphcut, classes_lut, segm_out, soft_out,
-                          graph_labels_out, proba_out, debug_out, 0, &found);
-    // a label map whose regions are not connected (installed with imsegm_image2d_set_labels) can have more neighbour pairs than
-    // a planar graph: once more with a table of the size the device has reported
-    if (rc == -2)
-        rc = segment_impl(im, gmm, proba, n_classes, pairwise, edge_type, edge_cost, use_graphcut, classes_lut, segm_out, soft_out,
-                          graph_labels_out, proba_out, debug_out, found + 64, &found);
-    return rc == -2 ? -1 : rc;
 }
 
 // ---- the graph of the resident label map: neighbour pairs + centre sums, then edges (a < b, ordered by (b, a)), CSR arcs in
@@ -381,6 +343,8 @@ int imsegm_image2d_graph_prepare(imsegm_image2d *im)
     return 0;
 }
 
+// `edge_capacity` 0: sized for a planar adjacency graph (every superpixel connected); *edges_found: edges of the graph, also
+// when the table was too small for them (return value -2: the caller retries with that many)
 static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double *proba, int n_classes,
                         const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
                         const int32_t *classes_lut, int32_t *segm_out, double *soft_out, int32_t *graph_labels_out,
@@ -396,13 +360,9 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         set_error("segment: 1..16 classes, a pairwise matrix and either a class model or probabilities are required");
         return -1;
     }
-    int edge_code = edge_type & 0xff;
-    const int spatial_norm = (edge_type & IMSEGM_EDGE_SPATIAL_NORM) ? 1 : 0;
-    if (edge_code < 0 || edge_code > 5) {
-        set_error("segment: unknown edge type");
-        return -1;
-    }
-    const bool need_features = gmm != nullptr || edge_code == 5;
+    BackHalf bh;
+    if (decode_edge_type(edge_type, &bh.edge_code, &bh.spatial_norm)) return -1;
+    const bool need_features = gmm != nullptr || bh.edge_code == 5;
     if (need_features && im->feat_mask == 0) {
         set_error("segment: the class model / edge type needs the resident feature table (imsegm_image2d_features_color)");
         return -1;
@@ -412,12 +372,7 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         set_error("segment: class model does not match the resident features / number of classes");
         return -1;
     }
-    for (int a = 0; a < C; ++a)
-        for (int b = 0; b < C; ++b)
-            if (pairwise[a * C + b] != pairwise[b * C + a]) {
-                set_error("Cost matrix not square or not symmetric");
-                return -1;
-            }
+    if (check_pairwise(pairwise, C)) return -1;
     // the graph: prepared ahead (imsegm_image2d_graph_prepare, same label map, room for the edges asked for) or built here
     const bool prepared = im->graph_ready && im->gplan.K == K && (edge_capacity <= 0 || im->gplan.Ecap >= edge_capacity);
     const GraphPlan g = prepared ? im->gplan : graph_plan(im, K, edge_capacity);
@@ -427,135 +382,42 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
     imsegm_ctx *ctx = im->ctx;
     hipStream_t st = ctx->stream;
     const size_t n = im->n;
-    const int ndim = im->is_volume ? 3 : 2;
-    const int Ecap = g.Ecap;
-    auto al = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    // ---- host -> device parameter block (one pinned staging copy)
-    const size_t FF = (size_t)F * F;
-    size_t o = 0;
-    const size_t o_misc = o; o += 256;          // K | E | status | pad | energy (8) | scalars[8]: initialised by the same copy
-    const size_t o_pw = o; o += al((size_t)C * C * 8);
-    const size_t o_sm = o; o += al((size_t)C * C * 4);
-    const size_t o_cl = o; o += al((size_t)C * 4);
-    const size_t o_sc = o; o += al((size_t)2 * F * 8);
-    const size_t o_pc = o; o += al((size_t)C * FF * 8);
-    const size_t o_mp = o; o += al((size_t)C * F * 8);
-    const size_t o_ld = o; o += al((size_t)C * 8);
-    const size_t o_lw = o; o += al((size_t)C * 8);
-    const size_t o_pr = o; o += (gmm ? 0 : al((size_t)K * C * 8));
-    const size_t up_bytes = o;
-    // ---- device layout
-    const size_t d_par = 0;
-    size_t d = al(up_bytes);
-    if (gmm) { /* proba lives behind the parameters */ }
-    const size_t d_proba = gmm ? d : d_par + o_pr; if (gmm) d += al((size_t)K * C * 8);
-    const size_t d_unary = d; d += al((size_t)K * C * 8);
-    const size_t d_unary_i = d; d += al((size_t)K * C * 4);
-    const size_t d_w = d; d += al((size_t)Ecap * 8);
-    const size_t d_wi = d; d += al((size_t)Ecap * 4);
-    const size_t d_edist = d; d += al((size_t)Ecap * 8);
-    const size_t d_elen = d; d += al((size_t)Ecap * 8);
-    const size_t d_gl = d; d += al((size_t)K * 4);
-    const size_t d_lut = d; d += al((size_t)K * 4);
-    const size_t d_misc = d_par + o_misc;
-    const size_t d_fstd = d; d += al((size_t)2 * std::max(F, 1) * 8);
-    const size_t d_work = d; d += al(alpha_expansion_work_bytes(K, Ecap));
-    if (im->seg.ensure(d + 256)) return -1;
-    unsigned char *dev = im->seg.as<unsigned char>();
+    // ---- host -> device parameter block (one pinned staging copy), the scratch of the terms and the cut behind it
+    bh.C = C; bh.F = F;
+    bh.par = param_block(C, F, gmm ? 0 : K);
+    bh.scr = terms_scratch(bh.par, K, C, F, g.Ecap, gmm == nullptr);
+    const size_t up_bytes = bh.par.bytes;
+    if (im->seg.ensure(bh.scr.end + 256)) return -1;
+    bh.base = im->seg.as<unsigned char>();
     unsigned char *host = static_cast<unsigned char *>(ctx->stage(up_bytes + 64));
     if (!host) {
         set_error("cannot allocate pinned staging memory");
         return -1;
     }
     memset(host, 0, up_bytes);
-    reinterpret_cast<int32_t *>(host + o_misc)[0] = K;            // E = 0 | status = 0 | gc status = 0 | energy = 0 behind it
-    memcpy(host + o_pw, pairwise, (size_t)C * C * 8);
-    int32_t *si = reinterpret_cast<int32_t *>(host + o_sm);
-    int smax = 0;
-    double pmax = -DBL_MAX;
-    for (int i = 0; i < C * C; ++i) {
-        si[i] = (int32_t)(pairwise[i] * 100);                 // pygco: smooth cost * 100, truncated
-        smax = std::max(smax, std::abs(si[i]));
-        pmax = std::max(pmax, pairwise[i]);
-    }
-    const int metric = smooth_is_metric(si, C);
-    if (classes_lut) memcpy(host + o_cl, classes_lut, (size_t)C * 4);
-    if (gmm) {
-        if (gmm->scaler_mean) memcpy(host + o_sc, gmm->scaler_mean, (size_t)F * 8);
-        if (gmm->scaler_scale) memcpy(host + o_sc + (size_t)F * 8, gmm->scaler_scale, (size_t)F * 8);
-        memcpy(host + o_pc, gmm->prec_chol, (size_t)C * FF * 8);
-        memcpy(host + o_mp, gmm->mu_proj, (size_t)C * F * 8);
-        memcpy(host + o_ld, gmm->log_det, (size_t)C * 8);
-        memcpy(host + o_lw, gmm->log_weights, (size_t)C * 8);
-    } else {
-        memcpy(host + o_pr, proba, (size_t)K * C * 8);
-    }
-    HIP_TRY(hipMemcpyAsync(dev + d_par, host, up_bytes, hipMemcpyHostToDevice, st));
+    param_fill(bh, host, K, pairwise, classes_lut, gmm, proba);
+    HIP_TRY(hipMemcpyAsync(bh.base, host, up_bytes, hipMemcpyHostToDevice, st));
     ctx->mark_stage_in_flight();
-    int32_t *misc = reinterpret_cast<int32_t *>(dev + d_misc);
-    int32_t *K_dev = misc, *E_dev = misc + 1, *status = misc + 2;
-    long long *energy = reinterpret_cast<long long *>(dev + d_misc + 16);
-    double *scalars = reinterpret_cast<double *>(dev + d_misc + 64);
+    int32_t *misc = bh.misc();
+    bh.K_dev = misc; bh.E_dev = misc + 1;
     // ---- graph: neighbour pairs + centres, then the symmetric CSR (im->gseg)
-    if (prepared) E_dev = nullptr;                           // (the prepared graph counted its edges in its own head)
-    else if (graph_enqueue(im, g, K_dev, E_dev)) return -1;
+    if (!prepared && graph_enqueue(im, g, bh.K_dev, bh.E_dev)) return -1;
     unsigned char *gb = im->gseg.as<unsigned char>();
     int32_t *ghead = reinterpret_cast<int32_t *>(gb + g.o_head);
-    if (!E_dev) E_dev = ghead + 1;
-    int32_t *edges = reinterpret_cast<int32_t *>(gb + g.o_edges);
-    double *centres = reinterpret_cast<double *>(gb + g.o_cent);
-    int32_t *arc_start = reinterpret_cast<int32_t *>(gb + g.o_as), *arc_to = reinterpret_cast<int32_t *>(gb + g.o_at);
-    int32_t *arc_rev = reinterpret_cast<int32_t *>(gb + g.o_ar), *edge_arc = reinterpret_cast<int32_t *>(gb + g.o_ea);
-    // ---- class probabilities, unary / edge terms, integer energies
-    TermsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Kp = K_dev; a.K_cap = K; a.Ep = E_dev; a.edge_capacity = Ecap; a.F = F; a.C = C;
-    a.features = need_features ? im->featK.as<double>() : nullptr;
-    a.gmm = gmm ? 1 : 0;
-    if (gmm) {
-        a.scaler_mean = gmm->scaler_mean ? reinterpret_cast<double *>(dev + d_par + o_sc) : nullptr;
-        a.scaler_scale = gmm->scaler_scale ? reinterpret_cast<double *>(dev + d_par + o_sc) + F : nullptr;
-        a.prec_chol = reinterpret_cast<double *>(dev + d_par + o_pc);
-        a.mu_proj = reinterpret_cast<double *>(dev + d_par + o_mp);
-        a.log_det = reinterpret_cast<double *>(dev + d_par + o_ld);
-        a.log_w = reinterpret_cast<double *>(dev + d_par + o_lw);
-        a.const_term = gmm->const_term;
-    }
-    a.proba = reinterpret_cast<double *>(dev + d_proba);
-    a.edge_type = edge_code; a.spatial_norm = spatial_norm; a.edge_cost = edge_cost;
-    a.edges = edges; a.centres = centres; a.ndim = ndim;
-    a.edge_dist = reinterpret_cast<double *>(dev + d_edist); a.edge_len = reinterpret_cast<double *>(dev + d_elen);
-    a.unary = reinterpret_cast<double *>(dev + d_unary); a.weights = reinterpret_cast<double *>(dev + d_w);
-    a.pairwise = reinterpret_cast<double *>(dev + d_par + o_pw); a.pairwise_max = pmax;
-    a.unary_i = reinterpret_cast<int32_t *>(dev + d_unary_i); a.weights_i = reinterpret_cast<int32_t *>(dev + d_wi);
-    a.smooth_max = smax; a.status = status; a.scalars = scalars; a.fstd = reinterpret_cast<double *>(dev + d_fstd);
-    int spt = ctx->begin(PG_TERMS);
-    if (launch_gc_terms(a, st)) return -1;
-    ctx->end(spt);
-    // ---- alpha-expansion (or the argmin of the unary cost for gc_regul <= 0)
-    int32_t *glab = reinterpret_cast<int32_t *>(dev + d_gl);
-    int spg = ctx->begin(PG_GC);
-    if (use_graphcut) {
-        GcProblem p;
-        p.K = K; p.C = C; p.E = Ecap; p.E_dev = E_dev;
-        p.edges = edges; p.w = a.weights_i; p.unary = a.unary_i; p.smooth = reinterpret_cast<int32_t *>(dev + d_par + o_sm);
-        p.metric = metric;
-        if (launch_alpha_expansion(p, arc_start, arc_to, arc_rev, edge_arc, -1, glab, energy, status + 1, dev + d_work, st))
-            return -1;
-    } else if (launch_unary_argmin(a.unary, K_dev, K, C, glab, st)) {
-        return -1;
-    }
-    ctx->end(spg);
-    // ---- gathers: classes_[graph_labels][slic] and proba[slic]
-    int32_t *lut = reinterpret_cast<int32_t *>(dev + d_lut);
-    if (launch_label_lut(glab, K_dev, K, classes_lut ? reinterpret_cast<int32_t *>(dev + d_par + o_cl) : nullptr, lut, st)) return -1;
+    if (prepared) bh.E_dev = ghead + 1;                      // (the prepared graph counted its edges in its own head)
+    bh.edges = reinterpret_cast<int32_t *>(gb + g.o_edges); bh.centres = reinterpret_cast<double *>(gb + g.o_cent);
+    bh.arc_start = reinterpret_cast<int32_t *>(gb + g.o_as); bh.arc_to = reinterpret_cast<int32_t *>(gb + g.o_at);
+    bh.arc_rev = reinterpret_cast<int32_t *>(gb + g.o_ar); bh.edge_arc = reinterpret_cast<int32_t *>(gb + g.o_ea);
+    // ---- terms, cut, gathers: classes_[graph_labels][slic] and proba[slic]
     if (im->gather_out_i.ensure(n * 4)) return -1;
     const bool want_soft = soft_out != nullptr || (debug_out && debug_out->keep_soft_on_device);
     if (want_soft && im->gather_out_f.ensure(n * C * 8)) return -1;
-    int spq = ctx->begin(PG_GATHER);
-    if (launch_gather_labels(lut, im->labels.as<int32_t>(), n, im->gather_out_i.as<int32_t>(), st)) return -1;
-    if (want_soft && launch_gather_proba(a.proba, C, im->labels.as<int32_t>(), n, im->gather_out_f.as<double>(), st)) return -1;
-    ctx->end(spq);
+    bh.features = need_features ? im->featK.as<double>() : nullptr;
+    bh.labels = im->labels.as<int32_t>(); bh.n = n;
+    bh.segm_out = im->gather_out_i.as<int32_t>(); bh.soft_out = want_soft ? im->gather_out_f.as<double>() : nullptr;
+    bh.K_cap = K; bh.Ecap = g.Ecap; bh.ndim = im->is_volume ? 3 : 2;
+    bh.edge_cost = edge_cost; bh.use_graphcut = use_graphcut;
+    if (backhalf_enqueue(ctx, bh)) return -1;
     // ---- results (int32 / float64 as the reference returns them, or the narrow formats the caller asked for)
     const bool segm_u8 = debug_out && debug_out->segm_u8, soft_f32 = debug_out && debug_out->soft_f32;
     if ((segm_u8 && segm_out) || (soft_f32 && soft_out)) {
@@ -576,16 +438,16 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
     }
     if (segm_out) HIP_TRY(hipMemcpyAsync(segm_out, im->gather_out_i.p, n * 4, hipMemcpyDeviceToHost, st));
     if (soft_out) HIP_TRY(hipMemcpyAsync(soft_out, im->gather_out_f.p, n * C * 8, hipMemcpyDeviceToHost, st));
-    if (graph_labels_out) HIP_TRY(hipMemcpyAsync(graph_labels_out, glab, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    if (proba_out) HIP_TRY(hipMemcpyAsync(proba_out, a.proba, (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
+    if (graph_labels_out) HIP_TRY(hipMemcpyAsync(graph_labels_out, bh.at<int32_t>(bh.scr.d_gl), (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    if (proba_out) HIP_TRY(hipMemcpyAsync(proba_out, bh.at<double>(bh.scr.d_proba), (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
     int32_t hmisc[4] = { 0, 0, 0, 0 }, hgraph[4] = { 0, 0, 0, 0 };
     HIP_TRY(hipMemcpyAsync(hmisc, misc, sizeof(hmisc), hipMemcpyDeviceToHost, st));
     if (prepared || g.table) HIP_TRY(hipMemcpyAsync(hgraph, ghead, sizeof(hgraph), hipMemcpyDeviceToHost, st));
     if (debug_out) {
-        if (debug_out->unary) HIP_TRY(hipMemcpyAsync(debug_out->unary, a.unary, (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
-        if (debug_out->unary_int) HIP_TRY(hipMemcpyAsync(debug_out->unary_int, a.unary_i, (size_t)K * C * 4, hipMemcpyDeviceToHost, st));
-        if (debug_out->centres) HIP_TRY(hipMemcpyAsync(debug_out->centres, centres, (size_t)K * ndim * 8, hipMemcpyDeviceToHost, st));
-        if (debug_out->energy) HIP_TRY(hipMemcpyAsync(debug_out->energy, energy, 8, hipMemcpyDeviceToHost, st));
+        if (debug_out->unary) HIP_TRY(hipMemcpyAsync(debug_out->unary, bh.at<double>(bh.scr.d_unary), (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
+        if (debug_out->unary_int) HIP_TRY(hipMemcpyAsync(debug_out->unary_int, bh.at<int32_t>(bh.scr.d_unary_i), (size_t)K * C * 4, hipMemcpyDeviceToHost, st));
+        if (debug_out->centres) HIP_TRY(hipMemcpyAsync(debug_out->centres, bh.centres, (size_t)K * bh.ndim * 8, hipMemcpyDeviceToHost, st));
+        if (debug_out->energy) HIP_TRY(hipMemcpyAsync(debug_out->energy, misc + 4, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     const int E = prepared ? hgraph[1] : hmisc[1];
@@ -597,25 +459,29 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         debug_out->n_edges = E;
         const int Ec = std::min(E, debug_out->edge_capacity);
         if (Ec > 0) {
-            if (debug_out->edges) HIP_TRY(hipMemcpy(debug_out->edges, edges, (size_t)Ec * 8, hipMemcpyDeviceToHost));
-            if (debug_out->edge_weights) HIP_TRY(hipMemcpy(debug_out->edge_weights, a.weights, (size_t)Ec * 8, hipMemcpyDeviceToHost));
-            if (debug_out->edge_weights_int) HIP_TRY(hipMemcpy(debug_out->edge_weights_int, a.weights_i, (size_t)Ec * 4, hipMemcpyDeviceToHost));
+            if (debug_out->edges) HIP_TRY(hipMemcpy(debug_out->edges, bh.edges, (size_t)Ec * 8, hipMemcpyDeviceToHost));
+            if (debug_out->edge_weights) HIP_TRY(hipMemcpy(debug_out->edge_weights, bh.at<double>(bh.scr.d_w), (size_t)Ec * 8, hipMemcpyDeviceToHost));
+            if (debug_out->edge_weights_int) HIP_TRY(hipMemcpy(debug_out->edge_weights_int, bh.at<int32_t>(bh.scr.d_wi), (size_t)Ec * 4, hipMemcpyDeviceToHost));
         }
     }
     if (edges_found) *edges_found = E;
-    if (hmisc[2] & 2) {
-        set_error("segment: more graph edges than the edge table holds");
-        return -2;
-    }
-    if (use_graphcut && (hmisc[2] & 1)) {
-        set_error("cut_general_graph: smoothness term is larger than GCO_MAX_ENERGYTERM");
-        return -1;
-    }
-    if (use_graphcut && hmisc[3] != 0) {
-        set_error("alpha_expansion: max-flow did not converge");
-        return -1;
-    }
-    return 0;
+    return backhalf_status(hmisc, use_graphcut);
+}
+
+int imsegm_image2d_segment(imsegm_image2d *im, const imsegm_gmm *gmm, const double *proba, int n_classes,
+                           const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
+                           const int32_t *classes_lut, int32_t *segm_out, double *soft_out, int32_t *graph_labels_out,
+                           double *proba_out, imsegm_terms_debug *debug_out)
+{
+    int found = 0;
+    int rc = segment_impl(im, gmm, proba, n_classes, pairwise, edge_type, edge_cost, use_graphcut, classes_lut, segm_out, soft_out,
+                          graph_labels_out, proba_out, debug_out, 0, &found);
+    // a label map whose regions are not connected (installed with imsegm_image2d_set_labels) can have more neighbour pairs than
+    // a planar graph: once more with a table of the size the device has reported
+    if (rc == -2)
+        rc = segment_impl(im, gmm, proba, n_classes, pairwise, edge_type, edge_cost, use_graphcut, classes_lut, segm_out, soft_out,
+                          graph_labels_out, proba_out, debug_out, found + 64, &found);
+    return rc == -2 ? -1 : rc;
 }
 
 
@@ -637,7 +503,5 @@ int imsegm_image2d_run_color(imsegm_image2d *im, const void *host_pixels, int dt
     return imsegm_image2d_segment(im, gmm, nullptr, n_classes, pairwise, edge_type, edge_cost, use_graphcut, classes_lut, segm_out,
                                   soft_out, nullptr, nullptr, nullptr);
 }
-
-
 
 }  // extern "C"

@@ -159,13 +159,7 @@ int imsegm_image2d_slic(imsegm_image2d *im, int minmax_normalize, int n_segments
     slic_place_state(s, geo, im->cent.as<unsigned char>(), im->tiles.as<unsigned char>(), premax, im->slic_fail_host);
     double *init_dev = nullptr;                            // the grid is generated on the device
 
-    ProfHook hook;
-    if (ctx->profile) {
-        hook.user = ctx;
-        hook.begin = [](void *u, int g) { return static_cast<imsegm_ctx *>(u)->begin(g); };
-        hook.end = [](void *u, int id) { static_cast<imsegm_ctx *>(u)->end(id); };
-        hook.pair = [](void *u, int g, hipEvent_t *a, hipEvent_t *b) { static_cast<imsegm_ctx *>(u)->pair(g, a, b); };
-    }
+    const ProfHook hook = ctx->hook();
     // Optional (IMSEGM_SLIC_GRAPH=1): the sweeps replayed from a captured HIP graph -- one submission instead of 31.  Measured
     // on ROCm 7.2 / MI355X it is SLOWER than the 31 plain launches (one image alone 1.97-2.03 ms against 1.86-1.87 ms; three
     // in flight 1.01-1.08 ms per image against 0.79-0.80 ms: the graph launches of different streams do not overlap the way
@@ -528,23 +522,19 @@ int imsegm_image2d_gather(imsegm_image2d *im, const int32_t *graph_labels, const
     return 0;
 }
 
-int stats_run(imsegm_image2d *im, const void *src, int dtype, double maxabs, int planar, int prescale, double mul,
-                     double div, double *mean_out, double *energy_out, double *var_out, long plane_stride)
+}  // extern "C"
+
+int imsegm::stats_run(imsegm_image2d *im, const void *src, int dtype, double maxabs, int planar, int prescale, double mul,
+                      double div, double *mean_out, double *energy_out, double *var_out, long plane_stride)
 {
     imsegm_ctx *ctx = im->ctx;
     hipStream_t st = ctx->stream;
     const int K = im->n_labels;
-    size_t fb = (size_t)K * (13 * 8 + 3 * 3 * 8 + 3 * 4) + 256;
-    if (im->feat.ensure(fb)) return -1;
-    unsigned char *b = im->feat.as<unsigned char>();
-    long long *acc = reinterpret_cast<long long *>(b); b += (size_t)K * 13 * 8;
-    double *d_mean = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    double *d_energy = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    double *d_var = reinterpret_cast<double *>(b); b += (size_t)K * 3 * 8;
-    float *d_mean32 = reinterpret_cast<float *>(b);
+    if (im->feat.ensure(stats_scratch_bytes(K))) return -1;
+    const StatsScratch ss = stats_scratch_at(im->feat.p, K);
     int sp = ctx->begin(PG_STATS);
-    if (launch_color_stats(src, dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, var_out != nullptr, acc, d_mean,
-                           d_energy, d_var, d_mean32, st, planar, prescale, mul, div, plane_stride))
+    if (launch_color_stats(src, dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, var_out != nullptr, ss.acc, ss.mean,
+                           ss.energy, ss.var, ss.mean32, st, planar, prescale, mul, div, plane_stride))
         return -1;
     ctx->end(sp);
     size_t ob = (size_t)K * 3 * 8;
@@ -553,13 +543,10 @@ int stats_run(imsegm_image2d *im, const void *src, int dtype, double maxabs, int
         set_error("cannot allocate pinned staging memory");
         return -1;
     }
-    HIP_TRY(hipMemcpyAsync(host, d_mean, 3 * ob, hipMemcpyDeviceToHost, st));     // mean | energy | var
+    HIP_TRY(hipMemcpyAsync(host, ss.mean, 3 * ob, hipMemcpyDeviceToHost, st));     // mean | energy | var
     HIP_TRY(hipStreamSynchronize(st));
     if (mean_out) memcpy(mean_out, host, ob);
     if (energy_out) memcpy(energy_out, host + (size_t)K * 3, ob);
     if (var_out) memcpy(var_out, host + (size_t)K * 6, ob);
     return 0;
 }
-
-
-}  // extern "C"

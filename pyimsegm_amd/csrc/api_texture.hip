@@ -146,18 +146,11 @@ int imsegm_image2d_lm_features_sep(imsegm_image2d *im, const double *weights, co
     HIP_TRY(hipMemcpyAsync(d_w, host, wtotal * 8, hipMemcpyHostToDevice, st));
     ctx->mark_stage_in_flight();
     // statistics scratch (as stats_run) and the K x F table
-    const int nflags = ((feature_mask & 1) != 0) + ((feature_mask & 2) != 0) + ((feature_mask & 4) != 0);
-    const int Fb = 3 * nflags, F = Fb * n_batteries;
+    const int Fb = color_feature_columns(feature_mask), F = Fb * n_batteries;
     int table_F = F, col0 = 0;
     if (take_placement(im, F, features_out != nullptr, &table_F, &col0)) return -1;
-    size_t fb = (size_t)K * (13 * 8 + 3 * 3 * 8 + 3 * 4) + 256;
-    if (im->feat.ensure(fb) || im->featK.ensure((size_t)K * table_F * 8 + 64)) return -1;
-    unsigned char *sb = im->feat.as<unsigned char>();
-    long long *acc = reinterpret_cast<long long *>(sb); sb += (size_t)K * 13 * 8;
-    double *d_mean = reinterpret_cast<double *>(sb); sb += (size_t)K * 3 * 8;
-    double *d_energy = reinterpret_cast<double *>(sb); sb += (size_t)K * 3 * 8;
-    double *d_var = reinterpret_cast<double *>(sb); sb += (size_t)K * 3 * 8;
-    float *d_mean32 = reinterpret_cast<float *>(sb);
+    if (im->feat.ensure(stats_scratch_bytes(K)) || im->featK.ensure((size_t)K * table_F * 8 + 64)) return -1;
+    const StatsScratch ss = stats_scratch_at(im->feat.p, K);
     for (int b0 = 0; b0 < n_batteries; b0 += ROUND) {
         const int cnt = std::min(ROUND, n_batteries - b0);
         int spx = ctx->begin(PG_TEX);
@@ -191,9 +184,9 @@ int imsegm_image2d_lm_features_sep(imsegm_image2d *im, const double *weights, co
         for (int j = 0; j < cnt; ++j) {
             const int b = b0 + j;
             if (launch_color_stats(resp + (size_t)j * 3 * n, IMSEGM_F64, im->labels.as<int32_t>(), im->H, im->W, K, 32768.0,
-                                   (feature_mask & 2) != 0, acc, d_mean, d_energy, d_var, d_mean32, st, 1, 2, 1.0, 1.0, -1, d_ssq + b))
+                                   (feature_mask & 2) != 0, ss.acc, ss.mean, ss.energy, ss.var, ss.mean32, st, 1, 2, 1.0, 1.0, -1, d_ssq + b))
                 return -1;
-            if (launch_features_assemble(d_mean, d_energy, d_var, K, feature_mask, im->featK.as<double>(), st, table_F, col0 + b * Fb))
+            if (launch_features_assemble(ss.mean, ss.energy, ss.var, K, feature_mask, im->featK.as<double>(), st, table_F, col0 + b * Fb))
                 return -1;
         }
         ctx->end(sps);

@@ -10,7 +10,7 @@
 // image's slice of ONE arena, a kernel reaches image b by adding b * slice bytes to each of its pointers (common.h ZBatch).
 // Per batch: B uploads, ~55 launches (not 55 * B), TWO host synchronisations (label counts after connectivity, the end), B
 // downloads.  Results are those of imsegm_image2d_run_color image by image, bit for bit (tests/test_gpu_batch.py).
-#include "session.h"
+#include "backhalf.h"
 
 #include <string>
 
@@ -37,10 +37,10 @@ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // offsets of the per-image buffers inside a slice
 struct Layout {
     size_t img, lab, nearest, labels, conn_i32, conn_i32_bytes, conn_u8, small, cent, tiles, feat, featK, seg, segm_out, total;
-    // inside `seg` (the back half: parameters, graph, terms, cut)
-    size_t o_misc, o_pw, o_sm, o_cl, o_sc, o_pc, o_mp, o_ld, o_lw, up_bytes;
-    size_t d_proba, d_unary, d_unary_i, d_w, d_wi, d_edist, d_elen, d_edges, d_as, d_at, d_ar, d_ea, d_deg, d_dlow, d_es, d_wp, d_gl,
-        d_lut, d_fstd, d_cacc, d_bitmap, d_cent, d_present, d_work, seg_bytes;
+    // inside `seg` (the back half): parameters, terms and cut (backhalf.h), then the graph
+    ParamBlock par;
+    TermsScratch scr;
+    size_t d_edges, d_as, d_at, d_ar, d_ea, d_deg, d_dlow, d_es, d_wp, d_cacc, d_bitmap, d_cent, d_present;
     int Kb, Ecap;                    // most labels an image can end up with, edge table rows
 };
 
@@ -65,31 +65,14 @@ Layout make_layout(int H, int W, size_t elem, int K_grid, size_t n_tiles, long m
     L.cent = take(slic_cent_bytes(K_grid));
     L.tiles = take(slic_tiles_bytes(n_tiles, n));
     const size_t Kb = (size_t)L.Kb, E = (size_t)L.Ecap, words = (size_t)cdiv(L.Kb, 32);
-    L.feat = take(Kb * (13 * 8 + 3 * 3 * 8 + 3 * 4) + 256);
+    L.feat = take(stats_scratch_bytes(Kb));
     L.featK = take(Kb * (size_t)std::max(F, 1) * 8 + 64);
     L.segm_out = take(n * 4);
     // ---- the back half, relative to L.seg
-    size_t q = 0;
-    auto sub = [&](size_t bytes) { size_t at = q; q += (bytes + 63) & ~(size_t)63; return at; };
-    const size_t FF = (size_t)F * F;
-    L.o_misc = sub(256);             // K | E | status | gc status | energy (8) ... scalars[8] at +64
-    L.o_pw = sub((size_t)C * C * 8);
-    L.o_sm = sub((size_t)C * C * 4);
-    L.o_cl = sub((size_t)C * 4);
-    L.o_sc = sub((size_t)2 * F * 8);
-    L.o_pc = sub((size_t)C * FF * 8);
-    L.o_mp = sub((size_t)C * F * 8);
-    L.o_ld = sub((size_t)C * 8);
-    L.o_lw = sub((size_t)C * 8);
-    L.up_bytes = q;
-    q = al256(q);
-    L.d_proba = sub(Kb * C * 8);
-    L.d_unary = sub(Kb * C * 8);
-    L.d_unary_i = sub(Kb * C * 4);
-    L.d_w = sub(E * 8);
-    L.d_wi = sub(E * 4);
-    L.d_edist = sub(E * 8);
-    L.d_elen = sub(E * 8);
+    L.par = param_block(C, F, 0);
+    L.scr = terms_scratch(L.par, L.Kb, C, F, L.Ecap, false);
+    size_t q = L.scr.end;
+    auto sub = [&](size_t bytes) { size_t at = q; q += al64(bytes); return at; };
     L.d_edges = sub(E * 8);
     L.d_as = sub((Kb + 1) * 4);
     L.d_at = sub(E * 8);
@@ -99,16 +82,11 @@ Layout make_layout(int H, int W, size_t elem, int K_grid, size_t n_tiles, long m
     L.d_dlow = sub(Kb * 4);
     L.d_es = sub(Kb * 4);
     L.d_wp = sub(Kb * words * 4);
-    L.d_gl = sub(Kb * 4);
-    L.d_lut = sub(Kb * 4);
-    L.d_fstd = sub((size_t)2 * std::max(F, 1) * 8);
-    L.d_cacc = sub(Kb * 4 * 8);      // (right in front of the bitmap: one fill zeroes both)
+    L.d_cacc = sub(Kb * 4 * 8);      // (not behind the bitmap rows in use: launch_adjacency_bitmap zeroes the two with a fill each)
     L.d_bitmap = sub(Kb * words * 4);
     L.d_cent = sub(Kb * 3 * 8);
     L.d_present = sub(Kb);
-    L.d_work = sub(alpha_expansion_work_bytes(L.Kb, L.Ecap));
-    L.seg_bytes = q;
-    L.seg = take(L.seg_bytes + 256);
+    L.seg = take(q + 256);
     L.total = al256(o);
     return L;
 }
@@ -205,23 +183,14 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
         set_error("batch2d_run_color: colour features (mask 1..7), a device class model, 1..16 classes and a pairwise matrix are required");
         return -1;
     }
-    const int edge_code = edge_type & 0xff, spatial_norm = (edge_type & IMSEGM_EDGE_SPATIAL_NORM) ? 1 : 0;
-    if (edge_code < 0 || edge_code > 5) {
-        set_error("segment: unknown edge type");
-        return -1;
-    }
-    const int nflags = ((feature_mask & 1) != 0) + ((feature_mask & 2) != 0) + ((feature_mask & 4) != 0);
-    const int F = 3 * nflags;
+    BackHalf bh;
+    if (decode_edge_type(edge_type, &bh.edge_code, &bh.spatial_norm)) return -1;
+    const int F = color_feature_columns(feature_mask);
     if (gmm->n_features != F || gmm->n_classes != C) {
         set_error("segment: class model does not match the resident features / number of classes");
         return -1;
     }
-    for (int a = 0; a < C; ++a)
-        for (int b = 0; b < C; ++b)
-            if (pairwise[a * C + b] != pairwise[b * C + a]) {
-                set_error("Cost matrix not square or not symmetric");
-                return -1;
-            }
+    if (check_pairwise(pairwise, C)) return -1;
     Taps tz, ty, tx;
     if (fill_taps(tz, taps, radius) || fill_taps(ty, taps, radius) || fill_taps(tx, taps, radius)) return -1;
     if (radius > 8 || knobs().pre_3pass) {
@@ -242,7 +211,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
     }
     const Layout L = make_layout(H, W, es, K, geo.n_tiles, min_size, C, F);
     const size_t slice = L.total;
-    const size_t stage_row = al256(std::max<size_t>(L.up_bytes, 256));      // per image: parameter block in, counters out
+    const size_t stage_row = al256(std::max<size_t>(L.par.bytes, 256));      // per image: parameter block in, counters out
     const size_t arena_bytes = slice * bt->B + stage_row * bt->B + 4096;
     const bool same = bt->key.size() == sizeof(L) && !memcmp(bt->key.data(), &L, sizeof(L)) && bt->slice == slice && bt->arena.cap >= arena_bytes;
     if (!same) {
@@ -287,13 +256,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
         return -1;
     ctx->end(sp_pre);
     slic_place_state(s, geo, base + L.cent, base + L.tiles, premax, bt->fail_host);
-    ProfHook hook;
-    if (ctx->profile) {
-        hook.user = ctx;
-        hook.begin = [](void *u, int g) { return static_cast<imsegm_ctx *>(u)->begin(g); };
-        hook.end = [](void *u, int id) { static_cast<imsegm_ctx *>(u)->end(id); };
-        hook.pair = [](void *u, int g, hipEvent_t *a, hipEvent_t *b) { static_cast<imsegm_ctx *>(u)->pair(g, a, b); };
-    }
+    const ProfHook hook = ctx->hook();
     bool fused_update = false;
     if (launch_slic_iterations(s, lab, nullptr, nearest, max_iter, 0, hook, st, &fused_update, zb)) return -1;
 
@@ -344,12 +307,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
 
     // ---- descriptors: colour statistics of the uploaded pixels on the label maps, feature table K x F
     {
-        unsigned char *fb = base + L.feat;
-        long long *acc = reinterpret_cast<long long *>(fb); fb += (size_t)L.Kb * 13 * 8;
-        double *d_mean = reinterpret_cast<double *>(fb); fb += (size_t)L.Kb * 3 * 8;
-        double *d_energy = reinterpret_cast<double *>(fb); fb += (size_t)L.Kb * 3 * 8;
-        double *d_var = reinterpret_cast<double *>(fb); fb += (size_t)L.Kb * 3 * 8;
-        float *d_mean32 = reinterpret_cast<float *>(fb);
+        const StatsScratch ss = stats_scratch_at(base + L.feat, L.Kb);
         const double *mm_dev = nullptr;
         if (dtype != IMSEGM_U8) {
             // float images: the fixed-point scale of the sums follows each image's own largest magnitude (its min / max on the
@@ -358,10 +316,10 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
             mm_dev = minmax;
         }
         const int sps = ctx->begin(PG_STATS);
-        if (launch_color_stats(base + L.img, dtype, labels, H, W, K_cap, 255.0, (feature_mask & 2) != 0, acc, d_mean, d_energy, d_var,
-                               d_mean32, st, 0, 0, 1.0, 1.0, -1, nullptr, zb, mm_dev))
+        if (launch_color_stats(base + L.img, dtype, labels, H, W, K_cap, 255.0, (feature_mask & 2) != 0, ss.acc, ss.mean, ss.energy, ss.var,
+                               ss.mean32, st, 0, 0, 1.0, 1.0, -1, nullptr, zb, mm_dev))
             return -1;
-        if (launch_features_assemble(d_mean, d_energy, d_var, K_cap, feature_mask, reinterpret_cast<double *>(base + L.featK), st, 0, 0, zb))
+        if (launch_features_assemble(ss.mean, ss.energy, ss.var, K_cap, feature_mask, reinterpret_cast<double *>(base + L.featK), st, 0, 0, zb))
             return -1;
         ctx->end(sps);
     }
@@ -370,102 +328,40 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
     unsigned char *seg = base + L.seg;
     if (batch_pinned(bt, stage_row * n_images + 64)) return -1;
     unsigned char *host = static_cast<unsigned char *>(bt->pinned);
-    int smax = 0;
-    double pmax = -DBL_MAX;
-    int metric = 0;
-    {
-        unsigned char *row = host;
-        memset(row, 0, stage_row);
-        memcpy(row + L.o_pw, pairwise, (size_t)C * C * 8);
-        int32_t *si = reinterpret_cast<int32_t *>(row + L.o_sm);
-        for (int i = 0; i < C * C; ++i) {
-            si[i] = (int32_t)(pairwise[i] * 100);                 // pygco: smooth cost * 100, truncated
-            smax = std::max(smax, std::abs(si[i]));
-            pmax = std::max(pmax, pairwise[i]);
-        }
-        metric = smooth_is_metric(si, C);
-        if (classes_lut) memcpy(row + L.o_cl, classes_lut, (size_t)C * 4);
-        if (gmm->scaler_mean) memcpy(row + L.o_sc, gmm->scaler_mean, (size_t)F * 8);
-        if (gmm->scaler_scale) memcpy(row + L.o_sc + (size_t)F * 8, gmm->scaler_scale, (size_t)F * 8);
-        memcpy(row + L.o_pc, gmm->prec_chol, (size_t)C * F * F * 8);
-        memcpy(row + L.o_mp, gmm->mu_proj, (size_t)C * F * 8);
-        memcpy(row + L.o_ld, gmm->log_det, (size_t)C * 8);
-        memcpy(row + L.o_lw, gmm->log_weights, (size_t)C * 8);
-        for (int b = 0; b < n_images; ++b) {
-            if (b) memcpy(host + (size_t)b * stage_row, host, stage_row);
-            reinterpret_cast<int32_t *>(host + (size_t)b * stage_row + L.o_misc)[0] = nl[b];      // E, status words, energy: zero
-        }
+    memset(host, 0, stage_row);
+    bh.par = L.par; bh.scr = L.scr; bh.C = C; bh.F = F;
+    param_fill(bh, host, nl[0], pairwise, classes_lut, gmm, nullptr);
+    for (int b = 1; b < n_images; ++b) {
+        memcpy(host + (size_t)b * stage_row, host, stage_row);
+        reinterpret_cast<int32_t *>(host + (size_t)b * stage_row + L.par.o_misc)[0] = nl[b];      // E, status words, energy: zero
     }
     HIP_TRY(hipMemcpyAsync(stage_dev, host, stage_row * n_images, hipMemcpyHostToDevice, st));
-    if (launch_copy_rows(seg, slice, stage_dev, stage_row, L.up_bytes, n_images, st)) return -1;
-    int32_t *misc = reinterpret_cast<int32_t *>(seg + L.o_misc);
-    int32_t *K_dev = misc, *E_dev = misc + 1, *status = misc + 2;
-    long long *energy = reinterpret_cast<long long *>(seg + L.o_misc + 16);
-    double *scalars = reinterpret_cast<double *>(seg + L.o_misc + 64);
+    if (launch_copy_rows(seg, slice, stage_dev, stage_row, L.par.bytes, n_images, st)) return -1;
+    bh.base = seg;
+    int32_t *misc = bh.misc();
+    bh.K_dev = misc; bh.E_dev = misc + 1;
 
     // ---- graph: bitmap + centres, then the symmetric CSR
     uint32_t *bitmap = reinterpret_cast<uint32_t *>(seg + L.d_bitmap);
     long long *cacc = reinterpret_cast<long long *>(seg + L.d_cacc);
-    double *centres = reinterpret_cast<double *>(seg + L.d_cent);
+    bh.centres = reinterpret_cast<double *>(seg + L.d_cent); bh.edges = reinterpret_cast<int32_t *>(seg + L.d_edges);
+    bh.arc_start = reinterpret_cast<int32_t *>(seg + L.d_as); bh.arc_to = reinterpret_cast<int32_t *>(seg + L.d_at);
+    bh.arc_rev = reinterpret_cast<int32_t *>(seg + L.d_ar); bh.edge_arc = reinterpret_cast<int32_t *>(seg + L.d_ea);
     const int spg = ctx->begin(PG_GRAPH);
-    if (launch_adjacency_bitmap(labels, H, W, K_cap, bitmap, cacc, centres, seg + L.d_present, st, zb)) return -1;
-    int32_t *edges = reinterpret_cast<int32_t *>(seg + L.d_edges);
-    if (launch_graph_csr(bitmap, K_dev, K_cap, words, reinterpret_cast<int32_t *>(seg + L.d_wp), reinterpret_cast<int32_t *>(seg + L.d_deg),
-                         reinterpret_cast<int32_t *>(seg + L.d_dlow), reinterpret_cast<int32_t *>(seg + L.d_as),
-                         reinterpret_cast<int32_t *>(seg + L.d_es), E_dev, Ecap, edges, reinterpret_cast<int32_t *>(seg + L.d_at),
-                         reinterpret_cast<int32_t *>(seg + L.d_ar), reinterpret_cast<int32_t *>(seg + L.d_ea), st, zb))
+    if (launch_adjacency_bitmap(labels, H, W, K_cap, bitmap, cacc, bh.centres, seg + L.d_present, st, zb)) return -1;
+    if (launch_graph_csr(bitmap, bh.K_dev, K_cap, words, reinterpret_cast<int32_t *>(seg + L.d_wp), reinterpret_cast<int32_t *>(seg + L.d_deg),
+                         reinterpret_cast<int32_t *>(seg + L.d_dlow), bh.arc_start, reinterpret_cast<int32_t *>(seg + L.d_es), bh.E_dev, Ecap,
+                         bh.edges, bh.arc_to, bh.arc_rev, bh.edge_arc, st, zb))
         return -1;
     ctx->end(spg);
 
-    // ---- class probabilities, unary / edge terms, integer energies
-    TermsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.zs = slice;
-    a.Kp = K_dev; a.K_cap = K_cap; a.Ep = E_dev; a.edge_capacity = Ecap; a.F = F; a.C = C;
-    a.features = reinterpret_cast<double *>(base + L.featK);
-    a.gmm = 1;
-    a.scaler_mean = gmm->scaler_mean ? reinterpret_cast<double *>(seg + L.o_sc) : nullptr;
-    a.scaler_scale = gmm->scaler_scale ? reinterpret_cast<double *>(seg + L.o_sc) + F : nullptr;
-    a.prec_chol = reinterpret_cast<double *>(seg + L.o_pc);
-    a.mu_proj = reinterpret_cast<double *>(seg + L.o_mp);
-    a.log_det = reinterpret_cast<double *>(seg + L.o_ld);
-    a.log_w = reinterpret_cast<double *>(seg + L.o_lw);
-    a.const_term = gmm->const_term;
-    a.proba = reinterpret_cast<double *>(seg + L.d_proba);
-    a.edge_type = edge_code; a.spatial_norm = spatial_norm; a.edge_cost = edge_cost;
-    a.edges = edges; a.centres = centres; a.ndim = 2;
-    a.edge_dist = reinterpret_cast<double *>(seg + L.d_edist); a.edge_len = reinterpret_cast<double *>(seg + L.d_elen);
-    a.unary = reinterpret_cast<double *>(seg + L.d_unary); a.weights = reinterpret_cast<double *>(seg + L.d_w);
-    a.pairwise = reinterpret_cast<double *>(seg + L.o_pw); a.pairwise_max = pmax;
-    a.unary_i = reinterpret_cast<int32_t *>(seg + L.d_unary_i); a.weights_i = reinterpret_cast<int32_t *>(seg + L.d_wi);
-    a.smooth_max = smax; a.status = status; a.scalars = scalars; a.fstd = reinterpret_cast<double *>(seg + L.d_fstd);
-    const int spt = ctx->begin(PG_TERMS);
-    if (launch_gc_terms(a, st, n_images)) return -1;
-    ctx->end(spt);
-
-    // ---- alpha-expansion: one workgroup per image of ONE launch (or the argmin of the unary cost for gc_regul <= 0)
-    int32_t *glab = reinterpret_cast<int32_t *>(seg + L.d_gl);
-    const int spc2 = ctx->begin(PG_GC);
-    if (use_graphcut) {
-        GcProblem p;
-        p.K = K_cap; p.C = C; p.E = Ecap; p.E_dev = E_dev; p.K_dev = K_dev;
-        p.edges = edges; p.w = a.weights_i; p.unary = a.unary_i; p.smooth = reinterpret_cast<int32_t *>(seg + L.o_sm);
-        p.metric = metric;
-        if (launch_alpha_expansion(p, reinterpret_cast<int32_t *>(seg + L.d_as), reinterpret_cast<int32_t *>(seg + L.d_at),
-                                   reinterpret_cast<int32_t *>(seg + L.d_ar), reinterpret_cast<int32_t *>(seg + L.d_ea), -1, glab, energy,
-                                   status + 1, seg + L.d_work, st, zb))
-            return -1;
-    } else if (launch_unary_argmin(a.unary, K_dev, K_cap, C, glab, st, zb)) {
-        return -1;
-    }
-    ctx->end(spc2);
-
-    // ---- gather classes_[graph_labels][slic], results down
-    int32_t *lut = reinterpret_cast<int32_t *>(seg + L.d_lut);
-    if (launch_label_lut(glab, K_dev, K_cap, classes_lut ? reinterpret_cast<int32_t *>(seg + L.o_cl) : nullptr, lut, st, zb)) return -1;
-    const int spq = ctx->begin(PG_GATHER);
-    if (launch_gather_labels(lut, labels, n, reinterpret_cast<int32_t *>(base + L.segm_out), st, zb)) return -1;
-    ctx->end(spq);
+    // ---- terms, cut, gather classes_[graph_labels][slic]; results down
+    bh.features = reinterpret_cast<double *>(base + L.featK);
+    bh.labels = labels; bh.n = n;
+    bh.segm_out = reinterpret_cast<int32_t *>(base + L.segm_out); bh.soft_out = nullptr;
+    bh.K_cap = K_cap; bh.Ecap = Ecap; bh.ndim = 2;
+    bh.edge_cost = edge_cost; bh.use_graphcut = use_graphcut; bh.zb = zb;
+    if (backhalf_enqueue(ctx, bh)) return -1;
     if (segm_out)
         for (int b = 0; b < n_images; ++b)
             if (segm_out[b])
@@ -475,19 +371,9 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
     HIP_TRY(hipMemcpyAsync(hmisc.data(), stage_dev, (size_t)16 * n_images, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int b = 0; b < n_images; ++b) {
-        const int32_t *m = hmisc.data() + (size_t)4 * b;
-        if (m[2] & 2) {
-            set_error("batch2d_run_color: image " + std::to_string(b) + " has more graph edges than a planar graph of its labels");
-            return -1;
-        }
-        if (use_graphcut && (m[2] & 1)) {
-            set_error("cut_general_graph: smoothness term is larger than GCO_MAX_ENERGYTERM");
-            return -1;
-        }
-        if (use_graphcut && m[3] != 0) {
-            set_error("alpha_expansion: max-flow did not converge");
-            return -1;
-        }
+        const int rc = backhalf_status(hmisc.data() + (size_t)4 * b, use_graphcut);
+        if (rc == -2) set_error("batch2d_run_color: image " + std::to_string(b) + " has more graph edges than a planar graph of its labels");
+        if (rc) return -1;
     }
     return 0;
 }

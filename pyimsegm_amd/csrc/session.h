@@ -1,5 +1,6 @@
 // session.h -- the host-side objects behind the C ABI (include/imsegm_hip.h): context (device + stream + profiler), the
-// device-resident state of one image / volume, and the small helpers api.hip and batch.hip share.
+// device-resident state of one image / volume, and the small helpers the api_*.hip files and batch.hip share.  (The fused back
+// half behind a label map, which api_fused.hip and batch.hip both run, is backhalf.h / backhalf.hip.)
 #pragma once
 #include "../../include/imsegm_hip.h"
 #include "slic.h"
@@ -119,6 +120,18 @@ struct imsegm_ctx {
         spans.push_back(s);
         *a = s.a;
         *b = s.b;
+    }
+    // the hooks a launch chain that times its own kernels takes: empty when profiling is off
+    ProfHook hook()
+    {
+        ProfHook hook;
+        if (profile) {
+            hook.user = this;
+            hook.begin = [](void *u, int g) { return static_cast<imsegm_ctx *>(u)->begin(g); };
+            hook.end = [](void *u, int id) { static_cast<imsegm_ctx *>(u)->end(id); };
+            hook.pair = [](void *u, int g, hipEvent_t *a, hipEvent_t *b) { static_cast<imsegm_ctx *>(u)->pair(g, a, b); };
+        }
+        return hook;
     }
     void collect()
     {
@@ -268,15 +281,30 @@ inline bool is_pinned(const void *p)
 }
 
 
-// helpers shared by the files of the C ABI (api.hip was split by stage in round 6): defined in api_volume.hip, api_image2d.hip,
-// api_fused.hip
-extern "C" {
+namespace imsegm {
+
+// scratch of launch_color_stats for K labels: 13 int64 sums per label | mean, energy, variance (3 doubles each) | float32 means
+struct StatsScratch {
+    long long *acc;
+    double *mean, *energy, *var;
+    float *mean32;
+};
+inline size_t stats_scratch_bytes(size_t K) { return K * (13 * 8 + 3 * 3 * 8 + 3 * 4) + 256; }
+inline StatsScratch stats_scratch_at(void *base, size_t K)
+{
+    double *m = reinterpret_cast<double *>(static_cast<long long *>(base) + K * 13);
+    return { static_cast<long long *>(base), m, m + K * 3, m + K * 6, reinterpret_cast<float *>(m + K * 9) };
+}
+// columns of the colour descriptors of a feature_mask (1 mean, 2 std, 4 energy): three channels per statistic
+inline int color_feature_columns(int feature_mask) { return 3 * (((feature_mask & 1) != 0) + ((feature_mask & 2) != 0) + ((feature_mask & 4) != 0)); }
 // segmented statistics of `src` on the session's label map (mean, energy, variance: any may be null); planar: [C][H][W] planes
+// (api_image2d.hip)
 int stats_run(imsegm_image2d *im, const void *src, int dtype, double maxabs, int planar, int prescale, double mul, double div,
               double *mean_out, double *energy_out, double *var_out, long plane_stride = -1);
-// where a descriptor call puts its columns of the resident feature table (imsegm_image2d_features_place)
+// where a descriptor call puts its columns of the resident feature table (imsegm_image2d_features_place; api_fused.hip)
 int take_placement(imsegm_image2d *im, int own_F, bool to_host, int *table_F, int *col0);
-}
+
+}  // namespace imsegm
 
 // what of the 2-D SLIC state follows from the sizes (api_image2d.hip)
 struct SlicGeometry {
