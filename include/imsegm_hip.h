@@ -33,6 +33,10 @@ extern "C" {
  * imsegm_image2d_graph and cuts it with imsegm_cut_general_graph, the staged calls of imsegm/graph_cuts.py:660-747 */
 #define IMSEGM_E_FUSED_PATH (-3)
 
+/* status of imsegm_kmeans_lloyd / imsegm_mixture_em for a problem outside the caps of the device fit (more than 16 features, 8
+ * components, 16 restarts, 2^31 - 1 rows): nothing is wrong with the context -- the caller fits on the host */
+#define IMSEGM_E_FIT_CAPS (-4)
+
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
 typedef struct imsegm_image2d imsegm_image2d;   /* device-resident state of one H x W image */
 
@@ -416,6 +420,35 @@ IMSEGM_API int imsegm_ray_features_binary2d(imsegm_ctx *ctx, const int8_t *seg_b
 IMSEGM_API int imsegm_cut_general_graph(imsegm_ctx *ctx, const int32_t *edges, int n_edges, const double *edge_weights,
                              const double *unary_cost, int n_sites, int n_labels, const double *pairwise_cost,
                              int n_iter, int32_t *labels_out, int64_t *energy_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * the class model's fit (imsegm/graph_cuts.py:73-163 estim_class_model: scikit-learn's GaussianMixture.fit on the host in the
+ * reference) for all restarts at once on one uploaded table; sums in a fixed order, no atomics: same call, same bits
+ * ------------------------------------------------------------------------------------------- */
+/* Replaces the Lloyd iterations of sklearn.cluster.KMeans(algorithm='lloyd') (sklearn/cluster/_kmeans.py _kmeans_single_lloyd,
+ * the initialisation GaussianMixture(init_params='kmeans') runs per restart) from given centres.  table: n_rows x n_features
+ * float64, uploaded once and kept in the context for the imsegm_mixture_em that follows; seeds: n_restarts x n_clusters x
+ * n_features.  Nearest centre with ties to the lowest index; a restart stops when no label changes, or when the summed squared
+ * centre shift is <= tol (absolute; then one more labelling), or after max_iter iterations.  Per restart (each output may be
+ * NULL): labels_out n_restarts x n_rows int32, centres_out, inertia_out, n_iter_out, empty_out (1: an iteration left a cluster
+ * without rows -- the restart stopped there, nothing is repaired).  The labels also stay on the device.
+ * Returns IMSEGM_E_FIT_CAPS outside n_features <= 16, n_clusters <= 8, n_restarts <= 16, n_rows < 2^31. */
+IMSEGM_API int imsegm_kmeans_lloyd(imsegm_ctx *ctx, const double *table, long n_rows, int n_features, const double *seeds,
+                                   int n_restarts, int n_clusters, int max_iter, double tol, int32_t *labels_out,
+                                   double *centres_out, double *inertia_out, int32_t *n_iter_out, int32_t *empty_out);
+/* Replaces the EM loop of sklearn.mixture.GaussianMixture(covariance_type='full') (sklearn/mixture/_base.py fit_predict with
+ * _gaussian_mixture.py _estimate_gaussian_parameters -- covariances in their centred form --, _compute_precision_cholesky,
+ * _estimate_log_gaussian_prob) on the resident table.  Start per restart: the three *_init arrays (n_restarts x n_components
+ * [x n_features [x n_features]]; weights, means, precisions_cholesky_), or else one-hot responsibilities from `labels`
+ * (n_restarts x n_rows int32, host), or else (labels NULL) from the labels the last imsegm_kmeans_lloyd left on the device.
+ * A restart stops when |lower bound - previous| < tol or after max_iter iterations (tol = 0: exactly max_iter) and is frozen
+ * from then on.  Outputs per restart (each may be NULL): weights, means, covariances, precision Cholesky factors, last lower
+ * bound, iterations, converged flag, not_pd_out (1: a covariance was not positive definite -- the restart stopped there). */
+IMSEGM_API int imsegm_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_components, const int32_t *labels,
+                                 const double *weights_init, const double *means_init, const double *prec_chol_init,
+                                 double reg_covar, double tol, int max_iter, double *weights_out, double *means_out,
+                                 double *covariances_out, double *prec_chol_out, double *lower_bound_out, int32_t *n_iter_out,
+                                 int32_t *converged_out, int32_t *not_pd_out);
 
 #ifdef __cplusplus
 }

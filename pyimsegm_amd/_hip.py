@@ -45,7 +45,14 @@ class HipFusedPathError(HipError):
     caller takes the staged calls (graph, terms, ``cut_general_graph``, gather) instead"""
 
 
+class HipFitCapsError(HipError):
+    """``IMSEGM_E_FIT_CAPS`` of include/imsegm_hip.h: the table or the model is outside the caps of the device fit
+    (``imsegm_kmeans_lloyd`` / ``imsegm_mixture_em``: 16 features, 8 components, 16 restarts) -- nothing is wrong with the
+    context, the caller fits on the host"""
+
+
 IMSEGM_E_FUSED_PATH = -3
+IMSEGM_E_FIT_CAPS = -4
 
 
 _lib = None
@@ -146,6 +153,9 @@ _SIGNATURES = {
     'imsegm_ray_features_binary2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_cut_general_graph': (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp,
                                            C.POINTER(C.c_int64)]),
+    'imsegm_kmeans_lloyd': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'imsegm_mixture_em': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -211,7 +221,7 @@ def reload_env():
 def _check(status):
     if status != 0:
         message = load_library().imsegm_last_error().decode('utf-8', 'replace')
-        raise (HipFusedPathError if status == IMSEGM_E_FUSED_PATH else HipError)(message)
+        raise {IMSEGM_E_FUSED_PATH: HipFusedPathError, IMSEGM_E_FIT_CAPS: HipFitCapsError}.get(status, HipError)(message)
 
 
 _device_count = {}
@@ -386,6 +396,54 @@ def pinned_empty(shape, dtype):
     buf = (C.c_char * size).from_address(ptr)
     buf._block = block                                    # the ctypes buffer (base of the array) keeps the block alive
     return np.frombuffer(buf, dtype=dtype, count=nbytes // dtype.itemsize).reshape(shape)
+
+
+def kmeans_lloyd(table, seeds, max_iter=300, tol=0., want_labels=True, ctx=None):
+    """``imsegm_kmeans_lloyd``: Lloyd iterations of all restarts at once from the centres ``seeds`` (R x C x F) on ``table``
+    (n x F float64), which stays on the device of ``ctx`` for :func:`mixture_em`.  ``tol`` is absolute (scikit-learn's
+    ``tol * mean(var(table, axis=0))``).  Returns a dict: labels (R x n int32, or None when not wanted -- they stay on the device
+    either way), centres, inertia, n_iter, empty (R flags: a cluster lost all its rows, the restart stopped there).
+    Raises :class:`HipFitCapsError` outside F <= 16, C <= 8, R <= 16."""
+    ctx = ctx or default_context()
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    seeds = np.ascontiguousarray(seeds, dtype=np.float64)
+    if table.ndim != 2 or seeds.ndim != 3 or seeds.shape[2] != table.shape[1]:
+        raise ValueError('table is n x F, seeds are R x C x F')
+    n_restarts, n_clusters, _ = seeds.shape
+    labels = np.empty((n_restarts, len(table)), dtype=np.int32) if want_labels else None
+    centres, inertia = np.empty_like(seeds), np.empty(n_restarts)
+    n_iter, empty = np.zeros(n_restarts, dtype=np.int32), np.zeros(n_restarts, dtype=np.int32)
+    _check(load_library().imsegm_kmeans_lloyd(ctx._h, _ptr(table), len(table), table.shape[1], _ptr(seeds), n_restarts, n_clusters,
+                                              int(max_iter), float(tol), _ptr(labels), _ptr(centres), _ptr(inertia), _ptr(n_iter),
+                                              _ptr(empty)))
+    return dict(labels=labels, centres=centres, inertia=inertia, n_iter=n_iter, empty=empty.astype(bool))
+
+
+def mixture_em(n_restarts, n_components, n_features, labels=None, start=None, reg_covar=1e-6, tol=1e-3, max_iter=100, ctx=None):
+    """``imsegm_mixture_em``: EM for full covariances, all restarts at once, on the table the last :func:`kmeans_lloyd` of ``ctx``
+    uploaded.  Start: ``start`` = (weights R x C, means R x C x F, precisions_cholesky R x C x F x F), or one-hot responsibilities
+    from ``labels`` (R x n int32), or -- both None -- from the labels that call left on the device.  Returns a dict: weights,
+    means, covariances, precisions_cholesky, lower_bound, n_iter, converged, not_pd (R flags: a covariance was not positive
+    definite, the restart stopped there)."""
+    ctx = ctx or default_context()
+    R, K, F = int(n_restarts), int(n_components), int(n_features)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(R, -1)
+    w0 = m0 = p0 = None
+    if start is not None:
+        w0, m0, p0 = (np.ascontiguousarray(v, dtype=np.float64) for v in start)
+        if w0.shape != (R, K) or m0.shape != (R, K, F) or p0.shape != (R, K, F, F):
+            raise ValueError('start parameters are (R x C, R x C x F, R x C x F x F)')
+    safe = (min(R, 16), min(K, 8), min(F, 16))          # (beyond the caps the call writes nothing)
+    weights, means = np.zeros(safe[:2]), np.zeros(safe)
+    cov, prec = np.zeros(safe + (safe[2], )), np.zeros(safe + (safe[2], ))
+    bound = np.zeros(safe[0])
+    n_iter, converged, not_pd = (np.zeros(safe[0], dtype=np.int32) for _ in range(3))
+    _check(load_library().imsegm_mixture_em(ctx._h, R, K, _ptr(labels), _ptr(w0), _ptr(m0), _ptr(p0), float(reg_covar), float(tol),
+                                            int(max_iter), _ptr(weights), _ptr(means), _ptr(cov), _ptr(prec), _ptr(bound), _ptr(n_iter),
+                                            _ptr(converged), _ptr(not_pd)))
+    return dict(weights=weights, means=means, covariances=cov, precisions_cholesky=prec, lower_bound=bound, n_iter=n_iter,
+                converged=converged.astype(bool), not_pd=not_pd.astype(bool))
 
 
 class DeviceGmm(object):

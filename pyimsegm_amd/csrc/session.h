@@ -58,6 +58,10 @@ struct imsegm_ctx {
     int acc_n[PG_COUNT] = { 0 };
     DevBuf gc_buf;   // scratch of imsegm_cut_general_graph
     DevBuf aux_buf;  // small second scratch (border histogram of imsegm_assume_bg_on_boundary)
+    // mixture fit on the device (csrc/mixture_fit.hip): the n x F table imsegm_kmeans_lloyd uploaded stays here for the
+    // imsegm_mixture_em that follows, with the labels of its R restarts behind it in `fit_work`
+    DevBuf fit_table, fit_work;
+    int fit_n = 0, fit_F = 0, fit_label_restarts = 0, fit_label_classes = 0;
     void *pinned = nullptr;          // page-locked staging for the small host <-> device transfers
     size_t pinned_cap = 0;
     hipEvent_t pinned_ev = nullptr;   // recorded after an H2D out of `pinned` that nobody waits for

@@ -9,7 +9,8 @@ device sessions:
 * the per-edge formulas of ``graph_cuts.py:303-657`` are evaluated on the device inside the fused pipeline call
   (``csrc/terms.hip``); the numpy forms below serve callers that enter at this stage with their own arrays, and the
   parity tests, and give the same integer energies;
-* the mixture fit is scikit-learn on the host, configured as ``graph_cuts.py:73-163`` configures it.
+* the mixture fit is scikit-learn on the host, configured as ``graph_cuts.py:73-163`` configures it; ``fit_on='device'``
+  (or ``IMSEGM_FIT_ON=device``) runs its Lloyd and EM iterations in ``csrc/mixture_fit.hip`` instead (:func:`fit_mixture_device`).
 
 The alternative class models of ``graph_cuts.py:73-163`` (``GMM_kmeans``, ``GMM_Otsu``, ``kmeans``, ``kmeans_quantiles``,
 ``BGM``, ``Otsu``) are configured here too (:func:`estim_class_model`, one table row each): they are public parameters of the
@@ -416,14 +417,121 @@ def fit_mixture_restarts(mixture, table, workers=None):
     return mixture
 
 
-def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, use_scaler=True, max_iter=99):
+#: rows the k-means++ seeding of the device fit sees at most: every ceil(n / 16384)-th row of the table
+DEVICE_FIT_SEEDING_ROWS = 16384
+#: scikit-learn's KMeans defaults, which GaussianMixture(init_params='kmeans') runs with
+_KMEANS_MAX_ITER, _KMEANS_TOL = 300, 1e-4
+
+
+def device_fit_seeds(table, n_components, n_init, stream):
+    """the start centres of the ``n_init`` restarts of the device fit, R x C x F: ``sklearn.cluster.kmeans_plusplus``, one
+    restart after the other from ``stream``, on every ceil(n / 16384)-th row of the table (the seeding of all 298 116 rows of a
+    volume's table nine times costs half of the host fit; on 16 384 rows it is milliseconds)"""
+    from sklearn.cluster import kmeans_plusplus
+    rows = table[::-(-len(table) // DEVICE_FIT_SEEDING_ROWS)]
+    return np.stack([kmeans_plusplus(rows, n_components, random_state=stream)[0] for _ in range(n_init)])
+
+
+def _device_fit_refusal(mixture, table):
+    """why this mixture / table is fitted on the host although the device was asked for, or None"""
+    from sklearn.mixture import GaussianMixture
+    if type(mixture) is not GaussianMixture:
+        return 'the device fits plain GaussianMixture only, not %s' % type(mixture).__name__
+    if mixture.covariance_type != 'full' or mixture.init_params != 'kmeans':
+        return 'the device fits full covariances from a k-means initialisation only'
+    if mixture.warm_start or any(getattr(mixture, name) is not None for name in ('weights_init', 'means_init', 'precisions_init')):
+        return 'warm starts and given initial parameters are fitted on the host'
+    if table.dtype != np.float64:
+        return 'a %s table is fitted on the host' % table.dtype
+    if len(table) < mixture.n_components:
+        return 'fewer rows than components'
+    return None
+
+
+def fit_mixture_device(mixture, table, ctx=None):
+    """ ``mixture.fit(table)`` with the Lloyd and EM iterations of all ``n_init`` restarts on the device (``csrc/mixture_fit.hip``:
+    ``imsegm_kmeans_lloyd``, ``imsegm_mixture_em``), for ``GaussianMixture(covariance_type='full', init_params='kmeans')``.
+
+    Seeds from :func:`device_fit_seeds`, Lloyd with the KMeans defaults, EM from the labels with the mixture's ``reg_covar``,
+    ``tol``, ``max_iter``; the restart with the first largest lower bound (the rule of ``BaseMixture.fit_predict``) is written
+    into the ordinary scikit-learn estimator.  The sums run in another order than scikit-learn's: the result agrees with a host
+    fit from the same seeds to the last digits, not bit for bit, and the seeds are not the ones ``mixture.fit`` draws.
+
+    Whatever the device does not fit goes to :func:`fit_mixture_restarts`, on the random stream as it stood, with the reason
+    logged at INFO: more than 16 features / 8 components / 16 restarts, a restart with an empty cluster or a covariance that is
+    not positive definite (the host fit repairs or raises what scikit-learn raises), another kind of mixture, a float32 table.
+    A table with NaN or inf raises scikit-learn's ValueError; no library or no GPU raises ``HipUnavailableError``.
+    """
+    import warnings
+    from sklearn.exceptions import ConvergenceWarning
+    from sklearn.utils import check_array, check_random_state
+    table = np.asarray(table)
+    reason = _device_fit_refusal(mixture, table) if table.ndim == 2 else 'the table is not two-dimensional'
+    if reason is None:
+        check_array(table, dtype=[np.float64], ensure_min_samples=2)        # (NaN / inf: ValueError before anything is uploaded)
+        ctx = ctx or _hip.default_context()                                # (HipUnavailableError without a library or a GPU)
+        stream = check_random_state(mixture.random_state)
+        stream_state = stream.get_state()
+        table = np.ascontiguousarray(table)
+        n_init, n_comp = int(mixture.n_init), int(mixture.n_components)
+        try:
+            if hasattr(mixture, '_validate_params'):
+                mixture._validate_params()
+            seeds = device_fit_seeds(table, n_comp, n_init, stream)
+            lloyd = _hip.kmeans_lloyd(table, seeds, _KMEANS_MAX_ITER, _KMEANS_TOL * np.mean(np.var(table, axis=0)),
+                                      want_labels=False, ctx=ctx)
+            if lloyd['empty'].any():
+                reason = 'k-means left a cluster empty in restart %d' % int(np.argmax(lloyd['empty']))
+            else:
+                fit = _hip.mixture_em(n_init, n_comp, table.shape[1], reg_covar=mixture.reg_covar, tol=mixture.tol,
+                                      max_iter=mixture.max_iter, ctx=ctx)
+                if fit['not_pd'].any():
+                    reason = 'a covariance of restart %d is not positive definite' % int(np.argmax(fit['not_pd']))
+        except _hip.HipFitCapsError as ex:
+            reason = str(ex)
+        if reason is not None:
+            stream.set_state(stream_state)
+    if reason is not None:
+        logging.info('mixture fit on the host: %s', reason)
+        return fit_mixture_restarts(mixture, table)
+    best = int(np.argmax(fit['lower_bound']))                   # (the first largest, as `fit_predict` keeps it)
+    mixture.weights_, mixture.means_ = fit['weights'][best].copy(), fit['means'][best].copy()
+    mixture.covariances_, mixture.precisions_cholesky_ = fit['covariances'][best].copy(), fit['precisions_cholesky'][best].copy()
+    mixture.precisions_ = np.empty_like(mixture.precisions_cholesky_)
+    for k, prec_chol in enumerate(mixture.precisions_cholesky_):            # (`_set_parameters`)
+        mixture.precisions_[k] = np.dot(prec_chol, prec_chol.T)
+    mixture.converged_, mixture.n_iter_ = bool(fit['converged'][best]), int(fit['n_iter'][best])
+    mixture.lower_bound_, mixture.n_features_in_ = float(fit['lower_bound'][best]), table.shape[1]
+    if not mixture.converged_ and mixture.max_iter > 0:
+        warnings.warn('Best performing initialization did not converge. Try different init parameters, or increase max_iter, '
+                      'tol, or check for degenerate data.', ConvergenceWarning)
+    return mixture
+
+
+def _fit_place(fit_on):
+    """'host' or 'device' from the ``fit_on`` keyword; None: the environment variable IMSEGM_FIT_ON, unset: 'host'"""
+    import os
+    if fit_on is None:
+        fit_on = os.environ.get('IMSEGM_FIT_ON') or 'host'
+    if fit_on not in ('host', 'device'):
+        raise ValueError("fit_on is 'host' or 'device', not %r" % (fit_on, ))
+    return fit_on
+
+
+def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, use_scaler=True, max_iter=99, fit_on=None,
+                      _ctx=None):
     """ the class model of the unsupervised pipelines, fitted on the superpixel features with scikit-learn on the host:
     ``Pipeline([StandardScaler,] [PCA,] mixture(full covariance, int(sqrt(max_iter)) restarts))`` -- what
     ``graph_cuts.py:73-163`` builds.  ``estim_model='GMM'`` is the model the hot path uses and the device evaluates; the
     other names of the reference ('GMM_kmeans', 'GMM_Otsu', 'kmeans', 'kmeans_quantiles', 'BGM', 'Otsu') change the
     mixture's parameters as :func:`_class_model_plan` lists them.
+
+    ``fit_on``: ``'host'`` (the default: scikit-learn, bit for bit ``GaussianMixture.fit``) or ``'device'``
+    (:func:`fit_mixture_device`: the same model from other seeds and with sums in another order -- last digits and the winning
+    restart differ); ``None`` reads the environment variable ``IMSEGM_FIT_ON``.
     """
     from sklearn import decomposition, mixture, pipeline, preprocessing
+    fit_on = _fit_place(fit_on)
     kind, overrides, labelling = _class_model_plan(estim_model, nb_classes)
     params = dict(n_components=nb_classes, covariance_type='full', n_init=max(1, int(np.sqrt(max_iter))), max_iter=max_iter)
     params.update(overrides)
@@ -441,7 +549,10 @@ def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, us
         table = table.astype(np.float64)
     for _, step in model.steps[:-1]:        # what Pipeline.fit does with the steps in front of the last one
         table = step.fit_transform(table)
-    fit_mixture_restarts(model.steps[-1][1], table)
+    if fit_on == 'device':
+        fit_mixture_device(model.steps[-1][1], table, ctx=_ctx)
+    else:
+        fit_mixture_restarts(model.steps[-1][1], table)
     return model
 
 

@@ -425,7 +425,7 @@ def train_classif_color2d_slic_features(list_images, list_annots, dict_features,
 
 def pipe_color2d_slic_features_model_graphcut(image, nb_classes, dict_features, sp_size=30, sp_regul=0.2, pca_coef=None,
                                               use_scaler=True, estim_model='GMM', gc_regul=1., gc_edge_type='model',
-                                              debug_visual=None):
+                                              debug_visual=None, fit_on=None):
     """ complete unsupervised pipeline: superpixels, features, mixture model, GraphCut
 
     :param ndarray image: input RGB image
@@ -439,13 +439,14 @@ def pipe_color2d_slic_features_model_graphcut(image, nb_classes, dict_features, 
     :param float gc_regul: GraphCut regularisation
     :param str gc_edge_type: GraphCut edge type
     :param dict debug_visual: filled with intermediate results if given
+    :param str fit_on: where the mixture is fitted, see :func:`graph_cuts.estim_class_model`
     :return tuple(ndarray,ndarray): segmentation H x W, soft segmentation H x W x nb_classes
     """
     logging.info('PIPELINE Superpixels-Features-GMM-GraphCut')
     res = _ResidentImage(image, dict_features, sp_size, sp_regul)
     try:
         res.fill_debug(debug_visual)
-        model = estim_class_model(res.features, nb_classes, estim_model, pca_coef, use_scaler)
+        model = estim_class_model(res.features, nb_classes, estim_model, pca_coef, use_scaler, fit_on=fit_on)
         # the fitted mixture is evaluated on the device (resident features) when it is the scaler + GMM pipeline,
         # by scikit-learn otherwise
         segm, segm_soft = res.segment(None, gc_regul, gc_edge_type, debug_visual, model=model)
@@ -455,7 +456,7 @@ def pipe_color2d_slic_features_model_graphcut(image, nb_classes, dict_features, 
 
 
 def estim_model_classes_group(list_images, nb_classes, dict_features, sp_size=30, sp_regul=0.2, use_scaler=True, pca_coef=None,
-                              model_type='GMM', nb_workers=NB_WORKERS, group=None):
+                              model_type='GMM', nb_workers=NB_WORKERS, group=None, fit_on=None):
     """ estimate one class model from the superpixel features of a sequence of images (reference ``pipelines.py:113-157``)
 
     With a multi-rank ``group`` (:class:`pyimsegm_amd.distributed.Group`) every rank extracts the features of its images
@@ -468,7 +469,7 @@ def estim_model_classes_group(list_images, nb_classes, dict_features, sp_size=30
         return compute_color2d_superpixels_features(image, dict_features, sp_size=sp_size, sp_regul=sp_regul)[1]
 
     def _fit(features):
-        return estim_class_model(features, nb_classes, model_type, pca_coef, use_scaler)
+        return estim_class_model(features, nb_classes, model_type, pca_coef, use_scaler, fit_on=fit_on)
 
     if group is not None and group.world > 1:
         from pyimsegm_amd.distributed import estim_model_classes_group_sharded
@@ -585,7 +586,7 @@ def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeli
 
 
 def pipe_gray3d_slic_features_model_graphcut(image, nb_classes, dict_features, spacing=(12, 1, 1), sp_size=15, sp_regul=0.2,
-                                             gc_regul=0.1):
+                                             gc_regul=0.1, fit_on=None):
     """ complete pipeline on a gray volume: supervoxels, features, mixture model, GraphCut
     (reference ``pipelines.py:382-431``)
 
@@ -600,13 +601,14 @@ def pipe_gray3d_slic_features_model_graphcut(image, nb_classes, dict_features, s
     :param int sp_size: initial size of a supervoxel (edge length)
     :param float sp_regul: regularisation in (0, 1): 0 elastic, 1 nearly cubic segments
     :param float gc_regul: GraphCut regularisation
+    :param str fit_on: where the mixture is fitted, see :func:`graph_cuts.estim_class_model`
     :return ndarray: int32 class per voxel, D x H x W
     """
     logging.info('PIPELINE Superpixels-Features-GraphCut')
     image = np.asarray(image)
     sess = _open_volume(image, reuse=True)
     try:
-        segm = _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul)
+        segm = _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on)
     except Exception:
         sess.close()
         raise
@@ -651,7 +653,7 @@ def _result_array(shape, dtype=np.int32):
     return _touched_result(shape, dtype)
 
 
-def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul):
+def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on=None):
     segm_buf, segm_ready = _result_array(sess.shape)
     _run_slic3d(sess, sp_size, sp_regul, spacing)
     logging.info('extract segments/superpixels features.')
@@ -680,7 +682,7 @@ def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size,
         fused = False
         logging.info('volume graph by neighbour tables (%s)', ex)
 
-    model = estim_class_model(features, nb_classes)
+    model = estim_class_model(features, nb_classes, fit_on=fit_on, _ctx=sess.ctx)       # (a device fit: same stream, behind the graph)
     proba = predict_proba(model, features)          # (scikit-learn's arithmetic without its per-call validation: same bits)
     logging.debug('list of probabilities: %r', proba.shape)
 
