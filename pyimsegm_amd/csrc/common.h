@@ -408,17 +408,9 @@ template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v)
 {
     const long long b = __double_as_longlong(v);
-#ifndef IMSEGM_DPP_PRESET
-#define IMSEGM_DPP_PRESET 0
-#endif
-#if IMSEGM_DPP_PRESET
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
-#else
     // (mirror / quad permutations read a valid lane everywhere: no preset of the destination, one instruction per half)
     const int lo = __builtin_amdgcn_mov_dpp((int)b, CTRL, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xf, 0xf, false);
-#endif
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 __device__ __forceinline__ double row16_reduce8_f64(const double (&v)[8], int lane)

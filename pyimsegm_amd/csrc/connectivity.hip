@@ -172,10 +172,7 @@ k_ccl_init_rows(const int32_t *__restrict__ labels, int32_t *__restrict__ parent
 // of a lane over its rows -- a bit each in `todo`: 3 r + 0 left (a run that crosses into the segment), + 1 up, + 2 behind -- are
 // done two at a time (union2_min_root), every lane that still has some side by side.  (One row per wave, one union per lane and
 // round: 10.4 ms at 2^30 voxels, the latency of one chain of dependent loads after the other.)
-#ifndef CCL_MERGE_ROWS
-#define CCL_MERGE_ROWS 4
-#endif
-constexpr int CR_ROWS = CCL_MERGE_ROWS;          // (<= 10: three bits of `todo` per row)
+constexpr int CR_ROWS = 4;          // (<= 10: three bits of `todo` per row)
 
 __global__ void __launch_bounds__(256)
 k_ccl_merge_rows(const int32_t *__restrict__ labels, int32_t *parent, int D, int H, int W)

@@ -95,9 +95,7 @@ __device__ __forceinline__ long long gc_energy(const GcDevice &g, const int32_t 
     return block_sum_i64(e, scratch);
 }
 
-#ifndef GC_ARCS
-#define GC_ARCS 8
-#endif
+constexpr int GC_ARCS = 8;          // arcs of a node handled together: kept in registers / loaded in one round
 
 // OR over the workgroup with ONE barrier per call: three LDS words used in turn -- call r sets and reads word r % 3, and thread 0
 // clears word (r + 2) % 3 behind the barrier: its last readers (call r - 1) have all arrived at this barrier, its next writers

@@ -757,12 +757,8 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // the winner is the nearest grid node per axis, ties to the lower index (= lowest centroid index, what
 // the strict '<' of _slic.pyx keeps).  The launcher only selects this variant when every pixel lies inside
 // the search window of its nearest node.
-#ifndef SLIC_DOT_MIN_BLOCKS
-#define SLIC_DOT_MIN_BLOCKS 5
-#endif
-#ifndef SLIC_DOT_MIN_BLOCKS_TILE
-#define SLIC_DOT_MIN_BLOCKS_TILE 4
-#endif
+constexpr int SLIC_DOT_MIN_BLOCKS = 5, SLIC_DOT_MIN_BLOCKS_TILE = 4;      // waves per SIMD the register allocation aims at: U == 1, U == 2
+constexpr int SLIC_PH1 = 4, SLIC_PH2 = 8;      // PH1, PH2 above: candidates after which a wave forms its break bound
 // PROF: the instantiation with the in-kernel phase timers (IMSEGM_PHASE_PROF); the production kernels carry none of it
 // (the marks end basic blocks and wait for all memory operations, which also keeps the compiler from overlapping phases)
 template <bool ACCUM, bool FIRST, int U, bool PROF>
@@ -802,11 +798,7 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
     const bool xin = x < s.W;
     const double sw = s.spatial_weight;
 
-#ifndef SLIC_SADDR
-#define SLIC_SADDR 1
-#endif
     double pLu[U][ROWS], pAu[U][ROWS], pBu[U][ROWS];
-#if SLIC_SADDR
     // one scalar base per (row, plane) and ONE 32-bit byte offset per lane (global_load ... v_off, s[base]): the row index of a
     // unit is wave-uniform, so the 64-bit address arithmetic is scalar -- three vector instructions instead of fifty-five per wave.
     // A lane right of the image reads column 0 of its row, a row below the image reads row 0 (in bounds; never used).
@@ -821,19 +813,6 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
             pAu[u][r] = *reinterpret_cast<const double *>(row + plane * sizeof(double) + xoff8);
             pBu[u][r] = *reinterpret_cast<const double *>(row + 2 * plane * sizeof(double) + xoff8);
         }
-#else
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            const int y = tile_row * TILE_Y + relbase + u * ROWS + r;
-            const bool ok = xin && y < s.H;
-            const size_t p = (size_t)(ok ? y : 0) * s.W + (ok ? x : 0);
-            pLu[u][r] = lab[p];
-            pAu[u][r] = lab[plane + p];
-            pBu[u][r] = lab[2 * plane + p];
-        }
-#endif
     const int my_k = tile_k[(size_t)tile * MAXC + lane];
     const unsigned my_rows = s.tile_rows[(size_t)tile * MAXC + lane];      // rows of the tile inside the slot's window (bit mask)
     // candidate table in registers: lane c holds the record of candidate c; the loop fetches the fields
@@ -895,12 +874,6 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
                 }
         }
     } else if (nc > 0) {
-#ifndef SLIC_PH1
-#define SLIC_PH1 4
-#endif
-#ifndef SLIC_PH2
-#define SLIC_PH2 8
-#endif
         // Round 5: the same arithmetic per candidate and the same margins, with the instruction count of everything AROUND the
         // five multiply-adds cut down -- the kernel is bound by instruction issue (823 vector + 443 scalar instructions per wave
         // before, counted in the ISA and by SQ_INSTS_*):
@@ -915,7 +888,6 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
         //    and compared field by field (30 scalar instructions per candidate);
         //  * the first PH1 candidates, which every wave evaluates, come through the scalar cache (s_load_dwordx8) instead of seven
         //    v_readlane each.
-        constexpr int PH1 = SLIC_PH1, PH2 = SLIC_PH2;
         const float INF = __builtin_inff();
         const float sw32 = (float)sw;
         const double ref0 = ti->ref[0], ref1 = ti->ref[1], ref2 = ti->ref[2];
@@ -946,9 +918,6 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
         int c_end = nc;
 #define RL_F(v) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), c))
 #define F2S(v) ((f2){ (v), (v) })
-#ifndef SLIC_REC_SGPR
-#define SLIC_REC_SGPR 1
-#endif
         // one candidate against the four rows of this unit; `rows4` = which of them lie inside its window (from k_slic_bin's row mask)
         auto evaluate = [&](const int c, const float q0, const float qx, const float qy, const float qL, const float qa, const float qb,
                             const unsigned meta, const unsigned rows4) __attribute__((always_inline)) {
@@ -984,25 +953,22 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
 #undef SLIC_SELECT
             }
         };
-        int c_first = 0;
-#if SLIC_REC_SGPR
         // the first PH1 candidates are evaluated by every wave (no bound exists before them): their records come through the
         // scalar cache (uniform address: s_load_dwordx8) instead of seven v_readlane each -- the vector unit is the bottleneck
         {
             const unsigned *__restrict__ rows_tab = s.tile_rows + (size_t)tile * MAXC;
 #pragma unroll
-            for (int c = 0; c < PH1; ++c) {
+            for (int c = 0; c < SLIC_PH1; ++c) {
                 if (c >= nc) break;
                 const unsigned rows4 = (rows_tab[c] >> rel0) & 15u;
                 if (rows4 == 0) continue;
                 const Rec32 r = rec[c];
                 evaluate(c, r.q0, r.qx, r.qy, r.qL, r.qa, r.qb, r.meta, rows4);
             }
-            c_first = min(nc, PH1);
         }
-#endif
+        const int c_first = min(nc, SLIC_PH1);
         for (int c = c_first; c < nc; ++c) {
-            if (c == PH1 || c == PH2) {
+            if (c == SLIC_PH1 || c == SLIC_PH2) {
                 // W >= max over the pixels of this wave of (best D + margin), D = d + P with the pixel's own term
                 // P = sw * (Y^2 + X^2) + |f|^2; the factors 1.002 / 0.002 * (xb + 1) cover the fp32 evaluation error and the
                 // near-tie margin many times over, so neither the order of the additions nor a pixel outside the image that
@@ -1119,11 +1085,7 @@ k_slic_assign_dot(SlicState s, const double *__restrict__ lab, int32_t *__restri
     for (int r = 0; r < ROWS; ++r) {
         const int y = wy0 + r;
         if (!(xin && y < s.H)) continue;
-#if SLIC_SADDR
         int32_t &label_here = *reinterpret_cast<int32_t *>(reinterpret_cast<char *>(labels + (size_t)y * s.W) + (unsigned)x * 4u);
-#else
-        int32_t &label_here = labels[y * s.W + x];
-#endif
         if (best_s[r] >= 0) {
             label_here = win_k[r];
             pending |= 1u << r;

@@ -321,15 +321,9 @@ k_blur_axis(const double *__restrict__ src, double *__restrict__ dst, int H, int
 // Lab (+ z tap) of the tile and its blur halo goes to LDS (the halo is converted redundantly, x1.7), the y
 // pass runs LDS -> LDS one channel at a time, the x pass LDS -> HBM with the final 1/compactness.
 // ---------------------------------------------------------------------------------------------
-// (tile geometry overridable at compile time for A/B builds -- tools/variants_k.sh; e.g. -DSLIC_PF_TX=32 -DSLIC_PF_TY=32 converts
-// 40 x 40 pixels per 32 x 32 outputs, x1.56 instead of x1.69, in 48 KB of LDS: 125.8 against 129.0 us)
-#ifndef SLIC_PF_TX
-#define SLIC_PF_TX 64
-#endif
-#ifndef SLIC_PF_TY
-#define SLIC_PF_TY 16
-#endif
-constexpr int PF_TX = SLIC_PF_TX, PF_TY = SLIC_PF_TY, PF_MAXR = 8, PF_THREADS = 512;
+// (tile geometry, measured: a 32 x 32 tile converts 40 x 40 pixels per 32 x 32 outputs, x1.56 instead of x1.69, in 48 KB of LDS:
+// 125.8 against 129.0 us)
+constexpr int PF_TX = 64, PF_TY = 16, PF_MAXR = 8, PF_THREADS = 512;
 static_assert(PF_THREADS % PF_TX == 0 && PF_TY % (PF_THREADS / PF_TX) == 0, "x pass: whole rows per pass");
 
 template <typename T>

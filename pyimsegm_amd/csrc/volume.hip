@@ -681,48 +681,30 @@ __device__ __forceinline__ int wave_min_key(int key)
     return VOL_KEY_INF - __builtin_amdgcn_readlane(x, 63);
 }
 
-// VZ slices of one workgroup (see k_vol_assign_f32): a lane holds VZ x VROWS voxels -- one column of 4 rows in VZ consecutive
-// slices.  `cov[c]`: bit zi set when slice z0 + zi lies inside candidate c's search window.
-// Measured (round 6, 64 x 4096 x 4096, one box each): VZ = 1 11.4 ms per accumulating sweep; VZ = 2 -- the scan of the brick's list,
-// its barriers and the flush of the boxes serving twice the voxels, a candidate selected once for eight rows of a lane -- 12.1 ms:
-// 102 registers per lane leave four waves per SIMD where 56 leave eight, and the kernel lives on the waves that compute while
-// others wait.  The code takes either; the label maps are the same (tests with both).
-#ifndef VOL_ASSIGN_SLICES
-#define VOL_ASSIGN_SLICES 1
-#endif
-constexpr int VZ = VOL_ASSIGN_SLICES;
-
-// The voxels of a wave inside the workgroup's 64 x 16 cross-section.  VOL_ASSIGN_TILE 16 (round 6): a 16 x 16 TILE -- lane = (lane & 15)
-// in x, rows 4 (lane >> 4) .. + 3 in y; 64: a 64 x 4 strip (rounds 3 - 6) -- lane in x, four rows.  The walk evaluates a candidate for
-// all 256 voxels of the wave; at config 5 a supervoxel is ~35 x 35 voxels of a slice, a strip met the windows of ~9 centroids whose
-// bound lay below its worst distance, a tile meets ~half of that.  Same candidates per VOXEL, same arithmetic, same comparison: the
-// label maps do not move (tests with both).
-#ifndef VOL_ASSIGN_TILE
-#define VOL_ASSIGN_TILE 16
-#endif
-// (32: a 32 x 8 tile -- lane & 31 in x, rows 4 (lane >> 5) .. + 3 -- whose rows are whole 128-byte lines of the label map: the 16 x 16
-// tile writes half lines, 2.2 bytes to memory for every byte of the map by the counters.)
-constexpr bool VT16 = VOL_ASSIGN_TILE != 64;              // (a tile, not a strip)
-static_assert(VOL_ASSIGN_TILE == 16 || VOL_ASSIGN_TILE == 32 || VOL_ASSIGN_TILE == 64, "tile of a wave: 16 x 16, 32 x 8 or 64 x 4");
-constexpr int VT_W = VOL_ASSIGN_TILE, VT_H = (64 / VOL_ASSIGN_TILE) * VROWS;
-constexpr int VT_SHIFT = VOL_ASSIGN_TILE == 16 ? 4 : VOL_ASSIGN_TILE == 32 ? 5 : 6;
-// the neighbour to the left inside the wave's row of voxels (the first lane of a tile's row keeps `first`)
-__device__ __forceinline__ int tile_prev(int v, int first)
-{
-    if (VOL_ASSIGN_TILE == 16) return __builtin_amdgcn_update_dpp(first, v, 0x111, 0xf, 0xf, false);      // row_shr:1
-    const int p = lane_prev(v, first);
-    return (VOL_ASSIGN_TILE == 32 && (threadIdx.x & 31) == 0) ? first : p;
-}
+// A workgroup of k_vol_assign_f32 takes the 64 x 16 cross-section of a brick in ONE slice; a lane holds one column of VROWS rows.
+// Measured (64 x 4096 x 4096, one box each): 11.4 ms per accumulating sweep; with two consecutive slices per workgroup -- the scan
+// of the brick's list, its barriers and the flush of the boxes serving twice the voxels, a candidate selected once for eight rows
+// of a lane -- 12.1 ms: 102 registers per lane leave four waves per SIMD where 56 leave eight, and the kernel lives on the waves
+// that compute while others wait.
+//
+// The voxels of a wave inside the cross-section: a 16 x 16 TILE -- lane & 15 in x, rows 4 (lane >> 4) .. + 3 in y.  The walk evaluates
+// a candidate for all 256 voxels of the wave; at config 5 a supervoxel is ~35 x 35 voxels of a slice: a 64 x 4 strip (lane in x, four
+// rows) met the windows of ~9 centroids whose bound lay below its worst distance, a tile meets ~half of that.  A 32 x 8 tile,
+// whose rows are whole 128-byte lines of the label map where the 16 x 16 tile's are half lines, measured 9.93 against 9.38 ms per
+// sweep.  Same candidates per VOXEL, same arithmetic, same comparison whatever the shape: the label maps are the same.
+constexpr int VT_W = 16, VT_H = 16;
+// the neighbour to the left inside the tile's row of voxels (the first lane of a row keeps `first`)
+__device__ __forceinline__ int tile_prev(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x111, 0xf, 0xf, false); }      // row_shr:1
 
 template <int NS>
-__device__ __forceinline__ void vol_walk_f32(const VolRec *rec, const int *list, const unsigned char *cov, int count, int lane, int y0,
-                                             int y1w, int x0w, int x1w, int yl, int x, bool xin, int H, int nzv, float fz0, float fx, float sz,
-                                             float sy, float sx, float sw, const float (&pv)[VZ][VROWS], float (&best_d)[VZ][VROWS],
-                                             int (&best_k)[VZ][VROWS], float &wave_worst)
+__device__ __forceinline__ void vol_walk_f32(const VolRec *rec, const int *list, int count, int lane, int y0, int y1w, int x0w, int x1w,
+                                             int yl, int x, bool xin, int H, bool zin, float fz0, float fx, float sz, float sy, float sx,
+                                             float sw, const float (&pv)[VROWS], float (&best_d)[VROWS], int (&best_k)[VROWS],
+                                             float &wave_worst)
 {
     static_assert(NS >= 1 && NS <= 8, "three bits of a key hold the slot");
-    // bounds over this wave's voxels [y0, y1w) x [x0w, x1w) (per slice); a window that misses them is out.  The bound of a candidate
-    // is its smallest bound over the slices its window covers: below every distance it can give a voxel of this wave.
+    // bounds over this wave's voxels [y0, y1w) x [x0w, x1w); a window that misses them is out.  The bound of a candidate lies below
+    // every distance it can give a voxel of this wave (the scan has kept the windows that cover the slice).
     // (yl: the first of the lane's own VROWS rows)
     int key[NS];
 #pragma unroll
@@ -731,20 +713,14 @@ __device__ __forceinline__ void vol_walk_f32(const VolRec *rec, const int *list,
         key[j] = VOL_KEY_INF;
         if (c < count) {
             const VolRec rc = rec[c];
-            const int cv = VZ > 1 ? cov[c] : 1;            // (one slice: the scan has kept the windows that cover it)
             if (rc.wy0 < y1w && rc.wy1 > y0 && rc.wx0 < x1w && rc.wx1 > x0w) {
                 const float yn = fminf(fmaxf(rc.cy, (float)y0), (float)(y1w - 1));
                 const float xn = fminf(fmaxf(rc.cx, (float)x0w), (float)(x1w - 1));
                 const float tyl = sy * (rc.cy - yn), txl = sx * (rc.cx - xn);
                 const float dy2 = tyl * tyl, dx2 = txl * txl;
-                float lb = INFINITY;
-#pragma unroll
-                for (int zi = 0; zi < VZ; ++zi) {
-                    const float tz = sz * (rc.cz - (fz0 + (float)zi));
-                    const float dz = tz * tz;
-                    const float one = ((dz + dy2) + dx2) * sw;          // >= 0, or +inf / NaN (then: not a candidate)
-                    lb = ((cv >> zi) & 1) ? fminf(lb, one) : lb;
-                }
+                const float tz = sz * (rc.cz - fz0);
+                const float dz = tz * tz;
+                const float lb = ((dz + dy2) + dx2) * sw;              // >= 0, or +inf / NaN (then: not a candidate)
                 const int bits = __float_as_int(lb);
                 key[j] = (bits >= 0 && bits < VOL_KEY_INF) ? ((bits & ~7) | j) : VOL_KEY_INF;
             }
@@ -767,7 +743,6 @@ __device__ __forceinline__ void vol_walk_f32(const VolRec *rec, const int *list,
         const int c = src + 64 * jsel;
         const int ck = list[c];
         const VolRec rc = rec[c];
-        const int cv = VZ > 1 ? cov[c] : 1;
         VOL_PH_COUNT(11, 1);
         const bool inx = x >= rc.wx0 && x < rc.wx1;
         const float tx = sx * (rc.cx - fx);
@@ -778,35 +753,28 @@ __device__ __forceinline__ void vol_walk_f32(const VolRec *rec, const int *list,
             const float ty = sy * (rc.cy - (float)(yl + r));
             dy[r] = ty * ty;
         }
+        const float tz = sz * (rc.cz - fz0);
+        const float dz = tz * tz;
 #pragma unroll
-        for (int zi = 0; zi < VZ; ++zi) {
-            if (!((cv >> zi) & 1)) continue;                       // (wave uniform: the slice is outside the window)
-            const float tz = sz * (rc.cz - (fz0 + (float)zi));
-            const float dz = tz * tz;
-#pragma unroll
-            for (int r = 0; r < VROWS; ++r) {
-                const int y = yl + r;
-                const bool iny = y >= rc.wy0 && y < rc.wy1;
-                if (!VT16 && !iny) continue;                         // (a strip's row: wave uniform)
-                float d = ((dz + dy[r]) + dx2) * sw;
-                const float t = pv[zi][r] - rc.cv;
-                d = d + t * t;
-                const bool take = inx && iny && (best_d[zi][r] > d || (best_d[zi][r] == d && ck < best_k[zi][r]));
-                // (the compiler guards the arithmetic of a row with the window test -- branches; written with & and | instead, as
-                // compares into masks and two selects, every row is computed for every candidate and the kernel spills: 14.7
-                // against 8.7 ms per sweep at config 5)
-                best_d[zi][r] = take ? d : best_d[zi][r];
-                best_k[zi][r] = take ? ck : best_k[zi][r];
-            }
+        for (int r = 0; r < VROWS; ++r) {
+            const int y = yl + r;
+            const bool iny = y >= rc.wy0 && y < rc.wy1;
+            float d = ((dz + dy[r]) + dx2) * sw;
+            const float t = pv[r] - rc.cv;
+            d = d + t * t;
+            const bool take = inx && iny && (best_d[r] > d || (best_d[r] == d && ck < best_k[r]));
+            // (the compiler guards the arithmetic of a row with the window test -- branches; written with & and | instead, as
+            // compares into masks and two selects, every row is computed for every candidate and the kernel spills: 14.7
+            // against 8.7 ms per sweep at config 5)
+            best_d[r] = take ? d : best_d[r];
+            best_k[r] = take ? ck : best_k[r];
         }
         if (++since_refresh == 2) {
             since_refresh = 0;
             float m2 = 0.f;
 #pragma unroll
-            for (int zi = 0; zi < VZ; ++zi)
-#pragma unroll
-                for (int r = 0; r < VROWS; ++r)
-                    if (xin && (yl + r) < H && zi < nzv) m2 = fmaxf(m2, best_d[zi][r]);
+            for (int r = 0; r < VROWS; ++r)
+                if (xin && (yl + r) < H && zin) m2 = fmaxf(m2, best_d[r]);
             wave_worst = wave_max_nonneg_f32(m2);           // (distances: never negative; +inf while a voxel has no candidate)
         }
     }
@@ -867,40 +835,34 @@ __global__ void __launch_bounds__(256) k_vol_scatter_f32(VolState s)
 // against 2.68 ms per sweep of a quarter volume, alternating on one box --, spills at eight (64 registers: 3.47 ms).  On 16 x 16
 // tiles with the labels staged through LDS (more per-lane state: own rows, tile geometry) seven waves spill into scratch inside the
 // walk: 6 -> 7.48, 7 -> 8.72, 5 -> 8.37, 8 -> 11.97 ms per sweep at config 5, one box each pair.
-#ifndef VOL_ASSIGN_WAVES
-#define VOL_ASSIGN_WAVES 6
-#endif
-#define VOL_ASSIGN_ATTR __attribute__((amdgpu_waves_per_eu(VOL_ASSIGN_WAVES, VOL_ASSIGN_WAVES)))
+constexpr int VOL_ASSIGN_WAVES = 6;
 template <bool TRACK>
-__global__ void __launch_bounds__(256) VOL_ASSIGN_ATTR
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VOL_ASSIGN_WAVES, VOL_ASSIGN_WAVES)))
 k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict__ labels)
 {
-    // A workgroup = the 64 x 16 cross-section of a brick in VZ consecutive slices (VZ = 1; 2 was measured, see VZ above);
-    // a wave = 64 columns x 4 rows x VZ slices.
+    // A workgroup = the 64 x 16 cross-section of a brick in one slice; a wave = a 16 x 16 tile of it (see VT_W above).
     __shared__ int list[VLIST32];
     __shared__ __attribute__((aligned(16))) VolRec rec[VLIST32];      // (filled with 16-byte stores)
-    // (one slice: no coverage bytes and no z columns in the table of the boxes -- 19.7 KB per workgroup, eight of them per CU; with
-    // them it is 20.8 KB and seven)
-    __shared__ unsigned char cov[VZ > 1 ? VLIST32 : 1];
+    // (19.7 KB per workgroup, eight of them per CU; with a byte per record for the slices a window covers and z columns in the table
+    // of the boxes -- two slices per workgroup -- it was 20.8 KB and seven)
     __shared__ int wave_base[4];
-    constexpr int HB = VZ > 1 ? 6 : 4, HB_Y = VZ > 1 ? 2 : 0;                        // label -> [zmin, zmax,] ymin, ymax, xmin, xmax
-    // (tiles of one slice: the box of a label inside the cross-section as the SET of its columns -- 64 bits, hb_box[][0..1] -- and of
-    // its rows -- 16 bits, hb_box[][2] --, joined with OR)
-    constexpr bool HB_SETS = VT16 && VZ == 1;
+    // the box of a label inside the cross-section as the SET of its columns -- 64 bits, hb_box[][0..1] -- and of its rows -- 16 bits,
+    // hb_box[][2] --, joined with OR (hb_box[][3]: padding, the 64-bit set stays 8-byte aligned)
     __shared__ int hb_key[TRACK ? VT_SLOTS : 1];
-    __shared__ __attribute__((aligned(8))) int hb_box[TRACK ? VT_SLOTS : 1][HB];
+    __shared__ __attribute__((aligned(8))) int hb_box[TRACK ? VT_SLOTS : 1][4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     VOL_PH_BEGIN
     const int rows_per_block = 4 * VROWS;
     const int yb = cdiv(s.H, rows_per_block);
-    const int z0 = (blockIdx.y / yb) * VZ;
-    const int nzv = min(VZ, s.D - z0);                        // slices of this workgroup inside the volume
+    const int z0 = blockIdx.y / yb;
+    const int nzv = min(1, s.D - z0);                         // 1: the slice of this workgroup lies inside the volume (else <= 0)
+    const bool zin = nzv > 0;
     const int Y0 = (blockIdx.y % yb) * rows_per_block, Y1 = min(Y0 + rows_per_block, s.H);
     // the wave's voxels: [y0, y1w) x [xt0, xt1); the lane's: column x, rows yl .. yl + VROWS - 1
-    constexpr int TILES_X = 64 / VT_W;                        // tiles of a workgroup side by side (4, 2 or 1), 4 / TILES_X below each other
+    constexpr int TILES_X = 64 / VT_W;                        // the four tiles of a workgroup lie side by side
     const int y0 = Y0 + (wave / TILES_X) * VT_H;
-    const int yl = y0 + (lane >> VT_SHIFT) * VROWS;
+    const int yl = y0 + (lane / VT_W) * VROWS;
     const int x0w = blockIdx.x * 64, x1w = min(x0w + 64, s.W);                    // the cross-section (the scan of the brick's list)
     const int xt0 = x0w + (wave % TILES_X) * VT_W, xt1 = min(xt0 + VT_W, s.W);
     const int x = xt0 + (lane & (VT_W - 1));
@@ -910,25 +872,22 @@ k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict_
     if (TRACK && tid < VT_SLOTS) {                            // (visible to all after the first barrier of the scan below)
         hb_key[tid] = -1;
 #pragma unroll
-        for (int j = 0; j < HB; ++j) hb_box[tid][j] = HB_SETS ? 0 : (j & 1) ? -1 : 0x7fffffff;
+        for (int j = 0; j < 4; ++j) hb_box[tid][j] = 0;
     }
-    float pv[VZ][VROWS], best_d[VZ][VROWS];
-    int best_k[VZ][VROWS];
+    float pv[VROWS], best_d[VROWS];
+    int best_k[VROWS];
 #pragma unroll
-    for (int zi = 0; zi < VZ; ++zi)
-#pragma unroll
-        for (int r = 0; r < VROWS; ++r) {
-            const bool ok = alive && xin && (yl + r) < s.H && zi < nzv;
-            pv[zi][r] = vol[ok ? ((size_t)(z0 + zi) * s.H + yl + r) * s.W + x : 0];
-            best_d[zi][r] = INFINITY;
-            best_k[zi][r] = -1;
-        }
+    for (int r = 0; r < VROWS; ++r) {
+        const bool ok = alive && xin && (yl + r) < s.H && zin;
+        pv[r] = vol[ok ? ((size_t)z0 * s.H + yl + r) * s.W + x : 0];
+        best_d[r] = INFINITY;
+        best_k[r] = -1;
+    }
     const float fz0 = (float)z0, fx = (float)x;
     const float sz = (float)s.sz, sy = (float)s.sy, sx = (float)s.sx;
     const float sw = (float)s.spatial_weight;              // = (float)(1 / ((double)step * (double)step))
     int count = 0;                                         // (uniform over the workgroup)
     float wave_worst = INFINITY;
-    static_assert(VOL_BZ % VZ == 0, "the slices of a workgroup lie in one brick");
     const int brick = ((z0 / VOL_BZ) * s.nby + (Y0 / VOL_BY)) * s.nbx + blockIdx.x;
     const int bcount = s.brick_count[brick];
     const bool whole = bcount > s.brick_cap;                   // list overflow: scan every centroid
@@ -973,10 +932,6 @@ k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict_
             int4 *dst = reinterpret_cast<int4 *>(&rec[pos]);
             dst[0] = e0;
             dst[1] = e1;
-            int inside = 0;
-#pragma unroll
-            for (int zi = 0; zi < VZ; ++zi) inside |= (zi < nzv && z0 + zi >= e2.x && z0 + zi < e2.y) ? (1 << zi) : 0;
-            if (VZ > 1) cov[pos] = (unsigned char)inside;
         }
         count += added;
         __syncthreads();                                     // (list and records are complete; wave_base may be rewritten)
@@ -985,7 +940,7 @@ k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict_
         VOL_PH_COUNT(10, count);
         VOL_PH(2);
         if (alive) {
-#define VOL_WALK(NS) vol_walk_f32<NS>(rec, list, cov, count, lane, y0, y1w, xt0, xt1, yl, x, xin, s.H, nzv, fz0, fx, sz, sy, sx, sw, pv, best_d, best_k, wave_worst)
+#define VOL_WALK(NS) vol_walk_f32<NS>(rec, list, count, lane, y0, y1w, xt0, xt1, yl, x, xin, s.H, zin, fz0, fx, sz, sy, sx, sw, pv, best_d, best_k, wave_worst)
             switch ((count + 63) >> 6) {
             case 0: break;
             case 1: VOL_WALK(1); break;
@@ -1004,60 +959,46 @@ k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict_
         if (b + 1 < nblk) __syncthreads();                   // (everybody is done with this batch's list and records)
         VOL_PH(4);
     }
-    unsigned pending = 0;                                    // bit zi * VROWS + r: the voxel carries a label
-    // Tiles narrower than a line of the label map (16 voxels = 64 of its 128 bytes) hand their new labels to the LDS the records
-    // have left, and every wave stores four whole rows of the cross-section: written half line by half line the map cost 2.3 bytes
-    // to memory per byte (WRITE_SIZE, profiles/pmc_r06_cfg5_kernels.txt).
-#ifndef VOL_ASSIGN_DIRECT_STORES
-    constexpr bool STAGED = VOL_ASSIGN_TILE == 16 && VZ == 1;
-#else
-    constexpr bool STAGED = false;
-#endif
-    if (STAGED) {
-        int *stage = reinterpret_cast<int *>(rec);           // [16][64]
-        static_assert(sizeof(rec) >= 16 * 64 * sizeof(int), "the records' LDS holds a cross-section of labels");
-        __syncthreads();                                     // (everybody is done with the last batch's records)
+    unsigned pending = 0;                                    // bit r: the voxel of row r carries a label
+    // A tile's row is narrower than a line of the label map (16 voxels = 64 of its 128 bytes): the tiles hand their new labels to
+    // the LDS the records have left, and every wave stores four whole rows of the cross-section.  Written half line by half line,
+    // straight from the tiles, the map cost 2.3 bytes to memory per byte (WRITE_SIZE, profiles/pmc_r06_cfg5_kernels.txt).
+    int *stage = reinterpret_cast<int *>(rec);               // [16][64]
+    static_assert(sizeof(rec) >= 16 * 64 * sizeof(int), "the records' LDS holds a cross-section of labels");
+    __syncthreads();                                         // (everybody is done with the last batch's records)
 #pragma unroll
-        for (int r = 0; r < VROWS; ++r) stage[(yl - Y0 + r) * 64 + (x - x0w)] = best_k[0][r];
-        __syncthreads();
+    for (int r = 0; r < VROWS; ++r) stage[(yl - Y0 + r) * 64 + (x - x0w)] = best_k[r];
+    __syncthreads();
 #pragma unroll
-        for (int r = 0; r < VROWS; ++r) {
-            const int ys = Y0 + wave * VROWS + r, xs = x0w + lane;
-            const int k = stage[(wave * VROWS + r) * 64 + lane];
-            if (k >= 0 && xs < s.W && ys < s.H) labels[((size_t)z0 * s.H + ys) * s.W + xs] = k;
-        }
+    for (int r = 0; r < VROWS; ++r) {
+        const int ys = Y0 + wave * VROWS + r, xs = x0w + lane;
+        const int k = stage[(wave * VROWS + r) * 64 + lane];
+        if (k >= 0 && xs < s.W && ys < s.H) labels[((size_t)z0 * s.H + ys) * s.W + xs] = k;
     }
     if (alive) {
 #pragma unroll
-        for (int zi = 0; zi < VZ; ++zi)
-#pragma unroll
-            for (int r = 0; r < VROWS; ++r) {
-                if (!(xin && (yl + r) < s.H && zi < nzv)) continue;
-                const size_t p = ((size_t)(z0 + zi) * s.H + yl + r) * s.W + x;
-                if (best_k[zi][r] >= 0) {
-                    if (!STAGED) labels[p] = best_k[zi][r];
-                } else {
-                    best_k[zi][r] = labels[p];                    // uncovered voxel keeps its previous assignment
-                }
-                if (best_k[zi][r] >= 0) pending |= 1u << (zi * VROWS + r);
-            }
+        for (int r = 0; r < VROWS; ++r) {
+            if (!(xin && (yl + r) < s.H && zin)) continue;
+            if (best_k[r] < 0) best_k[r] = labels[((size_t)z0 * s.H + yl + r) * s.W + x];      // uncovered voxel keeps its previous assignment
+            if (best_k[r] >= 0) pending |= 1u << r;
+        }
     }
     VOL_PH(5);
     if (!TRACK) return;
     // bounding box of every segment's voxels (incl. the ones that kept an old label): the region the order-preserving update of
-    // that centroid has to walk.  By RUNS (round 5): in every row of the strip the first lane of a run of equal labels finds the
-    // end of its run in the vote of the run starts.  Round 6: it updates the box of its label in the workgroup's LDS table; the
-    // table goes to the global boxes once, below.  Minima and maxima: the boxes are the same whatever the order and however often
-    // a label is met.
-    // Tiles (one slice): by runs as the strips below, but a run joins the label's SETS of columns and rows with two ORs that return
-    // nothing, and a lane that has found the slot of a label keeps it for the rows below (a label change costs the search again).
-    // (Measured at config 5, one box: runs with minima / maxima as below 9.49 ms per sweep; label by label -- the first waiting lane
-    // names a label, four votes give its columns and rows, one lane joins them -- 11.05 ms: a serial chain per label and wave.)
-    if (HB_SETS && alive) {
+    // that centroid has to walk.  By RUNS: in every row of the tile the first lane of a run of equal labels finds the end of its run
+    // in the vote of the run starts and joins the label's SETS of columns and rows in the workgroup's LDS table with two ORs that
+    // return nothing; a lane that has found the slot of a label keeps it for the rows below (a label change costs the search
+    // again).  The table goes to the global boxes once, below.  Unions, minima and maxima: the boxes are the same whatever the order
+    // and however often a label is met.
+    // (Measured at config 5, one box: runs that update minima / maxima of y and x in the table 9.49 ms per sweep; label by label --
+    // the first waiting lane names a label, four votes give its columns and rows, one lane joins them -- 11.05 ms: a serial chain
+    // per label and wave.)
+    if (alive) {
         int slot_of = -2, slot = -1;
 #pragma unroll
         for (int r = 0; r < VROWS; ++r) {
-            const int k = (pending >> r) & 1u ? best_k[0][r] : -1;
+            const int k = (pending >> r) & 1u ? best_k[r] : -1;
             const int kp = tile_prev(k, -2);                        // (the first lane of a row of the tile: a start)
             const bool start = k >= 0 && kp != k;
             const unsigned long long starts = __ballot(start), valid = __ballot(k >= 0);
@@ -1091,64 +1032,17 @@ k_vol_assign_f32(VolState s, const float *__restrict__ vol, int32_t *__restrict_
             }
         }
     }
-    if (!HB_SETS && alive) {
-#pragma unroll
-        for (int zi = 0; zi < VZ; ++zi)
-#pragma unroll
-            for (int r = 0; r < VROWS; ++r) {
-                const int k = (pending >> (zi * VROWS + r)) & 1u ? best_k[zi][r] : -1;
-                const int kp = tile_prev(k, -2);                    // (the first lane of a row of the tile: a start)
-                const bool start = k >= 0 && kp != k;
-                const unsigned long long starts = __ballot(start), valid = __ballot(k >= 0);
-                if (start) {
-                    const unsigned long long stop = (starts | ~valid) & ~((2ULL << lane) - 1ULL);     // the lanes above this one
-                    const int end = stop ? __ffsll((long long)stop) - 1 : 64;
-                    const int z = z0 + zi, y = yl + r, xlo = x, xhi = x + (end - lane) - 1;
-                    int slot = (int)(((unsigned int)k * 2654435761u) >> 26);          // 6 bits
-                    bool placed = false;
-                    for (int probe = 0; probe < VT_SLOTS; ++probe) {
-                        const int old = atomicCAS(&hb_key[slot], -1, k);
-                        if (old == -1 || old == k) {
-                            placed = true;
-                            break;
-                        }
-                        slot = (slot + 1) & (VT_SLOTS - 1);
-                    }
-                    if (placed) {
-                        if (VZ > 1) {
-                            atomicMin(&hb_box[slot][0], z);
-                            atomicMax(&hb_box[slot][1], z);
-                        }
-                        atomicMin(&hb_box[slot][HB_Y], y);
-                        atomicMax(&hb_box[slot][HB_Y + 1], y);
-                        atomicMin(&hb_box[slot][HB_Y + 2], xlo);
-                        atomicMax(&hb_box[slot][HB_Y + 3], xhi);
-                    } else {                                          // (more than VT_SLOTS labels in a cross-section)
-                        int *bb = s.bbox + (size_t)k * 6;
-                        atomicMin(&bb[0], z); atomicMax(&bb[1], z);
-                        atomicMin(&bb[2], y); atomicMax(&bb[3], y);
-                        atomicMin(&bb[4], xlo); atomicMax(&bb[5], xhi);
-                    }
-                }
-            }
-    }
     __syncthreads();
     if (tid < VT_SLOTS && hb_key[tid] >= 0) {
         int *bb = s.bbox + (size_t)hb_key[tid] * 6;
         const int2 bz = *reinterpret_cast<const int2 *>(bb), by = *reinterpret_cast<const int2 *>(bb + 2),
                    bx = *reinterpret_cast<const int2 *>(bb + 4);
-        const int zlo = VZ > 1 ? hb_box[tid][0] : z0, zhi = VZ > 1 ? hb_box[tid][1] : z0;
-        int ylo = hb_box[tid][HB_Y], yhi = hb_box[tid][HB_Y + 1], xlo = hb_box[tid][HB_Y + 2], xhi = hb_box[tid][HB_Y + 3];
-        if (HB_SETS) {
-            const unsigned long long colset = *reinterpret_cast<const unsigned long long *>(&hb_box[tid][0]);
-            const unsigned rows = (unsigned)hb_box[tid][2];
-            ylo = Y0 + __ffs(rows) - 1;
-            yhi = Y0 + 31 - __clz(rows);
-            xlo = x0w + __ffsll((long long)colset) - 1;
-            xhi = x0w + 63 - __clzll((long long)colset);
-        }
-        if (bz.x > zlo) atomicMin(&bb[0], zlo);
-        if (bz.y < zhi) atomicMax(&bb[1], zhi);
+        const unsigned long long colset = *reinterpret_cast<const unsigned long long *>(&hb_box[tid][0]);
+        const unsigned rows = (unsigned)hb_box[tid][2];
+        const int ylo = Y0 + __ffs(rows) - 1, yhi = Y0 + 31 - __clz(rows);
+        const int xlo = x0w + __ffsll((long long)colset) - 1, xhi = x0w + 63 - __clzll((long long)colset);
+        if (bz.x > z0) atomicMin(&bb[0], z0);
+        if (bz.y < z0) atomicMax(&bb[1], z0);
         if (by.x > ylo) atomicMin(&bb[2], ylo);
         if (by.y < yhi) atomicMax(&bb[3], yhi);
         if (bx.x > xlo) atomicMin(&bb[4], xlo);
@@ -1176,16 +1070,11 @@ static_assert(VU_STEP == 4, "a round of the update is one Quad");
 // (quads of a lane requested per round, config 5, ms per sweep: 1 -> 3.01, 2 -> 2.03, 4 -> 1.81, 6 -> 1.84, 8 -> 1.82)
 // (the walk as one sequence of rounds with the NEXT round's labels requested before this round's values -- one trip per round
 // instead of two -- measured 1.84 against 1.80: with four quads per round the trips are no longer what the kernel waits for)
-#ifndef VOL_UPDATE_QUADS
-#define VOL_UPDATE_QUADS 4
-#endif
-constexpr int VU_QUADS = VOL_UPDATE_QUADS;
+constexpr int VU_QUADS = 4;
 
 // (lanes per workgroup, config 5, one box: 64 -> 3.26, 256 -> 2.93, 512 -> 3.13, 1 024 -> 3.89 ms per sweep; an eighth of the centroids
 // per XCD -- block index modulo 8 -> a fixed range -- 3.06 against 2.99: not kept)
-#ifndef VOL_UPDATE_BLOCK
-#define VOL_UPDATE_BLOCK 256
-#endif
+constexpr int VOL_UPDATE_BLOCK = 256;
 __global__ void __launch_bounds__(VOL_UPDATE_BLOCK)
 k_vol_update_f32_lane(VolState s, const float *__restrict__ vol, const int32_t *__restrict__ labels)
 {
@@ -1227,11 +1116,7 @@ k_vol_update_f32_lane(VolState s, const float *__restrict__ vol, const int32_t *
 #pragma unroll
                 for (int q = 0; q < VU_QUADS; ++q) {
                     val[q] = { { 0.f, 0.f, 0.f, 0.f } };
-#ifndef VOL_UPDATE_EAGER_VALUES
                     if (lab[q].v[0] == k || lab[q].v[1] == k || lab[q].v[2] == k || lab[q].v[3] == k)
-#else
-                    if (x + VU_STEP * q <= x1)
-#endif
                         val[q] = *reinterpret_cast<const Quad<float> *>(vol + row + x + VU_STEP * q);
                 }
 #pragma unroll
@@ -1261,7 +1146,7 @@ int launch_vol_slic_f32(VolState s, const float *vol, int32_t *labels, int max_i
     size_t n = (size_t)s.D * s.H * s.W;
     HIP_TRY(hipMemsetAsync(labels, 0xff, n * sizeof(int32_t), st));
     hipLaunchKernelGGL(k_vol_centroid_init_f32, cdiv(s.K, 256), 256, 0, st, s);
-    dim3 grid(cdiv(s.W, 64), cdiv(s.H, 4 * VROWS) * cdiv(s.D, VZ));      // a workgroup: 64 x 16 voxels of VZ slices
+    dim3 grid(cdiv(s.W, 64), cdiv(s.H, 4 * VROWS) * s.D);      // a workgroup: 64 x 16 voxels of one slice
     const size_t n_bricks = (size_t)s.nbz * s.nby * s.nbx;
     for (int it = 0; it < max_iter; ++it) {
         HIP_TRY(hipMemsetAsync(s.brick_count, 0, n_bricks * sizeof(int), st));

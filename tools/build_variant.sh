@@ -1,10 +1,11 @@
 #!/bin/bash
 # Build a variant of libimsegm_hip.so with extra compile flags for ONE source file, for A/B runs on the same GPU box:
-#   tools/build_variant.sh pf32 slic.hip -DSLIC_PF_TX=32 -DSLIC_PF_TY=32
+#   tools/build_variant.sh volprof volume.hip -DIMSEGM_VOL_PHASE_PROF
 #   tools/build_variant.sh base                       (a copy of the current library)
-# -> pyimsegm_amd/build/variants/<name>.so ; compare with  gpurun -- 'bash tools/variants_k.sh "pre_fused" base pf32'
-#    (kernel averages under rocprofv3) or tools/variants.sh (assignment kernel by HIP events).  Known switches:
-#    SLIC_DOT_MIN_BLOCKS (waves per SIMD of the assignment kernel), SLIC_PF_TX / SLIC_PF_TY (pre-processing tile).
+# -> pyimsegm_amd/build/variants/<name>.so ; select it with IMSEGM_HIP_LIBRARY (tools/ab/run.py alternates two libraries on one box).
+# The kernels take no -D tuning switch: their tile shapes, wave counts and phase lengths are constants in csrc/ with the measurements
+# next to them (to try another value, edit the constant in a copy of the tree and build `base` there).  The one compile-time
+# option is the instrumentation IMSEGM_VOL_PHASE_PROF (tools/vol_phase_probe.py).
 set -e
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; shift
