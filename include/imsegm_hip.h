@@ -380,8 +380,11 @@ IMSEGM_API int imsegm_image2d_all_finite(imsegm_image2d *img, int *all_finite_ou
 
 /* Device address of a result buffer of the session (valid until the next call that rewrites it):
  * which = 0: label map int32 H x W; 1: gathered segmentation int32 H x W; 2: gathered soft
- * segmentation float64 H x W x C.  For zero-copy hand-over to a collective library (RCCL) running on
- * the same HIP runtime; call imsegm_ctx_synchronize first. */
+ * segmentation float64 H x W x C; 3: resident feature table float64 n_labels x F, F as the last descriptor
+ * call (or its imsegm_image2d_features_place) laid it out -- an error while no table exists.  A caller may
+ * overwrite the n_labels x F values of the table (a class model is then evaluated on the caller's features).
+ * For zero-copy hand-over to a collective library (RCCL) running on the same HIP runtime; call
+ * imsegm_ctx_synchronize first. */
 IMSEGM_API int imsegm_image2d_device_ptr(imsegm_image2d *img, int which, void **ptr_out);
 
 /* ---------------------------------------------------------------------------------------------

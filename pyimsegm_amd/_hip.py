@@ -953,6 +953,25 @@ class Image2D(object):
         _check(load_library().imsegm_image2d_get_features(self._h, _ptr(out), int(columns)))
         return out
 
+    def put_features(self, table):
+        """make ``table`` (C-contiguous float64, ``n_labels`` x F with 3 <= F <= 256) the resident feature table: the colour means
+        placed into an F-wide table allocate it and mark it valid, then all K x F values are overwritten through
+        ``imsegm_image2d_device_ptr(which = 3)``.  A descriptor group is three columns wide, so a table of one or two columns
+        cannot be placed (``imsegm_image2d_features_place``).  Needs an uploaded image / volume and a label map."""
+        if not isinstance(table, np.ndarray) or table.dtype != np.float64 or table.ndim != 2 or not table.flags.c_contiguous:
+            raise ValueError('put_features: a C-contiguous float64 K x F array is required')
+        k, f = table.shape
+        if k != self.n_labels or k < 1:
+            raise ValueError('put_features: %d rows for %d labels' % (k, self.n_labels))
+        if f < 3 or f > 256:
+            raise ValueError('put_features: 3 .. 256 columns (a descriptor group is three columns wide), got %d' % f)
+        self.features_place(f, 0)
+        self.features_color(True, False, False, to_host=False)
+        ptr = _vp()
+        _check(load_library().imsegm_image2d_device_ptr(self._h, 3, C.byref(ptr)))
+        self.ctx.copy(ptr.value, table.ctypes.data, table.nbytes, synchronize=True)
+        return self
+
     def response_stats(self, mul, div, mean=True, energy=True, var=True):
         k = self.n_labels
         m = np.empty((k, 3), dtype=np.float64) if mean else None

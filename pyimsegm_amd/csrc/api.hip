@@ -346,7 +346,12 @@ int imsegm_image2d_device_ptr(imsegm_image2d *im, int which, void **ptr_out)
         set_error("null argument");
         return -1;
     }
-    DevBuf *b = which == 0 ? &im->labels : which == 1 ? &im->gather_out_i : which == 2 ? &im->gather_out_f : nullptr;
+    if (which == 3 && (!im->have_labels || im->feat_mask == 0 || im->feat_F < 1)) {
+        set_error("device_ptr: no resident feature table");
+        return -1;
+    }
+    DevBuf *b = which == 0 ? &im->labels : which == 1 ? &im->gather_out_i : which == 2 ? &im->gather_out_f :
+                which == 3 ? &im->featK : nullptr;
     if (!b || !b->p) {
         set_error("device_ptr: buffer not available");
         return -1;
