@@ -34,7 +34,9 @@ extern "C" {
 #define IMSEGM_E_FUSED_PATH (-3)
 
 /* status of imsegm_kmeans_lloyd / imsegm_mixture_em for a problem outside the caps of the device fit (more than 16 features, 8
- * components, 16 restarts, 2^31 - 1 rows): nothing is wrong with the context -- the caller fits on the host */
+ * components, 16 restarts, 2^31 - 1 rows), and of imsegm_kmeans_lloyd_wide / imsegm_mixture_em_wide outside theirs (fewer than
+ * 17 or more than 256 features, 8 components, 16 restarts, 2^31 - 1 rows): nothing is wrong with the context -- the caller
+ * fits on the host */
 #define IMSEGM_E_FIT_CAPS (-4)
 
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
@@ -452,6 +454,23 @@ IMSEGM_API int imsegm_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_componen
                                  double reg_covar, double tol, int max_iter, double *weights_out, double *means_out,
                                  double *covariances_out, double *prec_chol_out, double *lower_bound_out, int32_t *n_iter_out,
                                  int32_t *converged_out, int32_t *not_pd_out);
+/* The same two calls for WIDE tables, 17 <= n_features <= 256 (csrc/mixture_fit_wide.hip: fp64 matrix-instruction tiles instead
+ * of a table row in registers): argument lists, outputs and status conventions are those of imsegm_kmeans_lloyd and
+ * imsegm_mixture_em; the table imsegm_kmeans_lloyd_wide uploaded stays in the context for the imsegm_mixture_em_wide that
+ * follows, with the labels.  Both return IMSEGM_E_FIT_CAPS outside 17 <= n_features <= 256, n_clusters <= 8, n_restarts <= 16,
+ * n_rows < 2^31 -- ALSO for n_features <= 16, which the narrow pair fits: the caller routes by width
+ * (graph_cuts.fit_mixture_device_wide).  Of prec_chol_init imsegm_mixture_em_wide reads the upper triangle (precisions_cholesky_
+ * is upper triangular; what lies below its diagonal is taken as zero).  When a covariance is not positive definite, nothing of
+ * that iteration is written for the restart: weights, means, covariances, precision factors and the lower bound are those of
+ * its last COMPLETED iteration (all zero when the M step of the initialisation failed). */
+IMSEGM_API int imsegm_kmeans_lloyd_wide(imsegm_ctx *ctx, const double *table, long n_rows, int n_features, const double *seeds,
+                                        int n_restarts, int n_clusters, int max_iter, double tol, int32_t *labels_out,
+                                        double *centres_out, double *inertia_out, int32_t *n_iter_out, int32_t *empty_out);
+IMSEGM_API int imsegm_mixture_em_wide(imsegm_ctx *ctx, int n_restarts, int n_components, const int32_t *labels,
+                                      const double *weights_init, const double *means_init, const double *prec_chol_init,
+                                      double reg_covar, double tol, int max_iter, double *weights_out, double *means_out,
+                                      double *covariances_out, double *prec_chol_out, double *lower_bound_out,
+                                      int32_t *n_iter_out, int32_t *converged_out, int32_t *not_pd_out);
 
 #ifdef __cplusplus
 }

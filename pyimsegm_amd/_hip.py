@@ -47,8 +47,8 @@ class HipFusedPathError(HipError):
 
 class HipFitCapsError(HipError):
     """``IMSEGM_E_FIT_CAPS`` of include/imsegm_hip.h: the table or the model is outside the caps of the device fit
-    (``imsegm_kmeans_lloyd`` / ``imsegm_mixture_em``: 16 features, 8 components, 16 restarts) -- nothing is wrong with the
-    context, the caller fits on the host"""
+    (``imsegm_kmeans_lloyd`` / ``imsegm_mixture_em``: 16 features, 8 components, 16 restarts; the ``_wide`` pair: 17 to 256
+    features, 8 components, 16 restarts) -- nothing is wrong with the context, the caller fits on the host"""
 
 
 IMSEGM_E_FUSED_PATH = -3
@@ -156,6 +156,10 @@ _SIGNATURES = {
     'imsegm_kmeans_lloyd': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'imsegm_mixture_em': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
+    'imsegm_kmeans_lloyd_wide': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
+                                           _vp]),
+    'imsegm_mixture_em_wide': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -404,6 +408,11 @@ def kmeans_lloyd(table, seeds, max_iter=300, tol=0., want_labels=True, ctx=None)
     ``tol * mean(var(table, axis=0))``).  Returns a dict: labels (R x n int32, or None when not wanted -- they stay on the device
     either way), centres, inertia, n_iter, empty (R flags: a cluster lost all its rows, the restart stopped there).
     Raises :class:`HipFitCapsError` outside F <= 16, C <= 8, R <= 16."""
+    return _kmeans_lloyd('imsegm_kmeans_lloyd', table, seeds, max_iter, tol, want_labels, ctx)
+
+
+def _kmeans_lloyd(entry, table, seeds, max_iter, tol, want_labels, ctx):
+    """the narrow or the wide Lloyd entry point of the library"""
     ctx = ctx or default_context()
     table = np.ascontiguousarray(table, dtype=np.float64)
     seeds = np.ascontiguousarray(seeds, dtype=np.float64)
@@ -413,10 +422,17 @@ def kmeans_lloyd(table, seeds, max_iter=300, tol=0., want_labels=True, ctx=None)
     labels = np.empty((n_restarts, len(table)), dtype=np.int32) if want_labels else None
     centres, inertia = np.empty_like(seeds), np.empty(n_restarts)
     n_iter, empty = np.zeros(n_restarts, dtype=np.int32), np.zeros(n_restarts, dtype=np.int32)
-    _check(load_library().imsegm_kmeans_lloyd(ctx._h, _ptr(table), len(table), table.shape[1], _ptr(seeds), n_restarts, n_clusters,
-                                              int(max_iter), float(tol), _ptr(labels), _ptr(centres), _ptr(inertia), _ptr(n_iter),
-                                              _ptr(empty)))
+    _check(getattr(load_library(), entry)(ctx._h, _ptr(table), len(table), table.shape[1], _ptr(seeds), n_restarts, n_clusters,
+                                           int(max_iter), float(tol), _ptr(labels), _ptr(centres), _ptr(inertia), _ptr(n_iter),
+                                           _ptr(empty)))
     return dict(labels=labels, centres=centres, inertia=inertia, n_iter=n_iter, empty=empty.astype(bool))
+
+
+def kmeans_lloyd_wide(table, seeds, max_iter=300, tol=0., want_labels=True, ctx=None):
+    """``imsegm_kmeans_lloyd_wide``: :func:`kmeans_lloyd` for tables of 17 to 256 features (csrc/mixture_fit_wide.hip); the table
+    stays on the device of ``ctx`` for :func:`mixture_em_wide`.  Same arguments, same dict.
+    Raises :class:`HipFitCapsError` outside 17 <= F <= 256, C <= 8, R <= 16 -- also for F <= 16, which :func:`kmeans_lloyd` fits."""
+    return _kmeans_lloyd('imsegm_kmeans_lloyd_wide', table, seeds, max_iter, tol, want_labels, ctx)
 
 
 def mixture_em(n_restarts, n_components, n_features, labels=None, start=None, reg_covar=1e-6, tol=1e-3, max_iter=100, ctx=None):
@@ -425,6 +441,11 @@ def mixture_em(n_restarts, n_components, n_features, labels=None, start=None, re
     from ``labels`` (R x n int32), or -- both None -- from the labels that call left on the device.  Returns a dict: weights,
     means, covariances, precisions_cholesky, lower_bound, n_iter, converged, not_pd (R flags: a covariance was not positive
     definite, the restart stopped there)."""
+    return _mixture_em('imsegm_mixture_em', 16, n_restarts, n_components, n_features, labels, start, reg_covar, tol, max_iter, ctx)
+
+
+def _mixture_em(entry, max_features, n_restarts, n_components, n_features, labels, start, reg_covar, tol, max_iter, ctx):
+    """the narrow or the wide EM entry point of the library"""
     ctx = ctx or default_context()
     R, K, F = int(n_restarts), int(n_components), int(n_features)
     if labels is not None:
@@ -434,16 +455,24 @@ def mixture_em(n_restarts, n_components, n_features, labels=None, start=None, re
         w0, m0, p0 = (np.ascontiguousarray(v, dtype=np.float64) for v in start)
         if w0.shape != (R, K) or m0.shape != (R, K, F) or p0.shape != (R, K, F, F):
             raise ValueError('start parameters are (R x C, R x C x F, R x C x F x F)')
-    safe = (min(R, 16), min(K, 8), min(F, 16))          # (beyond the caps the call writes nothing)
+    safe = (min(R, 16), min(K, 8), min(F, max_features))          # (beyond the caps the call writes nothing)
     weights, means = np.zeros(safe[:2]), np.zeros(safe)
     cov, prec = np.zeros(safe + (safe[2], )), np.zeros(safe + (safe[2], ))
     bound = np.zeros(safe[0])
     n_iter, converged, not_pd = (np.zeros(safe[0], dtype=np.int32) for _ in range(3))
-    _check(load_library().imsegm_mixture_em(ctx._h, R, K, _ptr(labels), _ptr(w0), _ptr(m0), _ptr(p0), float(reg_covar), float(tol),
-                                            int(max_iter), _ptr(weights), _ptr(means), _ptr(cov), _ptr(prec), _ptr(bound), _ptr(n_iter),
-                                            _ptr(converged), _ptr(not_pd)))
+    _check(getattr(load_library(), entry)(ctx._h, R, K, _ptr(labels), _ptr(w0), _ptr(m0), _ptr(p0), float(reg_covar), float(tol),
+                                           int(max_iter), _ptr(weights), _ptr(means), _ptr(cov), _ptr(prec), _ptr(bound), _ptr(n_iter),
+                                           _ptr(converged), _ptr(not_pd)))
     return dict(weights=weights, means=means, covariances=cov, precisions_cholesky=prec, lower_bound=bound, n_iter=n_iter,
                 converged=converged.astype(bool), not_pd=not_pd.astype(bool))
+
+
+def mixture_em_wide(n_restarts, n_components, n_features, labels=None, start=None, reg_covar=1e-6, tol=1e-3, max_iter=100, ctx=None):
+    """``imsegm_mixture_em_wide``: :func:`mixture_em` on the table the last :func:`kmeans_lloyd_wide` of ``ctx`` uploaded (17 to
+    256 features).  Same arguments, same dict; of ``start``'s precision factors the upper triangle is read.  When a covariance
+    is not positive definite the restart keeps the parameters, the covariances and the lower bound of its last completed
+    iteration (nothing of the failed one is written)."""
+    return _mixture_em('imsegm_mixture_em_wide', 256, n_restarts, n_components, n_features, labels, start, reg_covar, tol, max_iter, ctx)
 
 
 class DeviceGmm(object):

@@ -16,7 +16,7 @@
 // fixed order (sixteen strided sub-sums, then those in order) and does the small dense algebra.  Every restart's arithmetic is
 // its own, so a restart gives the same bits alone and in a batch, and the same call gives the same bits every time.
 // A restart that is done (converged, out of iterations, flagged) is skipped by every kernel: its parameters and outputs freeze.
-#include "session.h"
+#include "mixture_fit.h"
 
 #include <cmath>
 #include <limits>
@@ -24,8 +24,7 @@
 namespace imsegm {
 
 enum { FIT_KM_ASSIGN = 0, FIT_KM_FINAL = 1, FIT_EM_SUMS = 2, FIT_EM_COV = 3 };
-enum { FIT_FLAG_EMPTY = 1, FIT_FLAG_NOT_PD = 2 };
-constexpr int FIT_MAX_F = 16, FIT_MAX_C = 8, FIT_MAX_R = 16, FIT_MAX_BLOCKS = 256, FIT_ITERS_PER_LOOK = 8;
+constexpr int FIT_MAX_F = 16, FIT_MAX_BLOCKS = 256;      // (the caps and flags shared with the wide fit: mixture_fit.h)
 
 struct FitArgs {
     const double *X;
@@ -560,22 +559,6 @@ int fit_caps(const char *who, long n, int F, int C, int R)
     return 0;
 }
 
-// run iterations until every restart is done: FIT_ITERS_PER_LOOK of them are enqueued, then the R `done` words are read
-template <typename Step> int fit_iterate(const FitArgs &a, int max_iter, hipStream_t st, Step step)
-{
-    int done[FIT_MAX_R];
-    for (int it = 0; it < max_iter;) {
-        for (int k = 0; k < FIT_ITERS_PER_LOOK && it < max_iter; ++k, ++it)
-            if (step()) return -1;
-        HIP_TRY(hipMemcpyAsync(done, a.done, (size_t)a.R * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        bool all = true;
-        for (int r = 0; r < a.R; ++r) all = all && done[r] != 0;
-        if (all) break;
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -607,7 +590,7 @@ int imsegm_kmeans_lloyd(imsegm_ctx *ctx, const double *table, long n_rows, int n
     HIP_TRY(hipMemsetAsync(a.labels, 0xff, (size_t)R * n * 4, st));          // no row has a label yet (-1)
     HIP_TRY(hipMemsetAsync(w + lay.o_ints, 0, (size_t)6 * R * 4, st));
     HIP_TRY(hipMemsetAsync(w + lay.o_dbl, 0, (size_t)2 * R * 8, st));
-    if (fit_iterate(a, max_iter, st, [&]() { return fit_pass<FIT_KM_ASSIGN>(a, st); })) return -1;
+    if (fit_iterate(a.done, a.R, max_iter, st, [&]() { return fit_pass<FIT_KM_ASSIGN>(a, st); })) return -1;
     if (fit_pass<FIT_KM_FINAL>(a, st)) return -1;
     int ints[6 * FIT_MAX_R];
     HIP_TRY(hipMemcpyAsync(ints, w + lay.o_ints, (size_t)6 * R * 4, hipMemcpyDeviceToHost, st));
@@ -680,7 +663,7 @@ int imsegm_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_components, const i
         a.from_labels = 0;
     }
     HIP_TRY(hipStreamSynchronize(st));          // (pageable sources are free again)
-    if (fit_iterate(a, max_iter, st, [&]() { return fit_pass<FIT_EM_SUMS>(a, st) || fit_pass<FIT_EM_COV>(a, st) ? -1 : 0; })) return -1;
+    if (fit_iterate(a.done, a.R, max_iter, st, [&]() { return fit_pass<FIT_EM_SUMS>(a, st) || fit_pass<FIT_EM_COV>(a, st) ? -1 : 0; })) return -1;
     int ints[6 * FIT_MAX_R];
     double bounds[2 * FIT_MAX_R];
     HIP_TRY(hipMemcpyAsync(ints, w + lay.o_ints, (size_t)6 * R * 4, hipMemcpyDeviceToHost, st));

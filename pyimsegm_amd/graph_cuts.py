@@ -462,6 +462,26 @@ def fit_mixture_device(mixture, table, ctx=None):
     not positive definite (the host fit repairs or raises what scikit-learn raises), another kind of mixture, a float32 table.
     A table with NaN or inf raises scikit-learn's ValueError; no library or no GPU raises ``HipUnavailableError``.
     """
+    return _fit_mixture_with(_hip.kmeans_lloyd, _hip.mixture_em, mixture, table, ctx)
+
+
+def fit_mixture_device_wide(mixture, table, ctx=None):
+    """:func:`fit_mixture_device` for tables of any width up to 256 features, routed by width: up to 16 features it IS
+    :func:`fit_mixture_device` (``imsegm_kmeans_lloyd`` / ``imsegm_mixture_em``, the same bytes); from 17 to 256 features the Lloyd
+    and EM iterations run on the fp64 matrix-instruction kernels of ``csrc/mixture_fit_wide.hip`` (``imsegm_kmeans_lloyd_wide`` /
+    ``imsegm_mixture_em_wide``).  Seeds, Lloyd tolerance, the pick of the best restart and every refusal are the narrow fit's;
+    what goes to :func:`fit_mixture_restarts` on the restored random stream, with the reason logged at INFO: more than 256
+    features / 8 components / 16 restarts, an empty cluster, a covariance that is not positive definite, another kind of
+    mixture, a float32 table.
+    """
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[1] <= 16:
+        return fit_mixture_device(mixture, table, ctx=ctx)
+    return _fit_mixture_with(_hip.kmeans_lloyd_wide, _hip.mixture_em_wide, mixture, table, ctx)
+
+
+def _fit_mixture_with(kmeans_lloyd, mixture_em, mixture, table, ctx):
+    """the device fit through one pair of entry points of ``_hip`` (narrow or wide)"""
     import warnings
     from sklearn.exceptions import ConvergenceWarning
     from sklearn.utils import check_array, check_random_state
@@ -478,13 +498,13 @@ def fit_mixture_device(mixture, table, ctx=None):
             if hasattr(mixture, '_validate_params'):
                 mixture._validate_params()
             seeds = device_fit_seeds(table, n_comp, n_init, stream)
-            lloyd = _hip.kmeans_lloyd(table, seeds, _KMEANS_MAX_ITER, _KMEANS_TOL * np.mean(np.var(table, axis=0)),
-                                      want_labels=False, ctx=ctx)
+            lloyd = kmeans_lloyd(table, seeds, _KMEANS_MAX_ITER, _KMEANS_TOL * np.mean(np.var(table, axis=0)),
+                                 want_labels=False, ctx=ctx)
             if lloyd['empty'].any():
                 reason = 'k-means left a cluster empty in restart %d' % int(np.argmax(lloyd['empty']))
             else:
-                fit = _hip.mixture_em(n_init, n_comp, table.shape[1], reg_covar=mixture.reg_covar, tol=mixture.tol,
-                                      max_iter=mixture.max_iter, ctx=ctx)
+                fit = mixture_em(n_init, n_comp, table.shape[1], reg_covar=mixture.reg_covar, tol=mixture.tol,
+                                 max_iter=mixture.max_iter, ctx=ctx)
                 if fit['not_pd'].any():
                     reason = 'a covariance of restart %d is not positive definite' % int(np.argmax(fit['not_pd']))
         except _hip.HipFitCapsError as ex:
@@ -509,12 +529,12 @@ def fit_mixture_device(mixture, table, ctx=None):
 
 
 def _fit_place(fit_on):
-    """'host' or 'device' from the ``fit_on`` keyword; None: the environment variable IMSEGM_FIT_ON, unset: 'host'"""
+    """'host', 'device' or 'device_wide' from the ``fit_on`` keyword; None: the environment variable IMSEGM_FIT_ON, unset: 'host'"""
     import os
     if fit_on is None:
         fit_on = os.environ.get('IMSEGM_FIT_ON') or 'host'
-    if fit_on not in ('host', 'device'):
-        raise ValueError("fit_on is 'host' or 'device', not %r" % (fit_on, ))
+    if fit_on not in ('host', 'device', 'device_wide'):
+        raise ValueError("fit_on is 'host', 'device' or 'device_wide', not %r" % (fit_on, ))
     return fit_on
 
 
@@ -528,7 +548,9 @@ def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, us
 
     ``fit_on``: ``'host'`` (the default: scikit-learn, bit for bit ``GaussianMixture.fit``) or ``'device'``
     (:func:`fit_mixture_device`: the same model from other seeds and with sums in another order -- last digits and the winning
-    restart differ); ``None`` reads the environment variable ``IMSEGM_FIT_ON``.
+    restart differ; tables of more than 16 features go to the host) or ``'device_wide'`` (:func:`fit_mixture_device_wide`:
+    the device fit for tables of up to 256 features -- up to 16 features the same bytes as ``'device'``); ``None`` reads the
+    environment variable ``IMSEGM_FIT_ON``.
     """
     from sklearn import decomposition, mixture, pipeline, preprocessing
     fit_on = _fit_place(fit_on)
@@ -551,6 +573,8 @@ def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, us
         table = step.fit_transform(table)
     if fit_on == 'device':
         fit_mixture_device(model.steps[-1][1], table, ctx=_ctx)
+    elif fit_on == 'device_wide':
+        fit_mixture_device_wide(model.steps[-1][1], table, ctx=_ctx)
     else:
         fit_mixture_restarts(model.steps[-1][1], table)
     return model
