@@ -218,7 +218,9 @@ IMSEGM_API int imsegm_image2d_response_stats(imsegm_image2d *img, double mul, do
  *   a label without pixels) and the mean of np.sum(np.gradient(plane), axis=0) of that normalised response per channel plane
  *   (a volume: per slice), float32 staging as the other means -- the 'median' / 'meanGrad' columns of :1096 on the device.
  *   mul >= 0, div > 0; the gradient needs H, W >= 2.  Neither changes the prepared planes, the response, the uploaded image,
- *   the resident feature table or a prepared graph: the next lm_battery runs without another lm_prepare. */
+ *   the resident feature table or a prepared graph: the next lm_battery runs without another lm_prepare.
+ *   response_mean_gradient: div must be at least the largest magnitude of the response (the L2 norm that lm_battery returns
+ *   is) -- the fixed-point scale of the mean is taken from mul (|gradient sum| <= 4 mul), not from a min / max pass. */
 IMSEGM_API int imsegm_image2d_response_median(imsegm_image2d *img, double mul, double div, double *median_out);
 IMSEGM_API int imsegm_image2d_response_mean_gradient(imsegm_image2d *img, double mul, double div, double *mean_out);
 /* inspection for the parity tests: the current filter response as [3][H][W] planes */

@@ -57,14 +57,15 @@ k_median_pick(const unsigned long long *__restrict__ keys, const unsigned int *_
     } else if (n & 1u) {
         m = key_value(keys[o + n / 2]);
         if (norm.on) m = (m * norm.mul) / norm.div;
+        m = 0.0 + m;                                              // np.mean sums from +0.0: a median of -0.0 comes out +0.0
     } else {
         double a = key_value(keys[o + n / 2 - 1]), b = key_value(keys[o + n / 2]);
         if (norm.on) {
             a = (a * norm.mul) / norm.div;
             b = (b * norm.mul) / norm.div;
         }
-        if (dtype == DT_F32) m = (double)(((float)a + (float)b) / 2.0f);
-        else m = (a + b) / 2.0;
+        if (dtype == DT_F32) m = (double)(((0.0f + (float)a) + (float)b) / 2.0f);
+        else m = ((0.0 + a) + b) / 2.0;
     }
     out[(size_t)k * C + c] = m;
 }
