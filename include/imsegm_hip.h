@@ -419,6 +419,45 @@ IMSEGM_API int imsegm_label_hist2d(imsegm_ctx *ctx, const int16_t *segm, int hei
 IMSEGM_API int imsegm_ray_features_binary2d(imsegm_ctx *ctx, const int8_t *seg_binary, int height, int width,
                                             const int32_t *positions, int n_positions, const float *directions, int n_angles,
                                             int edge, float *ray_dist_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * scoring label maps (imsegm/labeling.py): boundary masks, exact Euclidean distance maps, boundary distances, label overlaps.
+ * Label maps are host int32, height x width, raster order.  Integer arithmetic up to one correctly rounded fp64 square root per
+ * value: same bits as scipy.ndimage.distance_transform_edt on the same mask.  Squared distances are held in 32 bits: maps with
+ * height^2 + width^2 > 2^32 - 1 (or more than 65535 rows) are refused with an error.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_BOUNDARY_THICK 0            /* skimage.segmentation.find_boundaries(mode='thick'): a 4-neighbour inside the image differs */
+#define IMSEGM_BOUNDARY_CONTOUR 1          /* labeling.py:59-66: interior pixels that carry `label` with a 4-neighbour that does not */
+#define IMSEGM_BOUNDARY_CONTOUR_BORDER 2   /* labeling.py:59-77 include_boundary=True: plus the border pixels that carry `label` */
+/* Replaces the per-pixel Python loops of imsegm/labeling.py:34-79 contour_binary_map(seg, label, include_boundary) (modes 1, 2;
+ * also the points of contour_coords :82-117 in row-major order) and skimage.segmentation.find_boundaries(seg, mode='thick')
+ * as called at labeling.py:708,710 (mode 0, `label` unused).  mask_out: host uint8, 1 on the boundary. */
+IMSEGM_API int imsegm_boundary_mask(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int mode, int label,
+                                    uint8_t *mask_out);
+/* Replaces imsegm/labeling.py:146-169 compute_distance_map(seg, label) (mode 1: contour_coords, binary_image_from_coords and
+ * scipy.ndimage.distance_transform_edt of the complement) and, with mode 0, the distance map of labeling.py:710-711.
+ * dist_out: host float64, distance of every pixel to the nearest mask pixel.  A map without a mask pixel gives what scipy gives:
+ * the distance to (row -1, column 0). */
+IMSEGM_API int imsegm_distance_map(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int mode, int label,
+                                   double *dist_out);
+/* Replaces imsegm/labeling.py:684-716 compute_boundary_distances(segm_ref, segm) (the superpixel measure of
+ * experiments_segmentation/run_eval_superpixels.py:108-131): the pixels of the thick boundary of segm_ref in row-major order as
+ * points_out[2 i] = row, points_out[2 i + 1] = column, and dist_out[i] = their distance to the thick boundary of segm.  Only the
+ * points travel back, never a height x width map.  *n_points_out = number of points (0: segm_ref has no boundary); more points
+ * than `capacity` (entries of dist_out, pairs of points_out) is an error that still reports the number. */
+IMSEGM_API int imsegm_boundary_distances(imsegm_ctx *ctx, const int32_t *segm_ref, const int32_t *segm, int height, int width,
+                                         int32_t *points_out, double *dist_out, int capacity, int *n_points_out);
+/* The same against the label map a 2-D session holds (from imsegm_image2d_slic or imsegm_image2d_set_labels) as `segm`: only
+ * segm_ref is uploaded. */
+IMSEGM_API int imsegm_image2d_boundary_distances(imsegm_image2d *img, const int32_t *segm_ref, int32_t *points_out, double *dist_out,
+                                                 int capacity, int *n_points_out);
+/* Replaces the per-pixel Python loop of imsegm/labeling.py:490-523 compute_labels_overlap_matrix(seg1, seg2) (and the matrix
+ * relabel_max_overlap_unique :583 and relabel_max_overlap_merge :664 start from): overlap_out[a * n_labels2 + b] = number of
+ * positions i < n with seg1[i] == a and seg2[i] == b; pairs with a negative label (or one beyond its extent) are skipped.
+ * overlap_out: host int64 [n_labels1 * n_labels2], at most 2^28 entries. */
+IMSEGM_API int imsegm_labels_overlap(imsegm_ctx *ctx, const int32_t *seg1, const int32_t *seg2, size_t n, int n_labels1,
+                                     int n_labels2, int64_t *overlap_out);
+
 /* Replaces gco.cut_general_graph(edges, edge_weights, unary_cost, pairwise_cost, n_iter,
  * algorithm='expansion') (gco-wrapper >= 3.0.8) as called at imsegm/graph_cuts.py:735-744.
  * edges: E x 2 int32 with edges[:,0] < edges[:,1]; edge_weights: E; unary: K x C; pairwise: C x C

@@ -160,6 +160,11 @@ _SIGNATURES = {
                                            _vp]),
     'imsegm_mixture_em_wide': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
+    'imsegm_boundary_mask': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_distance_map': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_boundary_distances': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip]),
+    'imsegm_image2d_boundary_distances': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ip]),
+    'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -773,6 +778,15 @@ class Image2D(object):
         out = np.empty((self.n_labels, int(nb_annot)), dtype=np.int64)
         _check(load_library().imsegm_image2d_label_hist(self._h, _ptr(annot), int(nb_annot), _ptr(out)))
         return out
+
+    def boundary_distances(self, segm_ref):
+        """``imsegm_image2d_boundary_distances``: the thick boundary of ``segm_ref`` (points int32 n x 2, row-major) and its
+        distances (float64 n) to the thick boundary of the resident label map; only ``segm_ref`` is uploaded"""
+        segm_ref = np.ascontiguousarray(segm_ref, dtype=np.int32)
+        if segm_ref.shape != self.shape:
+            raise ValueError('reference map %r does not match the session %r' % (segm_ref.shape, self.shape))
+        lib = load_library()
+        return _boundary_distances(lambda *out: lib.imsegm_image2d_boundary_distances(self._h, _ptr(segm_ref), *out), self.shape)
 
     def get_lab(self):
         out = np.empty((3,) + self.shape, dtype=np.float64)
@@ -1406,6 +1420,51 @@ def label_hist2d(segm, windows, struc_elem, nb_labels, ctx=None):
     out = np.zeros((len(windows), int(nb_labels)), dtype=np.uint32)
     _check(load_library().imsegm_label_hist2d(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], _ptr(windows), len(windows),
                                               _ptr(selem), selem.shape[0], selem.shape[1], int(nb_labels), _ptr(out)))
+    return out
+
+
+#: modes of ``imsegm_boundary_mask`` / ``imsegm_distance_map`` (``IMSEGM_BOUNDARY_*`` of include/imsegm_hip.h)
+BOUNDARY_THICK, BOUNDARY_CONTOUR, BOUNDARY_CONTOUR_BORDER = 0, 1, 2
+
+
+def boundary_mask(labels, mode, label=0, ctx=None):
+    """``imsegm_boundary_mask`` on a contiguous 2-D int32 label map: uint8 H x W, 1 on the boundary"""
+    ctx = ctx or default_context()
+    out = np.empty(labels.shape, dtype=np.uint8)
+    _check(load_library().imsegm_boundary_mask(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], int(mode), int(label), _ptr(out)))
+    return out
+
+
+def distance_map(labels, mode, label=0, ctx=None):
+    """``imsegm_distance_map`` on a contiguous 2-D int32 label map: float64 H x W, distance to the nearest mask pixel"""
+    ctx = ctx or default_context()
+    out = np.empty(labels.shape, dtype=np.float64)
+    _check(load_library().imsegm_distance_map(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], int(mode), int(label), _ptr(out)))
+    return out
+
+
+def _boundary_distances(call, shape):
+    # room for every pixel: virtual memory only, the pages no point reaches are never touched.  The points go back as a view (the
+    # caller converts them to int64 and lets the block go), the distances as a copy of their own so that the block is not kept.
+    capacity = int(shape[0]) * int(shape[1])
+    points, dist, count = np.empty((capacity, 2), dtype=np.int32), np.empty(capacity, dtype=np.float64), C.c_int(0)
+    _check(call(_ptr(points), _ptr(dist), capacity, C.byref(count)))
+    return points[:count.value], dist[:count.value].copy()
+
+
+def boundary_distances(segm_ref, segm, ctx=None):
+    """``imsegm_boundary_distances`` on two contiguous 2-D int32 label maps of one shape: (points int32 n x 2, dist float64 n)"""
+    ctx = ctx or default_context()
+    lib = load_library()
+    return _boundary_distances(lambda *out: lib.imsegm_boundary_distances(ctx._h, _ptr(segm_ref), _ptr(segm), segm.shape[0],
+                                                                          segm.shape[1], *out), segm.shape)
+
+
+def labels_overlap(seg1, seg2, n_labels1, n_labels2, ctx=None):
+    """``imsegm_labels_overlap`` on two contiguous int32 label arrays of one size: int64 [n_labels1, n_labels2]"""
+    ctx = ctx or default_context()
+    out = np.empty((int(n_labels1), int(n_labels2)), dtype=np.int64)
+    _check(load_library().imsegm_labels_overlap(ctx._h, _ptr(seg1), _ptr(seg2), seg1.size, int(n_labels1), int(n_labels2), _ptr(out)))
     return out
 
 

@@ -308,6 +308,14 @@ int stats_run(imsegm_image2d *im, const void *src, int dtype, double maxabs, int
 // where a descriptor call puts its columns of the resident feature table (imsegm_image2d_features_place; api_fused.hip)
 int take_placement(imsegm_image2d *im, int own_F, bool to_host, int *table_F, int *col0);
 
+// where the pieces of one label-map scoring call live inside the context's scratch buffer (api_boundary.hip; every piece starts on a
+// 256-byte boundary; a piece the kind of call does not use stays at 0)
+struct BoundaryPlan {
+    size_t o_ref = 0, o_seg = 0, o_g = 0, o_d2 = 0, o_dist = 0, o_mask_a = 0, o_mask_b = 0, o_counts = 0, o_flags = 0, bytes = 0;
+};
+enum { BP_MASK = 0, BP_DISTANCE_MAP = 1, BP_DISTANCES = 2, BP_DISTANCES_SESSION = 3 };
+BoundaryPlan boundary_plan(int H, int W, int kind);
+
 }  // namespace imsegm
 
 // what of the 2-D SLIC state follows from the sizes (api_image2d.hip)

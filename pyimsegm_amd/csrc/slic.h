@@ -253,6 +253,22 @@ int launch_narrow_labels_u8(const int32_t *src, uint8_t *dst, size_t n, hipStrea
 int launch_narrow_soft_f32(const double *src, float *dst, size_t n, hipStream_t st);
 int launch_count_nonfinite(const void *src, int dtype, size_t n, unsigned int *count_dev, hipStream_t st);
 
+// boundary.hip -----------------------------------------------------------------------------------
+// mask[H][W] = 1 on the boundary pixels of a label map; mode 0: find_boundaries(mode='thick'), 1: contour of `label`
+// (labeling.py:59-66), 2: the same with the image border (:67-77).  any_set: one device int, left at 1 when a pixel is set
+int launch_boundary_mask(const int32_t *labels, int H, int W, int mode, int label, uint8_t *mask, int *any_set, hipStream_t st);
+// exact Euclidean distance of every pixel to the nearest set pixel of `mask`: squared as uint32 (d2_out) and / or as its fp64
+// root (dist_out), either may be null; g: H * W words of scratch.  Refuses H^2 + W^2 > 2^32 - 1 (edt_size_ok)
+int edt_size_ok(int H, int W);
+int launch_edt(const uint8_t *mask, const int *any_set, int H, int W, uint32_t *g, uint32_t *d2_out, double *dist_out, hipStream_t st);
+// stable (row-major) compaction of the set pixels of a mask of n pixels: launch_compact_count leaves the exclusive offsets of the
+// 2048-pixel chunks in counts[0 .. words - 1) and the number of set pixels in counts[words - 1], words = compact_count_words(n);
+// launch_compact_gather writes (row, column) and sqrt(d2) of set pixel number i to points[2 i], points[2 i + 1], dist[i]
+size_t compact_count_words(size_t n);
+int launch_compact_count(const uint8_t *mask, size_t n, uint32_t *counts, hipStream_t st);
+int launch_compact_gather(const uint8_t *mask, const uint32_t *d2, size_t n, int W, const uint32_t *offsets, int32_t *points,
+                          double *dist, hipStream_t st);
+
 // median.hip -------------------------------------------------------------------------------------
 // on: a float64 source is read as (value * mul) / div (a Leung-Malik response normalised as descriptors.py:1094)
 struct MedianNorm { int on; double mul, div; };
