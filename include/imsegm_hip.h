@@ -148,6 +148,9 @@ IMSEGM_API int imsegm_image2d_label_hist(imsegm_image2d *img, const int32_t *ann
 /* inspection for the parity tests: pre-processed Lab planes [3][H][W] and raw k-means assignment */
 IMSEGM_API int imsegm_image2d_get_lab(imsegm_image2d *img, double *lab_out);
 IMSEGM_API int imsegm_image2d_get_nearest(imsegm_image2d *img, int32_t *nearest_out);
+/* out[3] = { min, max of the uploaded image as the last imsegm_image2d_slic reduced them on the device, max |value| of its
+ * pre-processed planes (what fixes the fixed-point format of the centroid sums) } */
+IMSEGM_API int imsegm_image2d_get_pre_scalars(imsegm_image2d *img, double out[3]);
 
 /* Replaces imsegm.features_cython.computeColorImage2dMean / Energy / Variance + normColorFeatures
  * (imsegm/features_cython.pyx:59-141) on the uploaded image and the current label map.

@@ -129,6 +129,7 @@ _SIGNATURES = {
     'imsegm_image2d_label_hist': (C.c_int, [_vp, _vp, C.c_int, _vp]),
     'imsegm_image2d_get_lab': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_get_nearest': (C.c_int, [_vp, _vp]),
+    'imsegm_image2d_get_pre_scalars': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_color_stats': (C.c_int, [_vp, _vp, _vp, _vp]),
     'imsegm_image2d_graph': (C.c_int, [_vp, _vp, C.c_int, _ip, _vp, _vp]),
     'imsegm_image2d_gather': (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
@@ -792,6 +793,13 @@ class Image2D(object):
         out = np.empty((3,) + self.shape, dtype=np.float64)
         _check(load_library().imsegm_image2d_get_lab(self._h, _ptr(out)))
         return out
+
+    def get_pre_scalars(self):
+        """(min, max, premax) of the last :meth:`slic` as the device holds them: the extremes of the uploaded image and the
+        largest |value| of the pre-processed planes"""
+        out = np.empty(3, dtype=np.float64)
+        _check(load_library().imsegm_image2d_get_pre_scalars(self._h, _ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def get_nearest(self):
         out = np.empty(self.shape, dtype=np.int32)

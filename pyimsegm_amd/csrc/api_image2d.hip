@@ -387,6 +387,21 @@ int imsegm_image2d_get_lab(imsegm_image2d *im, double *lab_out)
     return 0;
 }
 
+// {min, max, premax} of the last slic: three consecutive doubles of the session's reduction page (behind the two key words)
+int imsegm_image2d_get_pre_scalars(imsegm_image2d *im, double out[3])
+{
+    if (!im || bind(im->ctx)) return -1;
+    if (wrong_kind(im, false)) return -1;
+    if (!out || im->labA.cap < 3 * im->n * 8 || im->small.cap < 4096) {
+        set_error("slic has not been run");
+        return -1;
+    }
+    const double *minmax = reinterpret_cast<const double *>(im->small.as<unsigned long long>() + 2);
+    HIP_TRY(hipStreamSynchronize(im->ctx->stream));
+    HIP_TRY(hipMemcpy(out, minmax, 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int imsegm_image2d_get_nearest(imsegm_image2d *im, int32_t *nearest_out)
 {
     if (!im || bind(im->ctx)) return -1;

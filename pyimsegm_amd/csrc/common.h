@@ -105,7 +105,7 @@ __device__ __forceinline__ double det_cbrt(double x)
 // x / C for a constant C, correctly rounded, in three instructions instead of the ~14 of an IEEE division (Markstein: with
 // y = RN(1 / C), q = RN(x * y) and r = x - q * C formed exactly by an FMA, RN(q + r * y) = RN(x / C) whenever the significand of C
 // is not all ones -- and as long as r does not underflow: for x = 0 or 2^-500 <= |x| <= 2^500 only, which the caller guarantees
-// (the XYZ values of a uint8 image: 0 or >= 5e-5).  Checked against the division on 4 * 10^8 random arguments per constant
+// (the X and Z of a uint8 image are 0 or >= 5.9e-6, the pixel (1, 0, 0) without normalisation; with it they are 0 or larger still).  Checked against the division on 4 * 10^8 random arguments per constant
 // (0.95047, 1.08883); same bits as the oracle's plain division.
 __device__ __forceinline__ double div_by_const_in_range(double x, double c, double rc)
 {

@@ -369,7 +369,7 @@ k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double
             double X = lin0 * 0.412453 + lin1 * 0.357580 + lin2 * 0.180423;
             double Y = lin0 * 0.212671 + lin1 * 0.715160 + lin2 * 0.072169;
             double Z = lin0 * 0.019334 + lin1 * 0.119193 + lin2 * 0.950227;
-            // (uint8 pixels: X, Z are 0 or >= 5e-5 -- the exact three-instruction quotient; Y / 1.0 = Y)
+            // (uint8 pixels: X, Z are 0 or >= 5.9e-6, far inside 2^+-500 -- the exact three-instruction quotient; Y / 1.0 = Y)
             double f[3] = { DIV_CONST_IN_RANGE(X, 0.95047), Y, DIV_CONST_IN_RANGE(Z, 1.08883) };
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
