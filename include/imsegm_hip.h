@@ -424,6 +424,39 @@ IMSEGM_API int imsegm_ray_features_binary2d(imsegm_ctx *ctx, const int8_t *seg_b
                                             int edge, float *ray_dist_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * centre-candidate point descriptors: one launch for all positions (row, col) of a map
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_RING_MAX_BINS 32            /* imsegm_ring_hist2d: n_radii * (nb_labels + 1) counters per lane fit the LDS budget */
+#define IMSEGM_RING_PROBA_MAX_DISCS 16     /* imsegm_ring_hist_proba2d: n_radii sums per lane fit the LDS budget */
+#define IMSEGM_RAY_MAX_ANGLES 4096
+#define IMSEGM_RAY_MAX_BORDER_LABELS 64
+/* Replaces the loops over positions and discs of imsegm.descriptors.compute_label_histograms_positions for label maps
+ * (imsegm/descriptors.py:1288-1369: per position and disc one compute_label_hist_segm :1413-1459 = adjust_bounding_box_crop
+ * :1372-1410 + computeLabelHistogram2d + np.sum(struc_elem)).  Disc d is skimage.morphology.disk(radii[d]), dy^2 + dx^2 <=
+ * radii[d]^2, clipped to the map; radii grow strictly, positions lie inside the map, n_radii * (nb_labels + 1) <=
+ * IMSEGM_RING_MAX_BINS.  hist_out[p][d][l] = pixels with label l (0 <= l < nb_labels) under disc d around position p;
+ * size_out[p][d] = pixels under the clipped disc whatever their label (the reference's sel_size).  Exact integers. */
+IMSEGM_API int imsegm_ring_hist2d(imsegm_ctx *ctx, const int16_t *segm, int height, int width, const int32_t *positions,
+                                  int n_positions, const int32_t *radii, int n_radii, int nb_labels, uint32_t *hist_out,
+                                  uint32_t *size_out);
+/* Replaces imsegm.descriptors.compute_label_hist_proba (descriptors.py:1498-1528) under the same loops (:1343-1363) for
+ * probability layers proba[height][width][n_layers] (float64): sum_out[p][d][c] = sum of layer c under disc d, float64 in a fixed
+ * order (two calls give the same bits), size_out[p][d] as above; n_radii <= IMSEGM_RING_PROBA_MAX_DISCS. */
+IMSEGM_API int imsegm_ring_hist_proba2d(imsegm_ctx *ctx, const double *proba, int height, int width, int n_layers,
+                                        const int32_t *positions, int n_positions, const int32_t *radii, int n_radii,
+                                        double *sum_out, uint32_t *size_out);
+/* Replaces the mask and the loop over positions of imsegm.descriptors.compute_ray_features_positions (descriptors.py:1869-1886:
+ * seg_binary[segm == lb] = True for every border label, then per position compute_ray_features_segm_2d :1715-1758 =
+ * computeRayFeaturesBinary2d + scipy.ndimage.gaussian_filter1d).  segm: host int32; the mask is formed on the device from
+ * border_labels; directions and edge as imsegm_ray_features_binary2d.  smooth_taps: NULL (no smoothing) or smooth_radius + 1
+ * weights of gaussian_filter1d's kernel from its centre outwards; the row of a position is filtered along the angle with
+ * boundary mode 'reflect', float64 sums in scipy's order, and stored as float32. */
+IMSEGM_API int imsegm_ray_features_labels2d(imsegm_ctx *ctx, const int32_t *segm, int height, int width, const int32_t *border_labels,
+                                            int n_border, const int32_t *positions, int n_positions, const float *directions,
+                                            int n_angles, int edge, const double *smooth_taps, int smooth_radius,
+                                            float *ray_dist_out);
+
+/* ---------------------------------------------------------------------------------------------
  * scoring label maps (imsegm/labeling.py): boundary masks, exact Euclidean distance maps, boundary distances, label overlaps.
  * Label maps are host int32, height x width, raster order.  Integer arithmetic up to one correctly rounded fp64 square root per
  * value: same bits as scipy.ndimage.distance_transform_edt on the same mask.  Squared distances are held in 32 bits: maps with

@@ -152,6 +152,10 @@ _SIGNATURES = {
     'imsegm_image2d_mean_gradient': (C.c_int, [_vp, _vp]),
     'imsegm_label_hist2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     'imsegm_ray_features_binary2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    'imsegm_ring_hist2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'imsegm_ring_hist_proba2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    'imsegm_ray_features_labels2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int,
+                                               _vp]),
     'imsegm_cut_general_graph': (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp,
                                            C.POINTER(C.c_int64)]),
     'imsegm_kmeans_lloyd': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
@@ -1485,4 +1489,60 @@ def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):
     out = np.empty((len(positions), len(directions)), dtype=np.float32)
     _check(load_library().imsegm_ray_features_binary2d(ctx._h, _ptr(seg), seg.shape[0], seg.shape[1], _ptr(positions), len(positions),
                                                        _ptr(directions), len(directions), int(edge), _ptr(out)))
+    return out
+
+
+#: LDS budgets of the ring kernels (``IMSEGM_RING_MAX_BINS`` / ``IMSEGM_RING_PROBA_MAX_DISCS`` of include/imsegm_hip.h)
+RING_MAX_BINS, RING_PROBA_MAX_DISCS = 32, 16
+#: ``IMSEGM_RAY_MAX_ANGLES`` / ``IMSEGM_RAY_MAX_BORDER_LABELS``
+RAY_MAX_ANGLES, RAY_MAX_BORDER_LABELS = 4096, 64
+
+
+def ring_hist2d(segm, positions, radii, nb_labels, ctx=None):
+    """label histograms under concentric discs for a batch of positions (``imsegm_ring_hist2d``; radii grow strictly):
+    uint32 hist [P, D, nb_labels] and the sizes of the clipped discs, uint32 [P, D]; no position: empty tables, no launch"""
+    positions = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1, 2)
+    radii = np.ascontiguousarray(radii, dtype=np.int32).ravel()
+    hist = np.zeros((len(positions), len(radii), int(nb_labels)), dtype=np.uint32)
+    size = np.zeros((len(positions), len(radii)), dtype=np.uint32)
+    if len(positions) == 0:
+        return hist, size
+    ctx = ctx or default_context()
+    segm = np.ascontiguousarray(segm, dtype=np.int16)
+    _check(load_library().imsegm_ring_hist2d(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], _ptr(positions), len(positions),
+                                             _ptr(radii), len(radii), int(nb_labels), _ptr(hist), _ptr(size)))
+    return hist, size
+
+
+def ring_hist_proba2d(proba, positions, radii, ctx=None):
+    """sums of the layers of ``proba`` (H x W x C) under concentric discs for a batch of positions (``imsegm_ring_hist_proba2d``):
+    float64 [P, D, C] and the sizes of the clipped discs, uint32 [P, D]; no position: empty tables, no launch"""
+    proba = np.ascontiguousarray(proba, dtype=np.float64)
+    positions = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1, 2)
+    radii = np.ascontiguousarray(radii, dtype=np.int32).ravel()
+    total = np.zeros((len(positions), len(radii), proba.shape[2]), dtype=np.float64)
+    size = np.zeros((len(positions), len(radii)), dtype=np.uint32)
+    if len(positions) == 0:
+        return total, size
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_ring_hist_proba2d(ctx._h, _ptr(proba), proba.shape[0], proba.shape[1], proba.shape[2], _ptr(positions),
+                                                   len(positions), _ptr(radii), len(radii), _ptr(total), _ptr(size)))
+    return total, size
+
+
+def ray_features_labels2d(segm, border_labels, positions, directions, edge, smooth_taps=None, ctx=None):
+    """ray features of a batch of positions against the mask ``segm in border_labels``, optionally smoothed along the angle with
+    the half kernel ``smooth_taps`` of :func:`gaussian_taps` (``imsegm_ray_features_labels2d``): float32 [P, A]"""
+    positions = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1, 2)
+    directions = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 2)
+    out = np.empty((len(positions), len(directions)), dtype=np.float32)
+    if len(positions) == 0:
+        return out
+    ctx = ctx or default_context()
+    segm = np.ascontiguousarray(segm, dtype=np.int32)
+    border = np.ascontiguousarray(border_labels, dtype=np.int32).ravel()
+    taps = None if smooth_taps is None else np.ascontiguousarray(smooth_taps, dtype=np.float64)
+    _check(load_library().imsegm_ray_features_labels2d(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], _ptr(border), len(border),
+                                                       _ptr(positions), len(positions), _ptr(directions), len(directions), int(edge),
+                                                       _ptr(taps), 0 if taps is None else len(taps) - 1, _ptr(out)))
     return out

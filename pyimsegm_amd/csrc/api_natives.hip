@@ -130,6 +130,152 @@ int imsegm_ray_features_binary2d(imsegm_ctx *ctx, const int8_t *seg_binary, int 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// centre-candidate point descriptors (points.hip): label / probability histograms under concentric discs, ray features against a
+// set of border labels with the smoothing along the angle
+// ---------------------------------------------------------------------------------------------------
+static_assert(RING_MAX_BINS == IMSEGM_RING_MAX_BINS && RING_PROBA_MAX_DISCS == IMSEGM_RING_PROBA_MAX_DISCS, "LDS budgets of points.hip");
+// the arguments the two ring calls share; fills the squared radii
+static int ring_arguments(const char *who, int height, int width, const int32_t *positions, int n_positions, const int32_t *radii,
+                          int n_radii, int max_radii, std::vector<int32_t> &radii2)
+{
+    char msg[160];
+    if (!positions || !radii || height < 1 || width < 1 || n_positions < 0 || n_radii < 1) {
+        snprintf(msg, sizeof(msg), "%s: bad arguments", who);
+        set_error(msg);
+        return -1;
+    }
+    if (n_radii > max_radii) {
+        snprintf(msg, sizeof(msg), "%s: %d discs exceed the LDS budget of the kernel (%d)", who, n_radii, max_radii);
+        set_error(msg);
+        return -1;
+    }
+    radii2.resize(n_radii);
+    for (int d = 0; d < n_radii; ++d) {
+        if (radii[d] < 0 || radii[d] > RING_MAX_RADIUS || (d && radii[d] <= radii[d - 1])) {
+            snprintf(msg, sizeof(msg), "%s: radii must grow strictly within 0 .. %d", who, RING_MAX_RADIUS);
+            set_error(msg);
+            return -1;
+        }
+        radii2[d] = radii[d] * radii[d];
+    }
+    for (int p = 0; p < n_positions; ++p)
+        if (positions[2 * p] < 0 || positions[2 * p] >= height || positions[2 * p + 1] < 0 || positions[2 * p + 1] >= width) {
+            snprintf(msg, sizeof(msg), "%s: position %d lies outside the map", who, p);
+            set_error(msg);
+            return -1;
+        }
+    return 0;
+}
+
+int imsegm_ring_hist2d(imsegm_ctx *ctx, const int16_t *segm, int height, int width, const int32_t *positions, int n_positions,
+                       const int32_t *radii, int n_radii, int nb_labels, uint32_t *hist_out, uint32_t *size_out)
+{
+    if (bind(ctx)) return -1;
+    std::vector<int32_t> radii2;
+    if (!segm || !hist_out || !size_out || nb_labels < 1) {
+        set_error("ring_hist2d: bad arguments");
+        return -1;
+    }
+    if (ring_arguments("ring_hist2d", height, width, positions, n_positions, radii, n_radii, RING_MAX_BINS, radii2)) return -1;
+    if ((long long)n_radii * ((long long)nb_labels + 1) > RING_MAX_BINS) {
+        set_error("ring_hist2d: n_radii * (nb_labels + 1) exceeds the LDS budget of the kernel (IMSEGM_RING_MAX_BINS)");
+        return -1;
+    }
+    if (n_positions == 0) return 0;                        // empty tables, no launch
+    hipStream_t st = ctx->stream;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t P = n_positions, D = n_radii;
+    const size_t b_seg = al((size_t)height * width * 2), b_pos = al(P * 8), b_rad = al(D * 4), b_hist = al(P * D * nb_labels * 4);
+    const size_t b_size = al(P * D * 4);
+    unsigned char *dev;
+    if (ctx_scratch(ctx, b_seg + b_pos + b_rad + b_hist + b_size, &dev)) return -1;
+    HIP_TRY(hipMemcpyAsync(dev, segm, (size_t)height * width * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + b_seg, positions, P * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + b_seg + b_pos, radii2.data(), D * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                     // (pageable sources: the host buffers are free again)
+    unsigned int *d_hist = reinterpret_cast<unsigned int *>(dev + b_seg + b_pos + b_rad);
+    unsigned int *d_size = reinterpret_cast<unsigned int *>(dev + b_seg + b_pos + b_rad + b_hist);
+    if (launch_ring_hist2d(reinterpret_cast<int16_t *>(dev), height, width, reinterpret_cast<int32_t *>(dev + b_seg), n_positions,
+                           reinterpret_cast<int32_t *>(dev + b_seg + b_pos), n_radii, radii[n_radii - 1], nb_labels, d_hist, d_size, st))
+        return -1;
+    HIP_TRY(hipMemcpyAsync(hist_out, d_hist, P * D * nb_labels * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(size_out, d_size, P * D * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int imsegm_ring_hist_proba2d(imsegm_ctx *ctx, const double *proba, int height, int width, int n_layers, const int32_t *positions,
+                             int n_positions, const int32_t *radii, int n_radii, double *sum_out, uint32_t *size_out)
+{
+    if (bind(ctx)) return -1;
+    std::vector<int32_t> radii2;
+    if (!proba || !sum_out || !size_out || n_layers < 1 || n_layers > 65535) {
+        set_error("ring_hist_proba2d: bad arguments (1 .. 65535 layers)");
+        return -1;
+    }
+    if (ring_arguments("ring_hist_proba2d", height, width, positions, n_positions, radii, n_radii, RING_PROBA_MAX_DISCS, radii2))
+        return -1;
+    if (n_positions == 0) return 0;
+    hipStream_t st = ctx->stream;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t P = n_positions, D = n_radii, C = n_layers, n_in = (size_t)height * width * C * 8;
+    const size_t b_seg = al(n_in), b_pos = al(P * 8), b_rad = al(D * 4), b_sum = al(P * D * C * 8), b_size = al(P * D * 4);
+    unsigned char *dev;
+    if (ctx_scratch(ctx, b_seg + b_pos + b_rad + b_sum + b_size, &dev)) return -1;
+    HIP_TRY(hipMemcpyAsync(dev, proba, n_in, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + b_seg, positions, P * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + b_seg + b_pos, radii2.data(), D * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double *d_sum = reinterpret_cast<double *>(dev + b_seg + b_pos + b_rad);
+    unsigned int *d_size = reinterpret_cast<unsigned int *>(dev + b_seg + b_pos + b_rad + b_sum);
+    if (launch_ring_hist_proba2d(reinterpret_cast<double *>(dev), height, width, n_layers, reinterpret_cast<int32_t *>(dev + b_seg),
+                                 n_positions, reinterpret_cast<int32_t *>(dev + b_seg + b_pos), n_radii, radii[n_radii - 1], d_sum,
+                                 d_size, st))
+        return -1;
+    HIP_TRY(hipMemcpyAsync(sum_out, d_sum, P * D * C * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(size_out, d_size, P * D * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int imsegm_ray_features_labels2d(imsegm_ctx *ctx, const int32_t *segm, int height, int width, const int32_t *border_labels,
+                                 int n_border, const int32_t *positions, int n_positions, const float *directions, int n_angles,
+                                 int edge, const double *smooth_taps, int smooth_radius, float *ray_dist_out)
+{
+    if (bind(ctx)) return -1;
+    if (!segm || !positions || !directions || !ray_dist_out || height < 1 || width < 1 || n_positions < 0 || n_angles < 1 ||
+        n_angles > IMSEGM_RAY_MAX_ANGLES || n_border < 0 || n_border > IMSEGM_RAY_MAX_BORDER_LABELS || (n_border && !border_labels) ||
+        (edge != 1 && edge != -1) || smooth_radius < 0 || smooth_radius > (1 << 20)) {
+        set_error("ray_features_labels2d: bad arguments (edge is 1 = up or -1 = down; at most IMSEGM_RAY_MAX_ANGLES angles and "
+                  "IMSEGM_RAY_MAX_BORDER_LABELS border labels)");
+        return -1;
+    }
+    if (n_positions == 0) return 0;
+    hipStream_t st = ctx->stream;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t P = n_positions, A = n_angles, T = smooth_taps ? (size_t)smooth_radius + 1 : 0;
+    const size_t b_seg = al((size_t)height * width * 4), b_lab = al((size_t)n_border * 4 + 8), b_pos = al(P * 8), b_dir = al(A * 8);
+    const size_t b_tap = al(T * 8 + 8), b_out = al(P * A * 4);
+    unsigned char *dev;
+    if (ctx_scratch(ctx, b_seg + b_lab + b_pos + b_dir + b_tap + b_out, &dev)) return -1;
+    unsigned char *d_lab = dev + b_seg, *d_pos = d_lab + b_lab, *d_dir = d_pos + b_pos, *d_tap = d_dir + b_dir, *d_out = d_tap + b_tap;
+    HIP_TRY(hipMemcpyAsync(dev, segm, (size_t)height * width * 4, hipMemcpyHostToDevice, st));
+    if (n_border) HIP_TRY(hipMemcpyAsync(d_lab, border_labels, (size_t)n_border * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pos, positions, P * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_dir, directions, A * 8, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(d_tap, smooth_taps, T * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (launch_ray_features_labels2d(reinterpret_cast<int32_t *>(dev), height, width, reinterpret_cast<int32_t *>(d_lab), n_border,
+                                     reinterpret_cast<int32_t *>(d_pos), n_positions, reinterpret_cast<float *>(d_dir), n_angles, edge,
+                                     T ? reinterpret_cast<double *>(d_tap) : nullptr, smooth_radius, reinterpret_cast<float *>(d_out),
+                                     st))
+        return -1;
+    HIP_TRY(hipMemcpyAsync(ray_dist_out, d_out, P * A * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 
 // ---------------------------------------------------------------------------------------------------
 // 'median' and 'meanGrad' statistics on the resident image / volume and label map

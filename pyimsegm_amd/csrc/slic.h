@@ -284,6 +284,19 @@ int launch_label_hist2d(const int16_t *segm, int H, int W, const int32_t *window
 int launch_ray_features_binary2d(const int8_t *seg, int H, int W, const int32_t *positions, int P, const float *grad, int A, int edge,
                                  float *out, hipStream_t st);
 
+// points.hip -------------------------------------------------------------------------------------
+// LDS budgets of the ring kernels: one column of counters per lane and bin (32 bins x 256 lanes x 4 B = 32 KB), one column of
+// float64 sums and counts per lane and disc (16 discs x 256 lanes x 12 B = 48 KB)
+constexpr int RING_MAX_BINS = 32;           // n_radii * (nb_labels + 1) of launch_ring_hist2d
+constexpr int RING_PROBA_MAX_DISCS = 16;    // n_radii of launch_ring_hist_proba2d
+constexpr int RING_MAX_RADIUS = 16384;      // (2 r + 1)^2 pixels and 2 r^2 stay inside int32
+int launch_ring_hist2d(const int16_t *segm, int H, int W, const int32_t *positions, int P, const int32_t *radii2, int D, int rmax,
+                       int nb_labels, unsigned int *hist, unsigned int *size, hipStream_t st);
+int launch_ring_hist_proba2d(const double *proba, int H, int W, int C, const int32_t *positions, int P, const int32_t *radii2, int D,
+                             int rmax, double *sum, unsigned int *size, hipStream_t st);
+int launch_ray_features_labels2d(const int32_t *segm, int H, int W, const int32_t *border, int n_border, const int32_t *positions,
+                                 int P, const float *grad, int A, int edge, const double *taps, int radius, float *out, hipStream_t st);
+
 // graphcut.hip ------------------------------------------------------------------------------------
 struct GcProblem {
     int K, C, E;            // E: number of edges, or their capacity when E_dev is given

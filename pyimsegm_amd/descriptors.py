@@ -810,3 +810,219 @@ def compute_ray_features_segm_2d(seg_binary, position, angle_step=5., smooth_coe
     if smooth_coef is not None and smooth_coef > 0:
         ray_dist = ndimage.gaussian_filter1d(ray_dist, smooth_coef)
     return ray_dist
+
+
+# ------------------------------------------------------------------------------------------------
+# centre-candidate point descriptors (reference descriptors.py:1288-1369, :1498-1528, :1761-1895): label histograms in
+# concentric rings and ray features against border labels, one launch for all positions (csrc/points.hip)
+# ------------------------------------------------------------------------------------------------
+
+
+def _disc(radius):
+    """``skimage.morphology.disk(radius)``: 1 where dy^2 + dx^2 <= radius^2 on the (2 radius + 1)^2 grid"""
+    axis = np.arange(-radius, radius + 1)
+    return np.array(axis[:, None] ** 2 + axis[None, :] ** 2 <= radius ** 2, dtype=np.uint8)
+
+
+def _positions_inside(positions, shape):
+    return bool(np.all((positions >= 0) & (positions < np.asarray(shape[:2]))))
+
+
+def _device_radii(diameters):
+    """the radii as the ring kernels take them (sorted, distinct) and the place of every given radius among them; None when the
+    radii are not integers the kernels accept"""
+    radii = np.asarray(diameters)
+    if radii.ndim != 1 or radii.dtype.kind not in 'iu' or len(radii) == 0 or radii.min() < 0 or radii.max() > 16384:
+        return None
+    return np.unique(radii, return_inverse=True)
+
+
+def _disc_label_hists(segm, positions, diameters, nb_labels):
+    """label counts P x D x nb_labels under the discs and the sizes P x D of the clipped discs, both float64 of exact integers"""
+    if segm.dtype.kind == 'f':
+        segm = np.where(np.isnan(segm), -1, segm)                 # NaN marks "no label" (descriptors.py:1490)
+    device = _device_radii(diameters) if _positions_inside(positions, segm.shape) else None
+    if device is not None and len(device[0]) * (int(nb_labels) + 1) <= _hip.RING_MAX_BINS:
+        hist, size = _hip.ring_hist2d(segm, positions, device[0], nb_labels)
+        return hist[:, device[1], :].astype(float), size[:, device[1]].astype(float)
+    # more counters than a lane's LDS columns hold (DESIGN.md, "Point descriptors"), radii that are no integers, or a position
+    # outside the map: one batched launch per disc
+    per_disc = [compute_label_hist_positions(segm, positions, _disc(d), nb_labels) for d in diameters]
+    return np.stack([h for h, _ in per_disc], axis=1), np.stack([s for _, s in per_disc], axis=1)
+
+
+def _disc_layer_sums(segm, positions, diameters):
+    """layer sums P x D x C under the discs (float64) and the sizes P x D of the clipped discs"""
+    device = _device_radii(diameters) if _positions_inside(positions, segm.shape) else None
+    if device is None:
+        per_pos = [[compute_label_hist_proba(segm, pos, _disc(d)) for d in diameters] for pos in positions]
+        return (np.array([[h for h, _ in row] for row in per_pos], dtype=float).reshape(len(positions), len(diameters), segm.shape[-1]),
+                np.array([[s for _, s in row] for row in per_pos], dtype=float).reshape(len(positions), len(diameters)))
+    radii, place = device
+    sums, sizes = [], []
+    for first in range(0, len(radii), _hip.RING_PROBA_MAX_DISCS):   # the discs of a launch are complete on their own
+        total, size = _hip.ring_hist_proba2d(segm, positions, radii[first:first + _hip.RING_PROBA_MAX_DISCS])
+        sums.append(total)
+        sizes.append(size)
+    return np.concatenate(sums, axis=1)[:, place, :], np.concatenate(sizes, axis=1)[:, place].astype(float)
+
+
+def compute_label_hist_proba(segm, position, struc_elem):
+    """ sums of the layers of ``segm`` (H x W x C, one layer per label) under ``struc_elem`` around ``position`` and the size of
+    the clipped element (reference ``descriptors.py:1498-1528``)
+
+    A single position under an arbitrary element is numpy on the host, as in the reference; the discs of
+    :func:`compute_label_histograms_positions` are summed on the device for all positions at once.
+
+    >>> seg = np.zeros((50, 50, 2), dtype=float)
+    >>> seg[15:35, 20:40, 1] = 1
+    >>> seg[:, :, 0] = 1 - seg[:, :, 1]
+    >>> hist, size = compute_label_hist_proba(seg, (15, 20), np.ones((12, 13), dtype=int))
+    >>> hist.tolist(), int(size)
+    ([114.0, 42.0], 156)
+    """
+    segm, struc_elem = np.asarray(segm), np.asarray(struc_elem)
+    if segm.ndim != (len(position) + 1):
+        raise ValueError('segment. (%r) should have larger (+1) dim than position %i' % (segm.shape, len(position)))
+    position = [int(p) for p in position]
+    im_begin, im_end, bb_begin, bb_end = adjust_bounding_box_crop(segm.shape[:struc_elem.ndim], struc_elem.shape, position)
+    crop = segm[im_begin[0]:im_end[0], im_begin[1]:im_end[1], :]
+    elem = struc_elem[bb_begin[0]:bb_end[0], bb_begin[1]:bb_end[1]]
+    if crop.shape[:-1] != elem.shape:
+        raise ValueError('initial dim of segmentation %r should match element %r' % (crop.shape, elem))
+    layers = np.rollaxis(crop, -1, 0) * np.tile(elem, (crop.shape[-1], 1, 1))
+    return np.sum(layers, axis=(1, 2)), np.sum(elem)
+
+
+def compute_label_histograms_positions(segm, positions, diameters=HIST_CIRCLE_DIAGONALS, nb_labels=None):
+    """ label histograms in consecutive rings around the positions (reference ``descriptors.py:1288-1369``)
+
+    Ring d lies between the discs ``skimage.morphology.disk(diameters[d - 1])`` and ``disk(diameters[d])`` (the reference hands
+    its "diameters" to ``disk`` as radii), clipped to the map; its value per label is the difference of the two discs' counts
+    over the difference of their sizes.  For a label map ``segm`` (H x W) the counts, for probability layers (H x W x C) the
+    float64 sums of all positions and discs come from ONE launch that reads every window once (``imsegm_ring_hist2d`` /
+    ``imsegm_ring_hist_proba2d``); the division is float64 on the host.
+
+    :param ndarray segm: H x W labels or H x W x C layers
+    :param list(tuple(int,int)) positions: (row, col)
+    :param list(int) diameters: radii of the discs
+    :param int nb_labels: number of labels (the maximum + 1, or C)
+    :return tuple(ndarray,list(str)): features P x (D * nb_labels), names 'hist-d_%i-lb_%i'
+    """
+    segm = np.asarray(segm)
+    pos_dim = np.asarray(positions).shape[1]
+    if (segm.ndim - pos_dim) not in (0, 1):
+        raise ValueError('dimension %r and %r difference should be 0 or 1' % (segm.ndim, pos_dim))
+    if pos_dim != 2:
+        raise ValueError('positions have to be (row, col), not %r values' % pos_dim)
+    layers = segm.ndim == pos_dim + 1
+    if nb_labels is None:
+        nb_labels = segm.shape[-1] if layers else segm.max() + 1
+    diameters = list(diameters)
+    # int(p) of the reference: towards zero
+    points = np.array([[int(p) for p in pos] for pos in positions], dtype=np.int64).reshape(-1, 2)
+    if layers:
+        hist, size = _disc_layer_sums(segm, points, diameters)
+    else:
+        hist, size = _disc_label_hists(segm, points, diameters, int(nb_labels))
+    # the rings, with the two checks of the reference's loop at the first position and disc that fails one
+    hist_last = np.concatenate([np.zeros_like(hist[:, :1]), hist[:, :-1]], axis=1)
+    inter_size = size - np.concatenate([np.zeros_like(size[:, :1]), size[:, :-1]], axis=1)
+    empty, shrinks = inter_size <= 0, ~np.all(hist >= hist_last, axis=2)
+    if np.any(empty | shrinks):
+        pos, disc = np.unravel_index(np.argmax(empty | shrinks), empty.shape)
+        if empty[pos, disc]:
+            raise ValueError('norm or element should be positive')
+        raise ValueError('outer elem should have more labels %r then the inter %r'
+                         % (hist[pos, disc].tolist(), hist_last[pos, disc].tolist()))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        pos_hists = ((hist - hist_last) / inter_size[:, :, None]).reshape(len(points), hist.shape[1] * hist.shape[2])
+    feature_names = ['hist-d_%i-lb_%i' % (d, lb) for d in diameters for lb in range(nb_labels)]
+    if pos_hists.shape[1] != len(feature_names):
+        raise ValueError('histogram: %r and names %r' % (pos_hists.shape, feature_names))
+    return pos_hists, feature_names
+
+
+def shift_ray_features(ray_dist, method='phase'):
+    """ rotate ray features to start at their main direction (reference ``descriptors.py:1761-1802``): the phase of the strongest
+    component of the spectrum of five periods (``method='phase'``), or the maximum; numpy on the host (an FFT of 5 A points)
+
+    >>> vec = np.array([43, 46, 44, 39, 28, 18, 12, 10,  9, 12, 22, 28])
+    >>> ray, shift = shift_ray_features(vec)
+    >>> ray.tolist(), round(float(shift), 1)
+    ([46, 44, 39, 28, 18, 12, 10, 9, 12, 22, 28, 43], 41.5)
+
+    :return tuple(ndarray,float): the rotated features, the shift in degrees
+    """
+    ray_dist = np.asarray(ray_dist)
+    angle_step = 360 / len(ray_dist)
+    if method == 'phase':
+        periods = np.hstack([ray_dist] * 5)
+        spectrum = np.fft.fft(periods - np.mean(periods)) / float(len(periods))
+        strongest = np.argmax(np.abs(spectrum)[:len(periods) // 2])
+        shift = np.rad2deg(-np.angle(spectrum)[:len(periods) // 2][strongest])
+        shift = (360 + shift) if shift < 0 else shift
+    else:
+        shift = float(np.argmax(ray_dist) * angle_step)
+    steps = int(round(shift / angle_step))
+    return np.array(ray_dist[steps:].tolist() + ray_dist[:steps].tolist()), shift
+
+
+def _border_table(segm, border_labels):
+    """the label map and the label table ``imsegm_ray_features_labels2d`` takes; a map that int32 does not hold exactly, or more
+    labels than the table has room for: the mask, formed on the host, against the table [1]"""
+    if segm.dtype.kind in 'iub' and len(border_labels) <= _hip.RAY_MAX_BORDER_LABELS:
+        info = np.iinfo(np.int32)
+        if segm.dtype.itemsize <= 2 or segm.dtype == np.int32 or (segm.size and info.min <= segm.min() and segm.max() <= info.max):
+            return segm, [int(lb) for lb in border_labels if lb == int(lb) and info.min <= lb <= info.max]
+    return np.isin(segm, list(border_labels)), [1]
+
+
+def compute_ray_features_positions(segm, list_positions, angle_step=5., border_labels=None, segm_open=None, smooth_ray=None,
+                                   shifting=True, edge='up'):
+    """ ray features of many positions against the labels ``border_labels`` (reference ``descriptors.py:1805-1895``)
+
+    One launch (``imsegm_ray_features_labels2d``) serves all positions: the mask ``segm in border_labels`` is formed on the device
+    from the label table, the rays are walked as ``computeRayFeaturesBinary2d`` walks them, and ``smooth_ray`` is
+    ``scipy.ndimage.gaussian_filter1d`` along the angle, in the same kernel.  What stays on the host: ``np.argmax`` over the layers
+    of an H x W x C ``segm``; the phase shift (:func:`shift_ray_features`, row by row); and ``segm_open``, which is not moved to
+    the device -- the mask is formed and opened with ``skimage.morphology.opening`` on the host (imported only then, as in the
+    reference) before the upload.
+
+    :param ndarray segm: H x W labels or H x W x C layers
+    :param list(tuple(int,int)) list_positions: (row, col)
+    :param float angle_step: degrees between two rays
+    :param list(int) border_labels: the labels the rays stop at, [0] by default
+    :param int segm_open: radius of the disc the mask is opened with
+    :param float smooth_ray: sigma of the smoothing along the angle
+    :param bool shifting: rotate every row to its main phase
+    :param str edge: 'up' or 'down'
+    :return tuple(ndarray,list(float),list(str)): distances P x A, shifts, names 'ray-lb_%s-agl_%i'
+    """
+    logging.debug('compute Ray features with border label=%r and angle step=%f', border_labels, angle_step)
+    segm = np.asarray(segm)
+    pos_dim = np.asarray(list_positions).shape[1]
+    if (segm.ndim - pos_dim) not in (0, 1):
+        raise ValueError('dimension %s and %s difference should be 0 or 1' % (segm.ndim, pos_dim))
+    border_labels = border_labels if border_labels is not None else [0]
+    if segm.ndim > pos_dim:
+        segm = np.argmax(segm, axis=-1)
+    if segm.ndim != pos_dim:
+        raise ValueError('Segmentation dim of %r and position (%i) does not match' % (segm.ndim, pos_dim))
+    if pos_dim != 2:
+        raise ValueError('positions have to be (row, col), not %r values' % pos_dim)
+    if isinstance(segm_open, int):
+        from skimage import morphology
+        segm, table = morphology.opening(np.isin(segm, list(border_labels)), morphology.disk(segm_open)), [1]
+    else:
+        segm, table = _border_table(segm, border_labels)
+    points = np.array([[int(p) for p in pos] for pos in list_positions], dtype=np.int64).reshape(-1, 2)
+    taps = _hip.gaussian_taps(smooth_ray) if smooth_ray is not None and smooth_ray > 0 else None
+    rays = _hip.ray_features_labels2d(segm, table, points, _ray_directions(float(angle_step)), {'down': -1, 'up': 1}[edge], taps)
+    pos_shift = [0.] * len(rays)
+    if shifting and len(rays):
+        shifted = [shift_ray_features(row) for row in rays]
+        rays, pos_shift = np.array([row for row, _ in shifted]), [float(shift) for _, shift in shifted]
+    feature_names = ['ray-lb_%s-agl_%i' % (''.join(map(str, border_labels)), int(a))
+                     for a in np.linspace(0, 360 - angle_step, rays.shape[1])]
+    return rays, pos_shift, feature_names
