@@ -245,6 +245,14 @@ IMSEGM_API int imsegm_volume_slic(imsegm_image2d *vol, int n_segments, double co
                                   int radius_z, const double *taps_y, int radius_y, const double *taps_x, int radius_x,
                                   const double *spacing, int max_iter, int enforce_connectivity, double min_size_factor,
                                   double max_size_factor, int start_label, int *n_labels_out);
+/* inspection for the parity tests: the state of the last imsegm_volume_slic (an error before the first one).
+ * get_pre: the pre-processed plane [D][H][W] in the type the SLIC kernels read it -- *dtype_out = IMSEGM_F32 for a float32 volume,
+ *   IMSEGM_F64 for every other -- and, for the latter, *premax_out = max |value| of the plane as the device reduced it (what fixes the
+ *   fixed-point format of the centroid sums; 0 for a float32 volume, which has none).  plane_out NULL: only the type is reported.
+ * get_centroids: the centroid table, *n_centroids_out rows of (z, y, x, value) in the same type.  centroids_out NULL: only type and
+ *   count.  The table is what the last centroid UPDATE left: max_iter sweeps are followed by max_iter - 1 updates. */
+IMSEGM_API int imsegm_volume_get_pre(imsegm_image2d *vol, void *plane_out, int *dtype_out, double *premax_out);
+IMSEGM_API int imsegm_volume_get_centroids(imsegm_image2d *vol, void *centroids_out, int *dtype_out, int *n_centroids_out);
 /* Replaces skimage.measure.label(segments) (imsegm/superpixels.py:111): components of equal non-zero
  * value under full connectivity, numbered 1.. in raster order of their first voxel; 0 stays background.
  * (On the map imsegm_volume_slic has just written with enforce_connectivity -- every value > 0 one connected set -- this is a

@@ -145,6 +145,8 @@ _SIGNATURES = {
     'imsegm_volume_upload': (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double]),
     'imsegm_volume_slic': (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                      C.c_int, C.c_double, C.c_double, C.c_int, _ip]),
+    'imsegm_volume_get_pre': (C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_double)]),
+    'imsegm_volume_get_centroids': (C.c_int, [_vp, _vp, _ip, _ip]),
     'imsegm_volume_label_cc': (C.c_int, [_vp, _ip]),
     'imsegm_volume_gray_stats': (C.c_int, [_vp, _vp, _vp, _vp]),
     'imsegm_volume_graph': (C.c_int, [_vp, _vp, C.c_int, _ip, _vp, _vp]),
@@ -1158,6 +1160,31 @@ class Volume3D(Image2D):
             C.byref(n_out)))
         self.n_labels = n_out.value
         return self.n_labels
+
+    def get_pre_scalar(self):
+        """(inspection for the parity tests) (plane, premax) of the last ``slic``: the pre-processed D x H x W plane in the type the
+        SLIC kernels read it -- float32 for a float32 volume, float64 for every other -- and the device's max |value| of a float64
+        plane (None for a float32 one)"""
+        lib = load_library()
+        code, premax = C.c_int(-1), C.c_double(0.)
+        _check(lib.imsegm_volume_get_pre(self._h, None, C.byref(code), None))
+        out = np.empty(self.shape, dtype=np.float32 if code.value == F32 else np.float64)
+        _check(lib.imsegm_volume_get_pre(self._h, _ptr(out), C.byref(code), C.byref(premax)))
+        return out, (None if code.value == F32 else premax.value)
+
+    def get_pre(self):
+        """(inspection for the parity tests) the pre-processed plane of the last ``slic`` (see ``get_pre_scalar``)"""
+        return self.get_pre_scalar()[0]
+
+    def get_centroids(self):
+        """(inspection for the parity tests) K x 4 centroid table (z, y, x, value) of the last ``slic``, float32 for a float32
+        volume and float64 otherwise: what the last centroid update left (no update follows the last sweep)"""
+        lib = load_library()
+        code, count = C.c_int(-1), C.c_int(0)
+        _check(lib.imsegm_volume_get_centroids(self._h, None, C.byref(code), C.byref(count)))
+        out = np.empty((count.value, 4), dtype=np.float32 if code.value == F32 else np.float64)
+        _check(lib.imsegm_volume_get_centroids(self._h, _ptr(out), C.byref(code), C.byref(count)))
+        return out
 
     def label_cc(self):
         """``skimage.measure.label`` of the current label map, in place; returns max label + 1"""

@@ -168,11 +168,58 @@ int imsegm_volume_slic(imsegm_image2d *im, int n_segments, double compactness, c
         HIP_TRY(hipMemcpyAsync(im->labels.p, im->nearest.p, n * 4, hipMemcpyDeviceToDevice, st));
     }
     ctx->end(sp_all);
+    im->vol_pre_dtype = f32 ? IMSEGM_F32 : IMSEGM_F64;
+    im->vol_K = K;
     im->n_labels = n_labels;
     im->have_labels = true;
     im->labels_connected = enforce_connectivity != 0;
     im->graph_ready = false;
     if (n_labels_out) *n_labels_out = n_labels;
+    return 0;
+}
+
+// inspection for the parity tests: what the SLIC kernels of the last imsegm_volume_slic read and left (host bookkeeping and copies
+// behind a stream synchronisation; nothing on the path of imsegm_volume_slic)
+static int vol_slic_state(imsegm_image2d *im)
+{
+    if (!im || bind(im->ctx)) return -1;
+    if (wrong_kind(im, true)) return -1;
+    if (im->vol_pre_dtype < 0) {
+        set_error("slic has not been run");
+        return -1;
+    }
+    return 0;
+}
+
+int imsegm_volume_get_pre(imsegm_image2d *im, void *plane_out, int *dtype_out, double *premax_out)
+{
+    if (vol_slic_state(im)) return -1;
+    const bool f32 = im->vol_pre_dtype == IMSEGM_F32;
+    hipStream_t st = im->ctx->stream;
+    if (dtype_out) *dtype_out = im->vol_pre_dtype;
+    if (plane_out) HIP_TRY(hipMemcpyAsync(plane_out, im->labB.p, im->n * (f32 ? 4 : 8), hipMemcpyDeviceToHost, st));
+    if (premax_out) {
+        *premax_out = 0.0;              // (a float32 volume has none: its centroid sums are float32, not fixed point)
+        if (!f32) HIP_TRY(hipMemcpyAsync(premax_out, im->small.as<unsigned char>() + 64, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int imsegm_volume_get_centroids(imsegm_image2d *im, void *centroids_out, int *dtype_out, int *n_centroids_out)
+{
+    if (vol_slic_state(im)) return -1;
+    const bool f32 = im->vol_pre_dtype == IMSEGM_F32;
+    const size_t K = (size_t)im->vol_K;
+    if (dtype_out) *dtype_out = im->vol_pre_dtype;
+    if (n_centroids_out) *n_centroids_out = im->vol_K;
+    if (centroids_out) {
+        // the layout imsegm_volume_slic gave `vol_cent`: cen (K x 4 double) | acc (K x 6 int64) | win (K x 6 int) | cen32 (K x 4 float)
+        const unsigned char *cb = im->vol_cent.as<unsigned char>();
+        const unsigned char *src = f32 ? cb + K * (4 * 8 + 6 * 8 + 6 * 4) : cb;
+        HIP_TRY(hipMemcpyAsync(centroids_out, src, K * 4 * (f32 ? 4 : 8), hipMemcpyDeviceToHost, im->ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(im->ctx->stream));
     return 0;
 }
 

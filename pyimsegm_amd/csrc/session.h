@@ -175,6 +175,7 @@ struct imsegm_image2d {
     bool tex_ready = false;
     bool is_volume = false;
     double vol_off = 0.0, vol_scale = 1.0;      // intensity seen by the volume SLIC = (v + off) * scale
+    int vol_pre_dtype = -1, vol_K = 0;          // the last imsegm_volume_slic: type of its plane in labB (IMSEGM_F32 / IMSEGM_F64), centroids
     // tex_aux: scratch of the statistics of a Leung-Malik response (median, gradient) -- tex_planes / tex_resp stay as they are
     DevBuf img, labA, labB, nearest, labels, conn_i32, conn_u8, small, cent, tiles, feat, graph, gather_lut, gather_out_i, gather_out_f,
         tex_planes, tex_resp, tex_small, tex_aux, vol_cent, annot, hist, featK, seg, gseg, narrow;
