@@ -387,6 +387,18 @@ IMSEGM_API int imsegm_batch2d_device_ptr(imsegm_batch2d *batch, int image, int w
 IMSEGM_API int imsegm_image2d_median(imsegm_image2d *img, double *median_out);
 IMSEGM_API int imsegm_image2d_mean_gradient(imsegm_image2d *img, double *mean_out);
 
+/* The uploaded RGB image in another colour space, converted on the device as pyimsegm_amd/utilities/data_io.py states the
+ * conversions (skimage.color.rgb2hsv / rgb2luv / rgb2lab / rgb2hed / rgb2xyz of scikit-image 0.18 behind
+ * imsegm/utilities/data_io.py:28-58), NaN / inf replaced as np.nan_to_num does: a float64 interleaved H x W x 3 image in a
+ * buffer of the session.  space: 1 hsv, 2 luv, 3 lab, 4 hed, 5 xyz; matrix9: the row-major 3 x 3 stain matrix of hed
+ * (out = log-ratio @ matrix; NULL for the other spaces).  Enqueued on the session's stream, no synchronisation.
+ * From then on imsegm_image2d_color_stats, _features_color, _median and _mean_gradient read the CONVERTED image -- until a
+ * call with space 0 (which converts nothing) or the next upload; every other call (slic, lm_prepare, ...) keeps reading the
+ * upload.  Refused before the device is touched: no upload, a volume session, an unknown space, hed without a matrix. */
+IMSEGM_API int imsegm_image2d_convert_color(imsegm_image2d *img, int space, const double *matrix9);
+/* the converted image (H x W x 3 float64) to the host; one synchronisation */
+IMSEGM_API int imsegm_image2d_get_converted(imsegm_image2d *img, double *out_hw3);
+
 /* 1 when the uploaded image / volume holds no NaN and no inf (uint8: always).  The pipelines replace non-finite descriptor
  * values by zero (/root/reference/imsegm/pipelines.py:410 `features[np.isnan(features)] = 0`, descriptors.py:818), which the
  * resident statistics cannot reproduce from non-finite pixels: the host mirror asks before it takes the resident path (a

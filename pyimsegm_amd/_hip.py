@@ -74,6 +74,9 @@ class TermsDebug(C.Structure):
                 ('keep_soft_on_device', C.c_int), ('segm_u8', C.c_int), ('soft_f32', C.c_int)]
 
 
+#: colour spaces of ``imsegm_image2d_convert_color`` (0: back to the uploaded image)
+COLOR_SPACES = {'hsv': 1, 'luv': 2, 'lab': 3, 'hed': 4, 'xyz': 5}
+
 #: edge types of ``imsegm_image2d_segment``; 0x100 = divide by the relative centre distance (graph_cuts.py:647-650)
 EDGE_TYPES = {'': 0, 'const': 0, 'spatial': 1 | 0x100, 'model': 2 | 0x100, 'model_lT': 2, 'model_l1': 3, 'model_l2': 4,
               'features': 5 | 0x100}
@@ -152,6 +155,8 @@ _SIGNATURES = {
     'imsegm_volume_graph': (C.c_int, [_vp, _vp, C.c_int, _ip, _vp, _vp]),
     'imsegm_image2d_median': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_mean_gradient': (C.c_int, [_vp, _vp]),
+    'imsegm_image2d_convert_color': (C.c_int, [_vp, C.c_int, _vp]),
+    'imsegm_image2d_get_converted': (C.c_int, [_vp, _vp]),
     'imsegm_label_hist2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     'imsegm_ray_features_binary2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_ring_hist2d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
@@ -625,6 +630,24 @@ class Image2D(object):
         """per-label mean of ``np.sum(np.gradient(slice), axis=0)`` (stored in the image's dtype): K x 3 (K for a volume)"""
         out = np.empty((self.n_labels, 3) if len(self.shape) == 2 else (self.n_labels, ), dtype=np.float64)
         _check(load_library().imsegm_image2d_mean_gradient(self._h, _ptr(out)))
+        return out
+
+    def convert_color(self, space, matrix=None):
+        """convert the uploaded RGB image to a colour space on the device (``imsegm_image2d_convert_color``; no synchronisation)
+        and make the result what :meth:`color_stats`, :meth:`features_color`, :meth:`median` and :meth:`mean_gradient` read,
+        until ``convert_color(0)`` or the next upload.  ``space``: a name of :data:`COLOR_SPACES` or its code; ``matrix``: the
+        3 x 3 stain matrix of 'hed' (``data_io._HED_FROM_RGB``)"""
+        code = COLOR_SPACES[space] if isinstance(space, str) else int(space)
+        mat = None if matrix is None else np.ascontiguousarray(matrix, dtype=np.float64)
+        if mat is not None and mat.shape != (3, 3):
+            raise ValueError('the stain matrix must be 3 x 3')
+        _check(load_library().imsegm_image2d_convert_color(self._h, code, _ptr(mat)))
+        return self
+
+    def converted(self):
+        """the image of the last :meth:`convert_color` on the host: H x W x 3 float64"""
+        out = np.empty(tuple(self.shape[-2:]) + (3, ), dtype=np.float64)
+        _check(load_library().imsegm_image2d_get_converted(self._h, _ptr(out)))
         return out
 
     def features_color(self, mean=True, std=True, energy=True, to_host=True):

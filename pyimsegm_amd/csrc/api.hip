@@ -275,7 +275,7 @@ void imsegm_image2d_destroy(imsegm_image2d *im)
     DevBuf *all[] = { &im->img, &im->labA, &im->labB, &im->nearest, &im->labels, &im->conn_i32, &im->conn_u8, &im->small,
                       &im->cent, &im->tiles, &im->feat, &im->graph, &im->gather_lut, &im->gather_out_i, &im->gather_out_f,
                       &im->tex_planes, &im->tex_resp, &im->tex_small, &im->tex_aux, &im->vol_cent, &im->annot, &im->hist, &im->featK, &im->seg,
-                      &im->gseg, &im->narrow };
+                      &im->gseg, &im->narrow, &im->conv };
     for (auto b : all) b->release();
     if (im->slic_fail_host) (void)hipHostFree(im->slic_fail_host);
     if (im->slic_exec) (void)hipGraphExecDestroy(im->slic_exec);
@@ -299,6 +299,7 @@ int imsegm_image2d_upload(imsegm_image2d *im, const void *host_pixels, int dtype
     // the caller keeps the buffer untouched until the next call that synchronises (slic does)
     if (!is_pinned(host_pixels)) HIP_TRY(hipStreamSynchronize(im->ctx->stream));
     im->dtype = dtype;
+    im->conv_source = false;
     im->feat_mask = 0;
     im->place_F = 0;
     return 0;

@@ -148,12 +148,13 @@ int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *
     imsegm_ctx *ctx = im->ctx;
     hipStream_t st = ctx->stream;
     const int K = im->n_labels;
+    const StatSource src = stat_source(im);          // (a volume session never has a conversion)
     double maxabs = 255.0;
-    if (im->dtype != IMSEGM_U8) {
+    if (src.dtype != IMSEGM_U8) {
         if (ensure_small(im)) return -1;
         unsigned long long *keys = im->small.as<unsigned long long>();
         double *minmax = reinterpret_cast<double *>(keys + 2);
-        if (launch_minmax(im->img.p, im->dtype, im->is_volume ? im->n : im->n * 3, keys, minmax, st)) return -1;
+        if (launch_minmax(src.p, src.dtype, im->is_volume ? im->n : im->n * 3, keys, minmax, st)) return -1;
         double mm[2];
         HIP_TRY(hipMemcpyAsync(mm, minmax, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -167,10 +168,10 @@ int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *
     int rc;
     if (im->is_volume)      // the one-channel kernel on the gray plane (plane stride 0), the volume as a (D*H) x W image; its
                             // finalisation copies the gray statistics into all three channels: [m m m | s s s | e e e]
-        rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->D * im->H, im->W, K, maxabs, (feature_mask & 2) != 0,
+        rc = launch_color_stats(src.p, src.dtype, im->labels.as<int32_t>(), im->D * im->H, im->W, K, maxabs, (feature_mask & 2) != 0,
                                 ss.acc, ss.mean, ss.energy, ss.var, ss.mean32, st, 1, 0, 1.0, 1.0, 0);
     else
-        rc = launch_color_stats(im->img.p, im->dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, (feature_mask & 2) != 0, ss.acc,
+        rc = launch_color_stats(src.p, src.dtype, im->labels.as<int32_t>(), im->H, im->W, K, maxabs, (feature_mask & 2) != 0, ss.acc,
                                 ss.mean, ss.energy, ss.var, ss.mean32, st, 0, 0, 1.0, 1.0, -1);
     if (rc) return -1;
     const int F = color_feature_columns(feature_mask);

@@ -424,19 +424,20 @@ int imsegm_image2d_color_stats(imsegm_image2d *im, double *mean_out, double *ene
     }
     imsegm_ctx *ctx = im->ctx;
     hipStream_t st = ctx->stream;
+    const StatSource src = stat_source(im);
     double maxabs = 255.0;
-    if (im->dtype != IMSEGM_U8) {
+    if (src.dtype != IMSEGM_U8) {
         if (ensure_small(im)) return -1;
         unsigned long long *keys = im->small.as<unsigned long long>();
         double *minmax = reinterpret_cast<double *>(keys + 2);
-        if (launch_minmax(im->img.p, im->dtype, im->n * 3, keys, minmax, st)) return -1;
+        if (launch_minmax(src.p, src.dtype, im->n * 3, keys, minmax, st)) return -1;
         double mm[2];
         HIP_TRY(hipMemcpyAsync(mm, minmax, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         maxabs = std::max(fabs(mm[0]), fabs(mm[1]));
         if (!(maxabs < 1e300)) maxabs = 1e300;
     }
-    return stats_run(im, im->img.p, im->dtype, maxabs, 0, 0, 1.0, 1.0, mean_out, energy_out, var_out);
+    return stats_run(im, src.p, src.dtype, maxabs, 0, 0, 1.0, 1.0, mean_out, energy_out, var_out);
 }
 
 int imsegm_image2d_graph(imsegm_image2d *im, int32_t *edges_out, int edge_capacity, int *n_edges_out,

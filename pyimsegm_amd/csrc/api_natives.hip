@@ -289,12 +289,13 @@ int imsegm_image2d_median(imsegm_image2d *im, double *median_out)
     }
     hipStream_t st = im->ctx->stream;
     const int K = im->n_labels, C = im->is_volume ? 1 : 3;
+    const StatSource src = stat_source(im);
     const size_t sb = median_scratch_bytes(im->n, K), ob = (size_t)K * C * 8;
     if (im->tex_resp.ensure(sb + ob + 256)) return -1;              // (the response buffer of the LM bank doubles as scratch)
     im->tex_ready = false;
     double *d_out = im->tex_resp.as<double>();
     unsigned char *scratch = im->tex_resp.as<unsigned char>() + ((ob + 255) & ~(size_t)255);
-    if (launch_segment_median(im->img.p, im->dtype, C, C, 1, im->n, im->labels.as<int32_t>(), K, MedianNorm{ 0, 1.0, 1.0 }, scratch, sb,
+    if (launch_segment_median(src.p, src.dtype, C, C, 1, im->n, im->labels.as<int32_t>(), K, MedianNorm{ 0, 1.0, 1.0 }, scratch, sb,
                               d_out, st))
         return -1;
     HIP_TRY(hipMemcpyAsync(median_out, d_out, ob, hipMemcpyDeviceToHost, st));
@@ -316,16 +317,17 @@ int imsegm_image2d_mean_gradient(imsegm_image2d *im, double *mean_out)
     imsegm_ctx *ctx = im->ctx;
     hipStream_t st = ctx->stream;
     const int K = im->n_labels, C = im->is_volume ? 1 : 3;
-    const size_t es = im->dtype == IMSEGM_U8 ? 1 : im->dtype == IMSEGM_F32 ? 4 : 8;
+    const StatSource src = stat_source(im);
+    const size_t es = src.dtype == IMSEGM_U8 ? 1 : src.dtype == IMSEGM_F32 ? 4 : 8;
     if (im->tex_planes.ensure(im->n * C * es + 64)) return -1;      // gradient image, dtype of the source
     im->tex_ready = false;
-    if (launch_gradient_image(im->img.p, im->tex_planes.p, im->dtype, im->D, im->H, im->W, C, st)) return -1;
+    if (launch_gradient_image(src.p, im->tex_planes.p, src.dtype, im->D, im->H, im->W, C, st)) return -1;
     double maxabs = 255.0;
-    if (im->dtype != IMSEGM_U8) {
+    if (src.dtype != IMSEGM_U8) {
         if (ensure_small(im)) return -1;
         unsigned long long *keys = im->small.as<unsigned long long>();
         double *minmax = reinterpret_cast<double *>(keys + 2);
-        if (launch_minmax(im->tex_planes.p, im->dtype, im->n * C, keys, minmax, st)) return -1;
+        if (launch_minmax(im->tex_planes.p, src.dtype, im->n * C, keys, minmax, st)) return -1;
         double mm[2];
         HIP_TRY(hipMemcpyAsync(mm, minmax, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -337,12 +339,12 @@ int imsegm_image2d_mean_gradient(imsegm_image2d *im, double *mean_out)
     if (im->is_volume) {
         const int keepH = im->H;
         im->H = im->D * keepH;
-        rc = stats_run(im, im->tex_planes.p, im->dtype, maxabs, 1, 0, 1.0, 1.0, m.data(), nullptr, nullptr, 0);
+        rc = stats_run(im, im->tex_planes.p, src.dtype, maxabs, 1, 0, 1.0, 1.0, m.data(), nullptr, nullptr, 0);
         im->H = keepH;
         if (!rc)
             for (int k = 0; k < K; ++k) mean_out[k] = m[(size_t)k * 3];
     } else {
-        rc = stats_run(im, im->tex_planes.p, im->dtype, maxabs, 0, 0, 1.0, 1.0, m.data(), nullptr, nullptr);
+        rc = stats_run(im, im->tex_planes.p, src.dtype, maxabs, 0, 0, 1.0, 1.0, m.data(), nullptr, nullptr);
         if (!rc) memcpy(mean_out, m.data(), (size_t)K * 3 * 8);
     }
     return rc;

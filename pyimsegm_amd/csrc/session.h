@@ -178,7 +178,9 @@ struct imsegm_image2d {
     int vol_pre_dtype = -1, vol_K = 0;          // the last imsegm_volume_slic: type of its plane in labB (IMSEGM_F32 / IMSEGM_F64), centroids
     // tex_aux: scratch of the statistics of a Leung-Malik response (median, gradient) -- tex_planes / tex_resp stay as they are
     DevBuf img, labA, labB, nearest, labels, conn_i32, conn_u8, small, cent, tiles, feat, graph, gather_lut, gather_out_i, gather_out_f,
-        tex_planes, tex_resp, tex_small, tex_aux, vol_cent, annot, hist, featK, seg, gseg, narrow;
+        tex_planes, tex_resp, tex_small, tex_aux, vol_cent, annot, hist, featK, seg, gseg, narrow,
+        conv;                                   // the image in another colour space (colorspace.hip): float64 interleaved H x W x 3
+    bool conv_source = false;                   // `conv` is what the statistic entry points read (imsegm_image2d_convert_color)
     GraphPlan gplan;                            // the graph imsegm_image2d_graph_prepare has enqueued into `gseg` ...
     bool graph_ready = false;                   // ... for the current label map (any call that changes the labels clears this)
     int *slic_fail_host = nullptr;              // page-locked word the centroid update inside the assignment kernel raises when it hands the image back
@@ -198,6 +200,19 @@ inline int wrong_kind(const imsegm_image2d *im, bool want_volume)
         return 1;
     }
     return 0;
+}
+
+// The image the statistic entry points (color_stats, features_color, median, mean_gradient) read: the uploaded one, or its
+// conversion to another colour space while imsegm_image2d_convert_color has made that the source.  Everything else (SLIC,
+// lm_prepare, ...) reads the upload.
+struct StatSource {
+    const void *p;
+    int dtype;
+};
+inline StatSource stat_source(const imsegm_image2d *im)
+{
+    if (im->conv_source) return { im->conv.p, IMSEGM_F64 };
+    return { im->img.p, im->dtype };
 }
 
 extern std::atomic<bool> g_runtime_started;      // a HIP call has been made through this library (imsegm_init is too late); api.hip

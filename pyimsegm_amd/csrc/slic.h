@@ -278,6 +278,13 @@ size_t median_scratch_bytes(size_t n, int K);
 int launch_segment_median(const void *img, int dtype, int C, size_t pix_stride, size_t chan_stride, size_t n, const int32_t *labels,
                           int K, MedianNorm norm, void *scratch, size_t scratch_bytes, double *out, hipStream_t st);
 
+// colorspace.hip ---------------------------------------------------------------------------------
+// RGB -> another colour space as utilities/data_io.py states it, NaN / inf replaced as np.nan_to_num does: src is the interleaved
+// H x W x 3 upload (n pixels), dst float64 in the same layout.  m: the 3 x 3 matrix of CS_HED, row major (out = t @ m)
+enum { CS_HSV = 1, CS_LUV = 2, CS_LAB = 3, CS_HED = 4, CS_XYZ = 5 };
+struct ColorMatrix { double m[9]; };
+int launch_convert_color(const void *src, int dtype, size_t n, int space, const ColorMatrix &matrix, double *dst, hipStream_t st);
+
 // natives.hip ------------------------------------------------------------------------------------
 int launch_label_hist2d(const int16_t *segm, int H, int W, const int32_t *windows, int P, const int16_t *selem, int SH, int SW,
                         int nb_labels, unsigned int *hist, hipStream_t st);

@@ -491,11 +491,32 @@ def _texture_on_device(feature_flags, filters):
     return set(feature_flags) <= set(NAMES_FEATURE_FLAGS) and all(len(f) <= 8 for f in filters)
 
 
-def resident_feature_groups(feature_flags):
+def _convert_on_device(image, convert_on):
+    """whether a 'color_<space>' group of ``image`` is converted on the device: asked for (``convert_on='device'``; ``'host'`` and
+    None are the numpy conversion) and the conversion of the uploaded pixels is the conversion the host would make -- uint8
+    images, and float images whose sum is finite (NaN / inf are replaced BEFORE the upload but AFTER the host's conversion);
+    planes of at least 2 x 2 (the mean gradient needs them)"""
+    if convert_on not in (None, 'host', 'device'):
+        raise ValueError('convert_on is %r, expected \'host\' or \'device\'' % (convert_on, ))
+    if convert_on != 'device':
+        return False
+    image = np.asarray(image)
+    return image.ndim == 3 and min(image.shape[:2]) >= 2 \
+        and (image.dtype == np.uint8 or bool(np.isfinite(image.sum(dtype=np.float64))))
+
+
+def _convert_session(sess, space):
+    """the session's uploaded RGB image converted to ``space`` on the device; its statistics read the result from now on"""
+    from pyimsegm_amd.utilities.data_io import _HED_FROM_RGB
+    return sess.convert_color(space, _HED_FROM_RGB if space == 'hed' else None)
+
+
+def resident_feature_groups(feature_flags, convert_on=None):
     """the descriptor groups of ``feature_flags`` in the column order of :func:`compute_selected_features_color2d` (the colour
     statistics, then the Leung-Malik ones) as ``[(kind, flags, batteries, columns)]`` when ALL of them can be formed and kept on
-    the device -- 'color' in RGB and 'tLM' / 'tLM_<bank>' with mean / std / energy; otherwise None (converted colour spaces,
-    median, meanGrad: the general path)"""
+    the device -- 'color' in RGB, with ``convert_on='device'`` also 'color_<space>' (``batteries`` is the name of the space then),
+    and 'tLM' / 'tLM_<bank>', each with mean / std / energy; otherwise None (median, meanGrad, colour spaces converted on the
+    host: the general path)"""
     order = [k for k in feature_flags if k.startswith('color')] + [k for k in feature_flags if k.startswith('tLM')]
     if not order or len(order) != len(feature_flags):
         return None
@@ -506,6 +527,8 @@ def resident_feature_groups(feature_flags):
             return None
         if key == 'color':
             groups.append(('color', flags, None, 3 * len(flags)))
+        elif convert_on == 'device' and key.startswith('color_') and key.split('_')[-1] in _hip.COLOR_SPACES:
+            groups.append(('color', flags, key.split('_')[-1], 3 * len(flags)))
         elif key == 'tLM' or key.startswith('tLM_'):
             filters, _ = _select_bank(key.split('_')[-1] if '_' in key else 'normal')
             if not _texture_on_device(flags, filters) or len({np.shape(f)[1:] for f in filters}) != 1:
@@ -524,7 +547,13 @@ def resident_feature_table(sess, groups):
     for kind, flags, filters, width in groups:
         sess.features_place(total, column)
         want = dict(mean='mean' in flags, std='std' in flags, energy='energy' in flags)
-        if kind == 'color':
+        if kind == 'color' and filters is not None:         # a colour space: converted where the RGB image already is
+            _convert_session(sess, filters)
+            try:
+                sess.features_color(to_host=False, **want)
+            finally:
+                sess.convert_color(0)
+        elif kind == 'color':
             sess.features_color(to_host=False, **want)
         else:
             if not prepared:
@@ -649,11 +678,13 @@ def compute_selected_features_gray2d(img, segments, features_flags=FEATURES_SET_
     return compute_selected_features_gray3d(img[None], segments[None], features_flags)
 
 
-def _selected_features_color2d(img, segments, feature_flags, sess=None):
-    """reference descriptors.py:1207-1270 with ONE device session for all groups that read the RGB image"""
+def _selected_features_color2d(img, segments, feature_flags, sess=None, convert_on=None):
+    """reference descriptors.py:1207-1270 with ONE device session for all groups that read the RGB image; with
+    ``convert_on='device'`` that includes the 'color_<space>' groups, whose conversion then runs on that session"""
     _three_channels(img)
     borrowed = sess is not None
     blocks, names = [], []
+    on_device = _convert_on_device(img, convert_on)
 
     def session():
         nonlocal sess
@@ -665,7 +696,14 @@ def _selected_features_color2d(img, segments, feature_flags, sess=None):
         for key, space in _groups(feature_flags, 'color'):
             if space is None:
                 part, part_names = _color_statistic_session(session(), img, segments, feature_flags[key], 'rgb')
-            else:           # a converted colour space: its own upload
+            elif on_device and space in _hip.COLOR_SPACES:
+                _convert_session(session(), space)
+                try:    # (the converted image is float64 on the device whatever the upload is: that is all the statistics ask of it)
+                    stand_in = np.broadcast_to(np.float64(0.), tuple(np.shape(img)[:2]) + (3, ))
+                    part, part_names = _color_statistic_session(sess, stand_in, segments, feature_flags[key], space)
+                finally:
+                    sess.convert_color(0)
+            else:           # a colour space converted on the host: its own upload
                 from pyimsegm_amd.utilities.data_io import convert_img_color_from_rgb
                 converted = np.nan_to_num(convert_img_color_from_rgb(img, space))
                 part, part_names = compute_image2d_color_statistic(converted, segments, feature_flags[key], color_name=space)
@@ -685,20 +723,26 @@ def _selected_features_color2d(img, segments, feature_flags, sess=None):
     return _side_by_side(blocks, names, feature_flags)
 
 
-def compute_selected_features_color2d(img, segments, feature_flags=FEATURES_SET_ALL):
+def compute_selected_features_color2d(img, segments, feature_flags=FEATURES_SET_ALL, convert_on=None):
     """ selected features of a colour 2D image (reference descriptors.py:1207-1270)
+
+    :param str convert_on: (not in the reference) where a 'color_<space>' group is converted from RGB: ``'host'`` (numpy, then
+        a second upload; the default) or ``'device'`` (on the session that holds the RGB image; last digits may differ)
     """
-    return _selected_features_color2d(np.asarray(img), np.asarray(segments), feature_flags)
+    return _selected_features_color2d(np.asarray(img), np.asarray(segments), feature_flags, convert_on=convert_on)
 
 
-def compute_selected_features_img2d(image, segm, features_flags=FEATURES_SET_COLOR):
-    """ by the kind of image: H x W x 3 colour or H x W gray (reference descriptors.py:1273-1285) """
+def compute_selected_features_img2d(image, segm, features_flags=FEATURES_SET_COLOR, convert_on=None):
+    """ by the kind of image: H x W x 3 colour or H x W gray (reference descriptors.py:1273-1285); ``convert_on``: see
+    :func:`compute_selected_features_color2d` (colour images only) """
     image, segm = np.asarray(image), np.asarray(segm)
     colour = image.ndim == 3 and image.shape[2] == 3
     if not colour and image.ndim != 2:
         logging.error('invalid image size - %r', image.shape)
         return None
-    return (compute_selected_features_color2d if colour else compute_selected_features_gray2d)(image, segm, features_flags)
+    if colour:
+        return compute_selected_features_color2d(image, segm, features_flags, convert_on=convert_on)
+    return compute_selected_features_gray2d(image, segm, features_flags)
 
 
 # ------------------------------------------------------------------------------------------------
