@@ -132,6 +132,9 @@ IMSEGM_API int imsegm_debug_slic_sweep_runs(long *persistent_runs_out, long *fal
  * k_alpha_expansion_grid) gave up -- a workgroup of its grid was not resident within the bounded wait of its barrier, e.g. on a GPU
  * shared with another process -- and the single workgroup cut again from scratch (results are identical). */
 IMSEGM_API long imsegm_debug_gc_grid_fallbacks(void);
+/* Diagnostic (no reference counterpart): the one-workgroup exclusive prefix sum that the labelling, graph and compaction stages share
+ * (csrc/scan.hip), on n host values: host_out[i] = host_in[0] + ... + host_in[i - 1], *total = the sum of all n (tests). */
+IMSEGM_API int imsegm_debug_exclusive_scan(const int32_t *host_in, int n, int32_t *host_out, int32_t *total);
 /* Replaces skimage.segmentation._slic._enforce_label_connectivity_cython(segments, min_size, max_size, start_label)
  * (scikit-image 0.18; the connectivity pass of skimage.segmentation.slic, reached from imsegm/superpixels.py:61-63 and
  * :104-106 with enforce_connectivity=True) on a label map given by the caller: labels = host int32, one value per

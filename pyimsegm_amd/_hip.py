@@ -118,6 +118,7 @@ _SIGNATURES = {
     'imsegm_debug_conn_general_runs': (C.c_long, []),
     'imsegm_debug_slic_sweep_runs': (C.c_int, [_vp, _vp]),
     'imsegm_debug_gc_grid_fallbacks': (C.c_long, []),
+    'imsegm_debug_exclusive_scan': (C.c_int, [_vp, C.c_int, _vp, _ip]),
     'imsegm_assume_bg_on_boundary': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _ip]),
     'imsegm_image2d_all_finite': (C.c_int, [_vp, _ip]),
     'imsegm_image2d_lm_features': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -1395,6 +1396,14 @@ class DeviceArray(object):
 def gc_grid_fallbacks():
     """grid-wide graph cuts of this process that gave up waiting for a workgroup and were redone by the single workgroup"""
     return int(load_library().imsegm_debug_gc_grid_fallbacks())
+
+
+def exclusive_scan(values):
+    """(exclusive prefix sums, total) of int32 `values` by the library's one-workgroup scan (csrc/scan.hip); for tests"""
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    out, total = np.empty_like(values), C.c_int(0)
+    _check(load_library().imsegm_debug_exclusive_scan(values.ctypes.data, values.size, out.ctypes.data, C.byref(total)))
+    return out, total.value
 
 
 def slic_sweep_runs():

@@ -317,6 +317,26 @@ int imsegm_debug_slic_sweep_runs(long *persistent_runs_out, long *fallback_runs_
     return 0;
 }
 
+int imsegm_debug_exclusive_scan(const int32_t *host_in, int n, int32_t *host_out, int32_t *total)
+{
+    if (n < 0 || !total || (n > 0 && (!host_in || !host_out))) {
+        set_error("exclusive_scan: n >= 0, and no null pointers");
+        return -1;
+    }
+    int32_t *dev = nullptr;                                    // n entries and, behind them, the total
+    HIP_TRY(hipMalloc(&dev, ((size_t)n + 1) * sizeof(int32_t)));
+    hipError_t e = n ? hipMemcpy(dev, host_in, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) {
+        launch_exclusive_scan(dev, n, dev + n, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && n) e = hipMemcpy(host_out, dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(total, dev + n, sizeof(int32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(dev);
+    HIP_TRY(e);
+    return 0;
+}
+
 // skimage.segmentation._slic._enforce_label_connectivity_cython(segments, min_size, max_size, start_label) -- the second
 // native call inside skimage.segmentation.slic (superpixels.py:61-63, enforce_connectivity=True) -- on a label map
 // given by the caller; the result becomes the session's label map.  2-D image sessions and volume sessions.

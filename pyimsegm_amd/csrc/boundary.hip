@@ -134,9 +134,9 @@ k_edt_rows(const uint32_t *__restrict__ g, int H, int W, const int *__restrict__
 
 // ---------------------------------------------------------------------------------------------------
 // stable compaction of the set pixels of a mask (row-major order is part of the result: a scan, no atomic append).
-// A workgroup owns CP_CHUNK consecutive pixels: k_compact_count counts them, k_compact_scan turns the counts into exclusive
-// offsets (one workgroup, chunks of 256 with a running carry) and leaves the total behind them, k_compact_gather writes
-// (row, column) and sqrt(d2) of every set pixel to its place.
+// A workgroup owns CP_CHUNK consecutive pixels: k_compact_count counts them, launch_exclusive_scan (scan.hip) turns the counts into
+// exclusive offsets and leaves the total behind them, k_compact_gather writes (row, column) and sqrt(d2) of every set pixel to its
+// place.
 // ---------------------------------------------------------------------------------------------------
 constexpr int CP_ITEMS = 8, CP_CHUNK = 256 * CP_ITEMS;
 
@@ -155,36 +155,6 @@ k_compact_count(const uint8_t *__restrict__ mask, size_t n, uint32_t *__restrict
     if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = (uint32_t)(s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3]);
-}
-
-// counts[0 .. nb) -> exclusive prefix sums in place, counts[nb] = total
-__global__ void __launch_bounds__(256)
-k_compact_scan(uint32_t *__restrict__ counts, int nb)
-{
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 256) {
-        const int i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? counts[i] : 0u;
-        uint32_t incl = v;                              // inclusive scan inside the wave
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < nb) counts[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[nb] = s_carry;
 }
 
 __global__ void __launch_bounds__(256)
@@ -263,7 +233,7 @@ int launch_compact_count(const uint8_t *mask, size_t n, uint32_t *counts, hipStr
 {
     const int nb = (int)(compact_count_words(n) - 1);
     hipLaunchKernelGGL(k_compact_count, nb, 256, 0, st, mask, n, counts);
-    hipLaunchKernelGGL(k_compact_scan, 1, 256, 0, st, counts, nb);
+    launch_exclusive_scan(counts, nb, counts + nb, st);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -190,43 +190,6 @@ __host__ __device__ __forceinline__ double fix_value(long long hi, long long lo,
 __device__ __forceinline__ int lane_prev(int v, int first) { return __builtin_amdgcn_update_dpp(first, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ int lane_next(int v, int last) { return __builtin_amdgcn_update_dpp(last, v, 0x130, 0xf, 0xf, false); }
 
-// Union-find with the smaller index as the root (atomicMin on the parent of the larger root), TWO unions of a lane side by side:
-// (a0, b0) and, where a1 >= 0, (a1, b1).  The four walks to the roots advance together -- four loads in flight per step instead
-// of the one of a find after the other -- and a union whose atomicMin lost a race goes on from what it saw.  Unions of one lane
-// may touch the same sets: atomicMin keeps every interleaving a forest whose roots are the smallest indices.
-__device__ __forceinline__ void union2_min_root(int32_t *parent, int a0, int b0, int a1, int b1)
-{
-    bool on0 = a0 >= 0, on1 = a1 >= 0;
-    while (on0 || on1) {
-        const int pa0 = on0 ? parent[a0] : 0, pb0 = on0 ? parent[b0] : 0;
-        const int pa1 = on1 ? parent[a1] : 0, pb1 = on1 ? parent[b1] : 0;
-        if (on0) {
-            if (pa0 == a0 && pb0 == b0) {
-                const int hi = max(a0, b0), lo = min(a0, b0);
-                const int old = hi == lo ? hi : atomicMin(&parent[hi], lo);
-                on0 = old != hi;
-                a0 = old;
-                b0 = lo;
-            } else {
-                a0 = pa0;
-                b0 = pb0;
-            }
-        }
-        if (on1) {
-            if (pa1 == a1 && pb1 == b1) {
-                const int hi = max(a1, b1), lo = min(a1, b1);
-                const int old = hi == lo ? hi : atomicMin(&parent[hi], lo);
-                on1 = old != hi;
-                a1 = old;
-                b1 = lo;
-            } else {
-                a1 = pa1;
-                b1 = pb1;
-            }
-        }
-    }
-}
-
 __device__ __forceinline__ long long wave_sum_i64(long long v)
 {
 #pragma unroll

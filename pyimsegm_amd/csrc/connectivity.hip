@@ -19,7 +19,9 @@
 //      neighbour is met last: "already labelled" == belongs to a component with a smaller root,
 //      which is static, so all small components run their (tiny) BFS concurrently, one thread each;
 //   5. merged-into-merged chains are resolved by pointer chasing (roots strictly decrease).
+#include "scan.h"
 #include "slic.h"
+#include "unionfind.h"
 
 #include <atomic>
 
@@ -40,56 +42,6 @@ __device__ __forceinline__ int neighbour(int p, int D, int H, int W, int d)
         case 3: return y > 0 ? p - W : -1;
         case 4: return z + 1 < D ? p + W * H : -1;
         default: return z > 0 ? p - W * H : -1;
-    }
-}
-
-__device__ __forceinline__ int uf_find(const int32_t *parent, int a)
-{
-    int p = parent[a];
-    while (p != a) {
-        a = p;
-        p = parent[a];
-    }
-    return a;
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int a, int b)
-{
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            int t = a;
-            a = b;
-            b = t;
-        }
-        // a > b: hang the larger root below the smaller one
-        int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// union with the two finds walked together (both loads of a step in flight at once: half the dependent trips of uf_union)
-__device__ __forceinline__ void uf_union_pair(int32_t *parent, int a, int b)
-{
-    while (true) {
-        while (true) {
-            const int pa = parent[a], pb = parent[b];
-            if (pa == a && pb == b) break;
-            a = pa;
-            b = pb;
-        }
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
     }
 }
 
@@ -248,25 +200,8 @@ __global__ void __launch_bounds__(256) k_ccl_flatten_sizes(int32_t *parent, int3
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     const bool in = p < n, full = p + 4 <= n;
     int r[4];
-    if (full) {
-        const int4 q = *reinterpret_cast<const int4 *>(parent + p);
-        r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) r[c] = p + c < n ? parent[p + c] : 0;
-    }
-    while (true) {
-        int q[4];
-        bool moved = false;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = parent[r[c]];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            moved |= q[c] != r[c];
-            r[c] = q[c];
-        }
-        if (!moved) break;
-    }
+    load4_i32(parent, p, n, 0, r);
+    walk4_to_roots(parent, r);
     if (full) {
         *reinterpret_cast<int4 *>(parent + p) = make_int4(r[0], r[1], r[2], r[3]);
     } else {
@@ -335,19 +270,10 @@ __global__ void __launch_bounds__(256) k_ccl_flatten_sizes_rows(int32_t *parent,
         const int4 q = ok ? *reinterpret_cast<const int4 *>(parent + slice + (size_t)(y0 + j) * W + x) : make_int4(0, 0, 0, 0);
         r[j][0] = q.x; r[j][1] = q.y; r[j][2] = q.z; r[j][3] = q.w;
     }
-    while (true) {
+    while (true) {                                                         // (the sixteen walks in ONE loop: their loads stay in flight together)
         bool moved = false;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int q[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) q[c] = parent[r[j][c]];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                moved |= q[c] != r[j][c];
-                r[j][c] = q[c];
-            }
-        }
+        for (int j = 0; j < 4; ++j) moved |= walk4_step(parent, r[j]);
         if (!moved) break;
     }
 #pragma unroll
@@ -464,29 +390,6 @@ k_oversize_commit(int32_t *parent, uint8_t *state, int32_t *csize_next, const in
 constexpr int SCAN_TILES = 4;
 constexpr int SCAN_BLOCK = SCAN_TILES * 1024;
 
-template <int NW> __device__ __forceinline__ int block_exclusive_scan(int v, int *total)
-{
-    __shared__ int wsum[NW];
-    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        base += w < wave ? wsum[w] : 0;
-        all += wsum[w];
-    }
-    *total = all;
-    __syncthreads();
-    return base + incl - v;
-}
-
 // !ASSIGN: first pass -- kept roots counted per workgroup; components that reach `max_size` raise counters[CNT_OVER] (the fast
 //          path's check that no component has to be truncated -- k_find_oversize in the rounds of the general path);
 // ASSIGN:  second pass -- kept roots receive their labels, the roots of small components are appended to `list` (one atomic per
@@ -503,13 +406,7 @@ k_kept_scan(const int32_t *__restrict__ parent, const int32_t *__restrict__ csiz
     for (int i = 0; i < SCAN_TILES; ++i) {
         const int p = base + i * 1024;
         int v[4];
-        if (p + 4 <= n) {
-            const int4 q = *reinterpret_cast<const int4 *>(parent + p);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = p + c < n ? parent[p + c] : -1;
-        }
+        load4_i32(parent, p, n, -1, v);
         cnt[i] = 0;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -532,12 +429,7 @@ k_kept_scan(const int32_t *__restrict__ parent, const int32_t *__restrict__ csiz
         if (n_over) atomicAdd(&counters[CNT_OVER], n_over);
     } else {
         // the small roots of the wave behind one another in the list
-        int incl = n_small;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if ((int)(threadIdx.x & 63) >= off) incl += t;
-        }
+        const int incl = wave_inclusive_scan(n_small);
         const int wave_total = __shfl(incl, 63, 64);
         int at = 0;
         if (wave_total) {
@@ -558,36 +450,6 @@ k_kept_scan(const int32_t *__restrict__ parent, const int32_t *__restrict__ csiz
             }
         }
     }
-}
-
-// exclusive scan of the per-block counts by one workgroup; total -> counters[CNT_KEPT]
-__global__ void __launch_bounds__(1024) k_scan_blocksums(int32_t *blocksum, int nblocks, int32_t *counters)
-{
-    // (four consecutive counts per lane and turn: a turn costs a trip to memory and its barriers whatever it carries)
-    constexpr int PER = 4;
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024 * PER) {
-        const int i = base + threadIdx.x * PER;
-        int v[PER], t = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            v[j] = i + j < nblocks ? blocksum[i + j] : 0;
-            t += v[j];
-        }
-        int total;
-        int excl = carry + block_exclusive_scan<16>(t, &total);
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            if (i + j < nblocks) blocksum[i + j] = excl;
-            excl += v[j];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counters[CNT_KEPT] = carry;
 }
 
 // ---- small components ------------------------------------------------------------------------------
@@ -669,14 +531,8 @@ k_small_bbox(const int32_t *__restrict__ parent, const int32_t *__restrict__ csi
 {
     if (counters[CNT_SMALL] > capacity) return;         // table too small: the thread-BFS fallback takes all (uniform)
     const int p0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    int r[4] = { -1, -1, -1, -1 };
-    if (p0 + 4 <= n) {
-        const int4 v = *reinterpret_cast<const int4 *>(parent + p0);
-        r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = p0 + j < n ? parent[p0 + j] : -1;
-    }
+    int r[4];
+    load4_i32(parent, p0, n, -1, r);
     // runs of equal small roots inside the lane: at most four boxes, nearly always one or none
     int slot[4];
     Box6 box[4];
@@ -1021,7 +877,7 @@ int launch_label_connected(int32_t *labels_inout, size_t n_voxels, int n_labels,
     hipLaunchKernelGGL(k_first_voxel, quads, 256, 0, st, labels_inout, n, n_labels, first);
     hipLaunchKernelGGL(k_first_mark, cdiv(n_labels, 256), 256, 0, st, first, n_labels, bitmap);
     hipLaunchKernelGGL(k_first_block_counts, cdiv(nblocks, 4), 256, 0, st, bitmap, nblocks, blocksum);
-    hipLaunchKernelGGL(k_scan_blocksums, 1, 1024, 0, st, blocksum, nblocks, counters);
+    launch_exclusive_scan(blocksum, nblocks, &counters[CNT_KEPT], st);
     hipLaunchKernelGGL(k_first_rank, cdiv(n_labels, 256), 256, 0, st, first, n_labels, bitmap, blocksum);
     hipLaunchKernelGGL(k_relabel, quads, 256, 0, st, labels_inout, n, n_labels, first);
     HIP_TRY(hipMemcpyAsync(total_dev, counters + CNT_KEPT, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -1069,7 +925,7 @@ static int conn_tail(const int32_t *csize_final, int32_t *adjptr, int D, int H, 
     }
     hipLaunchKernelGGL(k_kept_scan<false>, nblocks, 256, 0, st, w.parent, csize_final, n, min_size, oversize_from, w.blocksum,
                        w.newlabel, start_label, w.list, w.counters);
-    hipLaunchKernelGGL(k_scan_blocksums, 1, 1024, 0, st, w.blocksum, nblocks, w.counters);
+    launch_exclusive_scan(w.blocksum, nblocks, &w.counters[CNT_KEPT], st);
     hipLaunchKernelGGL(k_kept_scan<true>, nblocks, 256, 0, st, w.parent, csize_final, n, min_size, 0x7fffffff, w.blocksum,
                        w.newlabel, start_label, w.list, w.counters);
     HIP_TRY(hipMemsetAsync(w.visited, 0, n, st));
@@ -1405,12 +1261,7 @@ __device__ __forceinline__ void kept_rank_block(int *offs /* [KR_BUCKETS + 1] */
             sum += v[j];
         }
         const int lane = tid & 63, wave = tid >> 6;
-        int incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_inclusive_scan(sum);
         if (lane == 63) wsum[wave] = incl;
         __syncthreads();
         int base = 0;

@@ -125,35 +125,6 @@ __global__ void k_edge_rowcount(const uint32_t *__restrict__ bitmap, int K, int 
     rowcount[b] = c;
 }
 
-// exclusive scan of rowcount by one workgroup (K is small); total -> n_edges
-__global__ void __launch_bounds__(256) k_edge_scan(int32_t *rowcount, int K, int32_t *n_edges)
-{
-    __shared__ int wsum[4];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int base = 0; base < K; base += 256) {
-        int i = base + threadIdx.x;
-        int v = i < K ? rowcount[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            int t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int pre = carry;
-        for (int w = 0; w < wave; ++w) pre += wsum[w];
-        if (i < K) rowcount[i] = pre + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry = pre + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *n_edges = carry;
-}
-
 __global__ void k_edge_emit(const uint32_t *__restrict__ bitmap, int K, int words, const int32_t *__restrict__ offsets,
                             int32_t *edges, int capacity)
 {
@@ -219,7 +190,7 @@ int launch_edge_extract_table(const int32_t *table, int K, int cap, int32_t *row
                               int32_t *n_edges_dev, hipStream_t st)
 {
     hipLaunchKernelGGL(k_table_rowcount, cdiv((long)K * 64, 256), 256, 0, st, table, K, cap, rowcount);
-    hipLaunchKernelGGL(k_edge_scan, 1, 256, 0, st, rowcount, K, n_edges_dev);
+    launch_exclusive_scan(rowcount, K, n_edges_dev, st);            // rowcount -> first edge of every row
     hipLaunchKernelGGL(k_table_emit, cdiv((long)K * 64, 256), 256, 0, st, table, K, cap, rowcount, edges_out, edge_capacity);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -295,7 +266,7 @@ int launch_edge_extract(const uint32_t *bitmap, int K, int words, int32_t *rowco
                         int32_t *n_edges_dev, hipStream_t st)
 {
     hipLaunchKernelGGL(k_edge_rowcount, cdiv(K, 256), 256, 0, st, bitmap, K, words, rowcount);
-    hipLaunchKernelGGL(k_edge_scan, 1, 256, 0, st, rowcount, K, n_edges_dev);
+    launch_exclusive_scan(rowcount, K, n_edges_dev, st);            // rowcount -> first edge of every row
     hipLaunchKernelGGL(k_edge_emit, cdiv(K, 256), 256, 0, st, bitmap, K, words, rowcount, edges_out, edge_capacity);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -13,6 +13,7 @@
 // a fixed tree order (numpy uses pairwise summation, BLAS its own order): class probabilities agree with scikit-learn
 // to ~1e-13, edge weights to ~1e-15 relative (tests: 1e-9 / 1e-12) -- the integer energies are identical unless a
 // scaled cost lies within that distance of an integer.
+#include "scan.h"
 #include "slic.h"
 
 namespace imsegm {
@@ -97,12 +98,7 @@ k_adj_rowprefix(const uint32_t *__restrict__ bitmap, const int *__restrict__ Kp,
             const int w = w0 + lane;
             const uint32_t bits = w < words ? bitmap[(size_t)v * words + w] : 0u;
             const int c = __popc(bits);
-            int incl = c;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += t;
-            }
+            const int incl = wave_inclusive_scan(c);
             if (w < words) wordprefix[(size_t)v * words + w] = carry + incl - c;
             int lowc = 0;
             if (w < (v >> 5)) lowc = c;
@@ -146,15 +142,7 @@ k_adj_scan(const int *__restrict__ Kp, const int32_t *__restrict__ deg, const in
             t0 += v0[j];
             t1 += v1[j];
         }
-        int i0 = t0, i1 = t1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int u0 = __shfl_up(i0, off, 64), u1 = __shfl_up(i1, off, 64);
-            if (lane >= off) {
-                i0 += u0;
-                i1 += u1;
-            }
-        }
+        const int i0 = wave_inclusive_scan(t0), i1 = wave_inclusive_scan(t1);
         if (lane == 63) {
             wsum[0][wave] = i0;
             wsum[1][wave] = i1;

@@ -3,8 +3,8 @@
 // Replaces, for D x H x W gray volumes:
 //   skimage.segmentation.slic(im, n_segments, compactness, multichannel=False, spacing=space, sigma=1)
 //       as called at /root/reference/imsegm/superpixels.py:104-106   (no Lab, anisotropic spacing)
-//   skimage.measure.label(slic_segments)                     superpixels.py:111 (full connectivity, 0 = background)
-//   make_graph_segm_connect_grid3d_conn6 / superpixel_centers (3-D branch)   superpixels.py:180-242
+// (skimage.measure.label of the supervoxel map, superpixels.py:111: label_cc.hip; the graph and the centres of the supervoxels,
+// superpixels.py:180-242: volume_graph.hip)
 // Arithmetic contract of the assignment: identical to oracle orc_slic_iterate (fp64, operation order
 // of _slic.pyx with spacing):  d = ((sz*(cz-z))^2 + (sy*(cy-y))^2 + (sx*(cx-x))^2) * (1/step^2) + (v - cv)^2.
 //
@@ -1163,597 +1163,6 @@ int launch_vol_slic_f32(VolState s, const float *vol, int32_t *labels, int max_i
             else hipLaunchKernelGGL(k_vol_assign_f32<false>, grid, 256, 0, st, s, vol, labels);
         }
     }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- skimage.measure.label: full (26-/8-) connectivity, value 0 = background ------------------------------
-__device__ __forceinline__ int cc_find(const int32_t *parent, int a)
-{
-    int p = parent[a];
-    while (p != a) {
-        a = p;
-        p = parent[a];
-    }
-    return a;
-}
-__device__ __forceinline__ void cc_union(int32_t *parent, int a, int b)
-{
-    while (true) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) {
-            int t = a;
-            a = b;
-            b = t;
-        }
-        int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// union with the two finds walked together (both loads of a step in flight at once: half the dependent trips of cc_union)
-__device__ __forceinline__ void cc_union_pair(int32_t *parent, int a, int b)
-{
-    while (true) {
-        while (true) {
-            const int pa = parent[a], pb = parent[b];
-            if (pa == a && pb == b) break;
-            a = pa;
-            b = pb;
-        }
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_cc_init(int32_t *parent, int n)
-{
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) parent[p] = p;
-}
-
-__global__ void __launch_bounds__(256)
-k_cc_merge_full(const int32_t *__restrict__ labels, int32_t *parent, int D, int H, int W)
-{
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D * H * W) return;
-    const int l = labels[p];
-    if (l == 0) return;                              // background is never joined
-    const int x = p % W, y = (p / W) % H, z = p / (W * H);
-    // the 13 "earlier" neighbours of the full 3 x 3 x 3 neighbourhood
-    for (int dz = -1; dz <= 0; ++dz)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dx = -1; dx <= 1; ++dx) {
-                if (dz == 0 && (dy > 0 || (dy == 0 && dx >= 0))) continue;
-                int zz = z + dz, yy = y + dy, xx = x + dx;
-                if (zz < 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-                int q = (zz * H + yy) * W + xx;
-                if (labels[q] == l) cc_union(parent, p, q);
-            }
-}
-
-// Round 5 (k_cc_merge_runs, 28.9 ms at 2^30 voxels; replaced by k_cc_merge_rows below, which keeps its rule): the same components
-// with a handful of unions per RUN instead of thirteen per voxel.  Every voxel ties itself to its left neighbour when the labels
-// agree, so the voxels of a run (equal labels side by side in one row) are one set.  For each of the four earlier rows that touch
-// p -- (z, y-1), (z-1, y-1), (z-1, y), (z-1, y+1) -- with a, b, c its voxels at x-1, x, x+1:
-//   * p has no equal left neighbour (a run starts): b equal -> union with b (a and c, if equal, hang on b's run); else union with a
-//     and with c, whichever is equal;
-//   * p continues a run: its left neighbour is tied to its own equal neighbours of that row, which include a and b, so only c can
-//     be news, and only when b is not equal (otherwise c hangs on b's run).
-// By induction along the run every voxel ends up in one set with every equal voxel of its 26-neighbourhood, i.e. the components are
-// those of k_cc_merge_full; the root of a set is its smallest index either way (cc_union), so numbering and result are identical.
-// Unions happen where runs start or the row above changes -- on the surface of the segments, not in their volume.
-
-// Round 6: the same merge rule with the five rows it looks at -- (z, y) and the four earlier rows -- loaded ONCE per wave and the
-// x - 1 / x + 1 neighbours taken from the neighbouring lanes (one DPP move each) instead of up to thirteen loads per voxel, no
-// division for the coordinates (grid = row segments, y, z), and the forest initialised by runs: a wave covers MR_SPAN = 62 voxels of
-// a row with lane 0 and lane 63 carrying the voxels left and right of them; k_cc_init_rows points every voxel of a run at the
-// run's first voxel INSIDE its segment, so the merge kernel ties a voxel to its left neighbour only where a run crosses into the
-// segment.  Same sets, same roots (the smallest index of a set) as k_cc_merge_runs / k_cc_merge_full.
-constexpr int MR_SPAN = 62;
-
-__global__ void __launch_bounds__(256)
-k_cc_init_rows(const int32_t *__restrict__ labels, int32_t *__restrict__ parent, int H, int W)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int x = (blockIdx.x * 4 + wave) * MR_SPAN + lane - 1;
-    const size_t row = ((size_t)blockIdx.z * H + blockIdx.y) * W;
-    const bool inx = x >= 0 && x < W;
-    const int l = inx ? labels[row + x] : -1;
-    const bool mine = inx && lane >= 1 && lane <= MR_SPAN;
-    const bool cont = lane_prev(l, -1) == l && lane > 1 && l != 0;          // continues a run that began inside this segment
-    const unsigned long long starts = __ballot(mine && !cont);
-    if (!mine) return;
-    const unsigned long long below = starts & ((2ULL << lane) - 1ULL);     // (lane <= 62)
-    const int start_lane = 63 - __clzll((long long)below);
-    parent[row + x] = (int)(row + x) - (lane - start_lane);
-}
-
-// MR_ROWS rows of the slice per wave: the MR_ROWS + 1 rows of the slice and the MR_ROWS + 2 rows of the slice behind that they touch
-// are loaded once, and the unions of a lane over its rows -- a bit each in `todo`: 13 r + 3 e + (dx + 1) for the voxel at x + dx of
-// earlier row e, 13 r + 12 for the left neighbour -- are done two at a time (union2_min_root), every lane that still has some side by
-// side.  (One row per wave, one union per lane and round: 16.4 ms at 2^30 voxels.)
-constexpr int MR_ROWS = 4;
-
-__global__ void __launch_bounds__(256)
-k_cc_merge_rows(const int32_t *__restrict__ labels, int32_t *parent, int D, int H, int W)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int x = (blockIdx.x * 4 + wave) * MR_SPAN + lane - 1;
-    const int y0 = blockIdx.y * MR_ROWS, z = blockIdx.z;
-    const bool inx = x >= 0 && x < W;
-    const int plane = H * W;
-    const size_t row0 = (size_t)z * plane + (size_t)y0 * W;
-    // cz[i]: row y0 - 1 + i of this slice, pz[i]: row y0 - 1 + i of the slice behind; -1 where there is none (labels are >= 0)
-    int cz[MR_ROWS + 1], pz[MR_ROWS + 2];
-#pragma unroll
-    for (int i = 0; i <= MR_ROWS; ++i) {
-        const int y = y0 - 1 + i;
-        cz[i] = (inx && y >= 0 && y < H) ? labels[row0 + (size_t)(i - 1) * W + x] : -1;
-    }
-#pragma unroll
-    for (int i = 0; i <= MR_ROWS + 1; ++i) {
-        const int y = y0 - 1 + i;
-        pz[i] = (inx && z > 0 && y >= 0 && y < H) ? labels[row0 - plane + (size_t)(i - 1) * W + x] : -1;
-    }
-    int czp[MR_ROWS + 1], czn[MR_ROWS + 1], pzp[MR_ROWS + 2], pzn[MR_ROWS + 2];
-#pragma unroll
-    for (int i = 0; i <= MR_ROWS; ++i) {
-        czp[i] = lane_prev(cz[i], -1);
-        czn[i] = lane_next(cz[i], -1);
-    }
-#pragma unroll
-    for (int i = 0; i <= MR_ROWS + 1; ++i) {
-        pzp[i] = lane_prev(pz[i], -1);
-        pzn[i] = lane_next(pz[i], -1);
-    }
-    const bool seg = inx && lane >= 1 && lane <= MR_SPAN;
-    unsigned long long todo = 0;
-#pragma unroll
-    for (int r = 0; r < MR_ROWS; ++r) {
-        const int l = cz[1 + r];
-        const bool mine = seg && y0 + r < H && l != 0;                      // background is never joined
-        const bool left = czp[1 + r] == l;
-        if (mine && left && lane == 1) todo |= 1ULL << (13 * r + 12);        // a run that crosses into the segment
-        // the four earlier rows that touch row y0 + r: (z, y-1), (z-1, y-1), (z-1, y), (z-1, y+1)
-        const int el[4] = { cz[r], pz[r], pz[r + 1], pz[r + 2] };
-        const int ep[4] = { czp[r], pzp[r], pzp[r + 1], pzp[r + 2] };
-        const int en[4] = { czn[r], pzn[r], pzn[r + 1], pzn[r + 2] };
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool a = ep[e] == l, b = el[e] == l, c = en[e] == l;
-            if (!mine) continue;
-            if (left) {
-                if (c && !b) todo |= 1ULL << (13 * r + 3 * e + 2);
-            } else if (b) {
-                todo |= 1ULL << (13 * r + 3 * e + 1);
-            } else {
-                if (a) todo |= 1ULL << (13 * r + 3 * e);
-                if (c) todo |= 1ULL << (13 * r + 3 * e + 2);
-            }
-        }
-    }
-    const int p0 = (int)(row0 + x);
-    while (__any(todo != 0)) {
-        int ua[2] = { -1, -1 }, ub[2] = { -1, -1 };
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if (!todo) continue;
-            const int bit = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int r = bit / 13, k = bit - 13 * r;
-            const int p = p0 + r * W;
-            ua[j] = p;
-            if (k == 12) {
-                ub[j] = p - 1;
-            } else {
-                const int e = k / 3, dx = k - 3 * e - 1;
-                ub[j] = p + dx + (e == 0 ? -W : e == 1 ? -plane - W : e == 2 ? -plane : -plane + W);
-            }
-        }
-        union2_min_root(parent, ua[0], ub[0], ua[1], ub[1]);
-    }
-}
-
-// four consecutive words of an int32 array (one 16-byte load where all four exist, `fill` behind the end)
-__device__ __forceinline__ void load4_i32(const int32_t *a, int p, int n, int fill, int (&v)[4])
-{
-    if (p + 4 <= n) {
-        const int4 q = *reinterpret_cast<const int4 *>(a + p);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = p + c < n ? a[p + c] : fill;
-    }
-}
-
-// roots of non-background components are numbered 1, 2, ... in raster order (block scan in three steps).  A workgroup takes
-// CC_BLOCK voxels as CC_TILES tiles of 1 024 -- four consecutive voxels per lane, one 16-byte load, a wave reads 1 KB contiguous
-// (16 consecutive voxels per lane, as before round 6, made every load instruction touch 64 cache lines: 2.3 ms a pass at 2^30
-// voxels).  Only ROOTS are looked at -- parent[p] == p, which the merge pass leaves final -- so the forest is not flattened first:
-// k_cc_write walks from every voxel to its root itself.
-constexpr int CC_TILES = 4;
-constexpr int CC_BLOCK = CC_TILES * 1024;
-
-template <int NW> __device__ __forceinline__ int cc_block_scan(int v, int *total)
-{
-    __shared__ int wsum[NW];
-    int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        base += w < wave ? wsum[w] : 0;
-        all += wsum[w];
-    }
-    *total = all;
-    __syncthreads();
-    return base + incl - v;
-}
-
-template <bool ASSIGN>
-__global__ void __launch_bounds__(256)
-k_cc_number(const int32_t *__restrict__ labels, const int32_t *__restrict__ parent, int n, int32_t *blocksum,
-            int32_t *newlabel)
-{
-    const int base = blockIdx.x * CC_BLOCK + threadIdx.x * 4;
-    unsigned fg = 0, roots = 0;                     // bit 4 * tile + c: voxel is the root of a foreground / of any component
-    int cnt[CC_TILES];
-#pragma unroll
-    for (int i = 0; i < CC_TILES; ++i) {
-        const int p = base + i * 1024;
-        int v[4];
-        load4_i32(parent, p, n, -1, v);
-        cnt[i] = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (v[c] != p + c) continue;
-            roots |= 1u << (4 * i + c);
-            if (labels[p + c] != 0) {
-                fg |= 1u << (4 * i + c);
-                cnt[i]++;
-            }
-        }
-    }
-    if (!ASSIGN) {
-        int total;
-        cc_block_scan<4>(cnt[0] + cnt[1] + cnt[2] + cnt[3], &total);
-        if (threadIdx.x == 0) blocksum[blockIdx.x] = total;
-    } else {
-        int rank0 = blocksum[blockIdx.x];
-#pragma unroll
-        for (int i = 0; i < CC_TILES; ++i) {
-            int total;
-            int rank = rank0 + cc_block_scan<4>(cnt[i], &total);
-            rank0 += total;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (roots >> (4 * i + c) & 1u) newlabel[base + i * 1024 + c] = (fg >> (4 * i + c) & 1u) ? 1 + rank++ : 0;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(1024) k_cc_scan_blocks(int32_t *blocksum, int nblocks, int32_t *total_out)
-{
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024) {
-        int i = base + threadIdx.x;
-        int v = i < nblocks ? blocksum[i] : 0;
-        int total;
-        int excl = cc_block_scan<16>(v, &total);
-        if (i < nblocks) blocksum[i] = carry + excl;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-
-// out[p] = number of p's root: four voxels per lane, their walks to the root side by side (four loads in flight per step; the
-// forest is what the merge pass left -- a run's voxels point at its first voxel, that one at an earlier run -- two or three steps)
-__global__ void __launch_bounds__(256)
-k_cc_write(const int32_t *__restrict__ parent, const int32_t *__restrict__ newlabel, int n, int32_t *out)
-{
-    const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (p >= n) return;
-    int r[4];
-    load4_i32(parent, p, n, 0, r);
-    while (true) {
-        int q[4];
-        bool moved = false;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) q[c] = parent[r[c]];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            moved |= q[c] != r[c];
-            r[c] = q[c];
-        }
-        if (!moved) break;
-    }
-    int o[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = newlabel[r[c]];
-    if (p + 4 <= n) {
-        *reinterpret_cast<int4 *>(out + p) = make_int4(o[0], o[1], o[2], o[3]);
-    } else {
-        for (int c = 0; p + c < n; ++c) out[p + c] = o[c];
-    }
-}
-
-int launch_label_cc(int32_t *labels_inout, int D, int H, int W, int32_t *parent, int32_t *newlabel, int32_t *blocksum,
-                    int32_t *total_dev, hipStream_t st)
-{
-    const int n = D * H * W, grid = cdiv(n, 256), nb = cdiv(n, CC_BLOCK);
-    if (knobs().cc_merge_full || H > 65535 || D > 65535) {
-        hipLaunchKernelGGL(k_cc_init, grid, 256, 0, st, parent, n);
-        hipLaunchKernelGGL(k_cc_merge_full, grid, 256, 0, st, labels_inout, parent, D, H, W);
-    } else {
-        const dim3 rows(cdiv(W, 4 * MR_SPAN), H, D), row_groups(cdiv(W, 4 * MR_SPAN), cdiv(H, MR_ROWS), D);
-        hipLaunchKernelGGL(k_cc_init_rows, rows, 256, 0, st, labels_inout, parent, H, W);
-        hipLaunchKernelGGL(k_cc_merge_rows, row_groups, 256, 0, st, labels_inout, parent, D, H, W);
-    }
-    hipLaunchKernelGGL(k_cc_number<false>, nb, 256, 0, st, labels_inout, parent, n, blocksum, newlabel);
-    hipLaunchKernelGGL(k_cc_scan_blocks, 1, 1024, 0, st, blocksum, nb, total_dev);
-    hipLaunchKernelGGL(k_cc_number<true>, nb, 256, 0, st, labels_inout, parent, n, blocksum, newlabel);
-    hipLaunchKernelGGL(k_cc_write, cdiv(cdiv(n, 4), 256), 256, 0, st, parent, newlabel, n, labels_inout);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ---- 6-connected adjacency bitmap + centre sums of a label volume -----------------------------------------
-// (table: instead of bit (row b, column a) of a K x K bitmap, every label goes into the row of each of its neighbours in a K x cap
-// table of neighbour slots -- open addressing inside the row, -1 = free; a row that is full raises *overflow and the caller comes
-// back with wider rows.  The bitmap is 11 GB for the 3 * 10^5 supervoxels of BASELINE configs[4] and caps K; the table is
-// K * cap * 4 bytes.  Round 6: the table is SYMMETRIC (rounds 4 / 5 kept the smaller neighbours only), so that the fused call can
-// build its arcs from it -- terms.hip k_tab_sort_rows / k_tab_emit -- as it does from the mirrored bitmap.)
-__device__ __forceinline__ void neighbour_insert(int32_t *table, int cap, int b, int a, int *overflow)
-{
-    int32_t *row = table + (size_t)b * cap;
-    unsigned slot = ((unsigned)a * 2654435761u) >> 7;
-    for (int probe = 0; probe < cap; ++probe, ++slot) {
-        int32_t *cell = row + (slot & (unsigned)(cap - 1));
-        int seen = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen == a) return;
-        if (seen == -1) {
-            seen = atomicCAS(cell, -1, a);
-            if (seen == -1 || seen == a) return;
-        }
-    }
-    *overflow = 1;
-}
-
-// Round 6: by rows and runs, like the 2-D kernel (graph.hip).  A wave owns 64 x VA_ROWS voxels of one slice -- VA_ROWS + 1 rows of it
-// and VA_ROWS rows of the next slice in registers, the left / right neighbour through one DPP move each.
-//   * neighbour pairs: across x a pair exists exactly where a run ends; across y and z the pair (label, label below / behind) of a
-//     voxel is the pair of its left neighbour along the whole contact of two segments, so only the lane where EITHER label changes
-//     reports it -- a handful of inserts per run instead of one per surface voxel;
-//   * centre sums: the first lane of a run knows its length from the vote of the run starts, hence n, sum y, sum x of the run in
-//     closed form (z is the workgroup's); they meet in an LDS hash table of the workgroup (a 64 x 16 cross-section sees a dozen
-//     labels), flushed with one set of int64 global atomics per label and workgroup.
-// Rounds 2 - 5 went voxel by voxel: two 32-bit divisions per voxel for its coordinates, a serial loop over the distinct labels of
-// a wave with eight int64 wave reductions and four global atomics each (19.8 ms for the 2^30 voxels of BASELINE configs[4]).
-// MODE 0: bit (row b, column a), a < b, of the K x K bitmap; MODE 1: a into row b AND b into row a of the neighbour table.
-constexpr int VA_ROWS = 4;
-constexpr int VA_SLOTS = 64;
-constexpr int VA_DEPTH = 8;           // slices a workgroup walks (sums of a table slot stay far below 2^31: 8 192 voxels x 65 535)
-
-// The (up to) three neighbour pairs a voxel reports, both directions each: the six table cells a pair's labels hash to are looked at
-// TOGETHER -- one trip to memory -- and nearly always hold the label already (a pair of neighbouring supervoxels is reported by every
-// voxel along their common face); what is not found there goes through neighbour_insert.  (One pair after the other, each with
-// its own look: twenty-four dependent trips per wave of four rows, 4.6 ms for the 2^30 voxels of config 5.)
-__device__ __forceinline__ void neighbour_insert3(int32_t *table, int cap, int l, const int (&nb)[3], int *overflow)
-{
-    int seen[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int row = i < 3 ? l : nb[i - 3], val = i < 3 ? nb[i] : l;
-        seen[i] = val;                                             // (no pair: nothing to do)
-        if (nb[i % 3] >= 0)
-            seen[i] = __hip_atomic_load(table + (size_t)row * cap + ((((unsigned)val * 2654435761u) >> 7) & (unsigned)(cap - 1)),
-                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int row = i < 3 ? l : nb[i - 3], val = i < 3 ? nb[i] : l;
-        if (nb[i % 3] >= 0 && seen[i] != val) neighbour_insert(table, cap, row, val, overflow);
-    }
-}
-
-template <int MODE>
-__device__ __forceinline__ void adjacency_report(int l, int nb, int words, uint32_t *bitmap, int32_t *table, int cap, int *overflow)
-{
-    if (MODE == 1) {
-        neighbour_insert(table, cap, l, nb, overflow);
-        neighbour_insert(table, cap, nb, l, overflow);
-    } else {
-        const int a = min(l, nb), b = max(l, nb);
-        uint32_t *wp = bitmap + (size_t)b * words + (a >> 5);
-        const uint32_t bit = 1u << (a & 31);
-        if (!(*wp & bit)) atomicOr(wp, bit);
-    }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256)
-k_vol_adjacency_runs(const int32_t *__restrict__ labels, int D, int H, int W, int words, uint32_t *bitmap,
-                     long long *__restrict__ cacc, int32_t *table, int cap, int *overflow)
-{
-    // (round 6, later: a workgroup walks VA_DEPTH slices -- the rows of the slice behind are the next turn's own rows, so a voxel is
-    // loaded once instead of twice, and the centre sums of all the slices meet in one LDS table: 4.85 -> see profiles/README_r06.md)
-    __shared__ int h_key[VA_SLOTS], h_n[VA_SLOTS], h_sz[VA_SLOTS], h_sy[VA_SLOTS], h_sx[VA_SLOTS];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (threadIdx.x < VA_SLOTS) {
-        h_key[threadIdx.x] = -1;
-        h_n[threadIdx.x] = 0;
-        h_sz[threadIdx.x] = 0;
-        h_sy[threadIdx.x] = 0;
-        h_sx[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    const int z_first = blockIdx.z * VA_DEPTH, z_end = min(z_first + VA_DEPTH, D);
-    const int y0 = (blockIdx.y * 4 + wave) * VA_ROWS;
-    const int x = blockIdx.x * 64 + lane;
-    const bool xin = x < W;
-    const size_t plane = (size_t)H * W;
-    const unsigned long long le = (lane == 63) ? ~0ULL : ((2ULL << lane) - 1ULL);
-    // (edge: the voxel right of the wave's last lane, fetched by that lane WITH the rows -- asked for row by row where it is used, it
-    // was a trip to memory per row and slice for the sake of one lane)
-    int lab[VA_ROWS + 1], behind[VA_ROWS + 1], edge[VA_ROWS], edge_behind[VA_ROWS];
-    const bool last = lane == 63 && x + 1 < W;
-    {
-        const int32_t *__restrict__ first = labels + ((size_t)z_first * H + y0) * W;
-#pragma unroll
-        for (int r = 0; r <= VA_ROWS; ++r) lab[r] = (xin && y0 + r < H) ? first[(size_t)r * W + x] : -1;
-#pragma unroll
-        for (int r = 0; r < VA_ROWS; ++r) edge[r] = (last && y0 + r < H) ? first[(size_t)r * W + x + 1] : -1;
-#pragma unroll
-        for (int r = 0; r <= VA_ROWS; ++r) behind[r] = (xin && y0 + r < H && z_first + 1 < D) ? first[plane + (size_t)r * W + x] : -1;
-#pragma unroll
-        for (int r = 0; r < VA_ROWS; ++r) edge_behind[r] = (last && y0 + r < H && z_first + 1 < D) ? first[plane + (size_t)r * W + x + 1] : -1;
-    }
-    for (int z = z_first; z < z_end; ++z) {
-        // (the rows of slice z + 2 are requested HERE and used in the next turn: a turn does not wait for its own loads)
-        const int32_t *__restrict__ base = labels + ((size_t)z * H + y0) * W;          // (wave uniform)
-        const bool more = z + 1 < z_end && z + 2 < D;
-        int ahead[VA_ROWS + 1], edge_ahead[VA_ROWS];
-#pragma unroll
-        for (int r = 0; r <= VA_ROWS; ++r) ahead[r] = (more && xin && y0 + r < H) ? base[2 * plane + (size_t)r * W + x] : -1;
-#pragma unroll
-        for (int r = 0; r < VA_ROWS; ++r) edge_ahead[r] = (more && last && y0 + r < H) ? base[2 * plane + (size_t)r * W + x + 1] : -1;
-#pragma unroll
-        for (int r = 0; r < VA_ROWS; ++r) {
-            const int y = y0 + r;
-            const int l = lab[r];
-            const bool act = l >= 0;                                   // (the active lanes of a row are lanes 0 .. nact - 1)
-            int right = lane_next(l, -1);
-            if (lane == 63) right = edge[r];
-            const int left = lane_prev(l, -2);
-            const int below = lab[r + 1], back = behind[r];
-            const int below_left = lane_prev(below, -2), back_left = lane_prev(back, -2);
-            const bool rep_right = act && right >= 0 && right != l;
-            const bool rep_below = act && below >= 0 && below != l && !(left == l && below_left == below);
-            const bool rep_back = act && back >= 0 && back != l && !(left == l && back_left == back);
-            if (MODE == 1) {
-                if (rep_right || rep_below || rep_back) {
-                    const int nb[3] = { rep_right ? right : -1, rep_below ? below : -1, rep_back ? back : -1 };
-                    neighbour_insert3(table, cap, l, nb, overflow);
-                }
-            } else {
-                if (rep_right) adjacency_report<MODE>(l, right, words, bitmap, table, cap, overflow);
-                if (rep_below) adjacency_report<MODE>(l, below, words, bitmap, table, cap, overflow);
-                if (rep_back) adjacency_report<MODE>(l, back, words, bitmap, table, cap, overflow);
-            }
-            const bool start = act && left != l;                       // (lane 0: left = -2)
-            const unsigned long long starts = __ballot(start);
-            const int nact = __popcll(__ballot(act));
-            if (start) {
-                const unsigned long long above = starts & ~le;
-                const int len = (above ? __ffsll((long long)above) - 1 : nact) - lane;
-                const int sy = len * y, sx = len * x + (len * (len - 1)) / 2;
-                int slot = (int)(((unsigned int)l * 2654435761u) >> 26);          // 6 bits
-                bool placed = false;
-                for (int probe = 0; probe < VA_SLOTS; ++probe) {
-                    const int old = atomicCAS(&h_key[slot], -1, l);
-                    if (old == -1 || old == l) {
-                        placed = true;
-                        break;
-                    }
-                    slot = (slot + 1) & (VA_SLOTS - 1);
-                }
-                if (placed) {
-                    atomicAdd(&h_n[slot], len);
-                    atomicAdd(&h_sz[slot], len * z);
-                    atomicAdd(&h_sy[slot], sy);
-                    atomicAdd(&h_sx[slot], sx);
-                } else {                                               // (more than VA_SLOTS labels in the slices of a 64 x 16 cross-section)
-                    atomic_add_i64(cacc + (size_t)l * 4 + 0, len);
-                    atomic_add_i64(cacc + (size_t)l * 4 + 1, (long long)len * z);
-                    atomic_add_i64(cacc + (size_t)l * 4 + 2, (long long)sy);
-                    atomic_add_i64(cacc + (size_t)l * 4 + 3, (long long)sx);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r <= VA_ROWS; ++r) {
-            lab[r] = behind[r];
-            behind[r] = ahead[r];
-        }
-#pragma unroll
-        for (int r = 0; r < VA_ROWS; ++r) {
-            edge[r] = edge_behind[r];
-            edge_behind[r] = edge_ahead[r];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < VA_SLOTS && h_key[threadIdx.x] >= 0) {
-        const int k = h_key[threadIdx.x], n = h_n[threadIdx.x];
-        atomic_add_i64(cacc + (size_t)k * 4 + 0, n);
-        atomic_add_i64(cacc + (size_t)k * 4 + 1, h_sz[threadIdx.x]);
-        atomic_add_i64(cacc + (size_t)k * 4 + 2, h_sy[threadIdx.x]);
-        atomic_add_i64(cacc + (size_t)k * 4 + 3, h_sx[threadIdx.x]);
-    }
-}
-
-__global__ void k_vol_centres_finalize(const long long *__restrict__ cacc, int K, double *centres, uint8_t *present)
-{
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= K) return;
-    long long n = cacc[(size_t)k * 4];
-    present[k] = n > 0;
-    for (int c = 0; c < 3; ++c)
-        centres[3 * k + c] = n > 0 ? i64_to_double(cacc[(size_t)k * 4 + 1 + c]) / (double)n : -1.0;
-}
-
-static inline dim3 vol_adjacency_grid(int D, int H, int W) { return dim3(cdiv(W, 64), cdiv(H, 4 * VA_ROWS), cdiv(D, VA_DEPTH)); }
-
-int launch_vol_adjacency(const int32_t *labels, int D, int H, int W, int K, int words, uint32_t *bitmap, long long *cacc,
-                         double *centres, uint8_t *present, hipStream_t st)
-{
-    if (D > 65535 || cdiv(H, 4 * VA_ROWS) > 65535) {
-        set_error("adjacency: more than 65 535 slices or 1 048 560 rows");
-        return -1;
-    }
-    HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)K * words * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(cacc, 0, (size_t)K * 4 * sizeof(long long), st));
-    hipLaunchKernelGGL(k_vol_adjacency_runs<0>, vol_adjacency_grid(D, H, W), 256, 0, st, labels, D, H, W, words, bitmap, cacc, nullptr, 0, nullptr);
-    hipLaunchKernelGGL(k_vol_centres_finalize, cdiv(K, 256), 256, 0, st, cacc, K, centres, present);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// the same with the neighbour table (K x cap slots, cap a power of two) instead of the bitmap; *overflow (device) is raised when a
-// row was too narrow
-int launch_vol_adjacency_table(const int32_t *labels, int D, int H, int W, int K, int32_t *table, int cap, int *overflow, long long *cacc,
-                               double *centres, uint8_t *present, hipStream_t st)
-{
-    if (D > 65535 || cdiv(H, 4 * VA_ROWS) > 65535) {
-        set_error("adjacency: more than 65 535 slices or 1 048 560 rows");
-        return -1;
-    }
-    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)K * cap * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(overflow, 0, sizeof(int), st));
-    HIP_TRY(hipMemsetAsync(cacc, 0, (size_t)K * 4 * sizeof(long long), st));
-    hipLaunchKernelGGL(k_vol_adjacency_runs<1>, vol_adjacency_grid(D, H, W), 256, 0, st, labels, D, H, W, 0, nullptr, cacc, table, cap, overflow);
-    hipLaunchKernelGGL(k_vol_centres_finalize, cdiv(K, 256), 256, 0, st, cacc, K, centres, present);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -2,7 +2,7 @@
 // Needs no GPU (every valid call ends at "no device"), runs nothing on one, and is not loaded into Python.
 //
 //   cd pyimsegm_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-sanitize-recover=undefined ../../tools/sanitize_api_boundary.hip api_boundary.hip boundary.hip stats.hip \
+//       -Xarch_host -fno-sanitize-recover=undefined ../../tools/sanitize_api_boundary.hip api_boundary.hip boundary.hip scan.hip stats.hip \
 //       -o /tmp/sanitize_api_boundary && /tmp/sanitize_api_boundary
 //
 // The two helpers the API takes from api.hip (error text, HIP status check) are defined here so that the rest of the library stays out.
