@@ -286,18 +286,27 @@ IMSEGM_API int imsegm_image2d_features_color(imsegm_image2d *img, int feature_ma
 IMSEGM_API int imsegm_image2d_features_place(imsegm_image2d *img, int total_columns, int column);
 IMSEGM_API int imsegm_image2d_get_features(imsegm_image2d *img, double *features_out, int capacity_columns);
 
-/* class model evaluated on the device: sklearn Pipeline([StandardScaler,] GaussianMixture(covariance_type='full')) as
- * imsegm.graph_cuts.estim_class_model builds it (imsegm/graph_cuts.py:73-163).  The host passes what scikit-learn
- * itself precomputes per model (not per sample). */
+/* class model evaluated on the device: sklearn Pipeline([StandardScaler,] [PCA,] mixture) as
+ * imsegm.graph_cuts.estim_class_model builds it (imsegm/graph_cuts.py:73-163), the mixture a GaussianMixture or a
+ * BayesianGaussianMixture with covariance_type='full'.  The host passes what scikit-learn itself precomputes per model (not
+ * per sample); the per-component constants of the Bayesian mixture are folded into log_det and log_weights.
+ * n_features (F) is the dimension the mixture works in.  Without a PCA (n_inputs 0) it is also the width of the feature table.
+ * With one (version >= 101) the table is n_inputs (I) columns wide, 1 <= F <= I <= 256, the scaler vectors are [I] long, and a
+ * row x becomes (x @ pca_components_t - pca_shift) / pca_scale before the mixture sees it.  A zero-initialised tail behind
+ * const_term is the model without a PCA. */
 typedef struct {
     int n_features, n_classes;
-    const double *scaler_mean;    /* [F] StandardScaler.mean_ or NULL */
-    const double *scaler_scale;   /* [F] StandardScaler.scale_ or NULL */
-    const double *prec_chol;      /* [C][F][F] GaussianMixture.precisions_cholesky_ */
+    const double *scaler_mean;    /* [F] ([I] with a PCA) StandardScaler.mean_ or NULL */
+    const double *scaler_scale;   /* [F] ([I] with a PCA) StandardScaler.scale_ or NULL */
+    const double *prec_chol;      /* [C][F][F] precisions_cholesky_ */
     const double *mu_proj;        /* [C][F]   means_[c] @ precisions_cholesky_[c] */
-    const double *log_det;        /* [C]      _compute_log_det_cholesky */
-    const double *log_weights;    /* [C]      log(weights_) */
+    const double *log_det;        /* [C]      _compute_log_det_cholesky (+ the Bayesian mixture's constants) */
+    const double *log_weights;    /* [C]      log(weights_) (Bayesian mixture: _estimate_log_weights) */
     double const_term;            /* n_features * log(2 pi) */
+    int n_inputs;                 /* columns of the feature table the model reads; 0: n_features, no projection */
+    const double *pca_components_t;   /* [I][F] PCA.components_.T, contiguous */
+    const double *pca_shift;      /* [F] PCA.mean_ @ components_.T */
+    const double *pca_scale;      /* [F] sqrt(explained_variance_) clipped at eps (whiten=True) or NULL */
 } imsegm_gmm;
 
 /* edge types of imsegm.graph_cuts.compute_edge_weights (imsegm/graph_cuts.py:574-657); `| IMSEGM_EDGE_SPATIAL_NORM`

@@ -64,7 +64,8 @@ _ip = C.POINTER(C.c_int)
 class GmmParams(C.Structure):
     """``imsegm_gmm`` of include/imsegm_hip.h"""
     _fields_ = [('n_features', C.c_int), ('n_classes', C.c_int), ('scaler_mean', _vp), ('scaler_scale', _vp),
-                ('prec_chol', _vp), ('mu_proj', _vp), ('log_det', _vp), ('log_weights', _vp), ('const_term', C.c_double)]
+                ('prec_chol', _vp), ('mu_proj', _vp), ('log_det', _vp), ('log_weights', _vp), ('const_term', C.c_double),
+                ('n_inputs', C.c_int), ('pca_components_t', _vp), ('pca_shift', _vp), ('pca_scale', _vp)]
 
 
 class TermsDebug(C.Structure):
@@ -494,42 +495,83 @@ def mixture_em_wide(n_restarts, n_components, n_features, labels=None, start=Non
 
 
 class DeviceGmm(object):
-    """the constants of a fitted ``Pipeline([StandardScaler,] GaussianMixture(covariance_type='full'))`` that the
-    device needs for ``predict_proba``: what scikit-learn computes once per model (``means_ @ precisions_cholesky_``,
-    the log-determinants, ``log(weights_)``), formed with the very numpy expressions of ``sklearn/mixture/
-    _gaussian_mixture.py`` (``_estimate_log_gaussian_prob``, ``_compute_log_det_cholesky``)"""
+    """the constants of a fitted ``Pipeline([StandardScaler,] [PCA,] mixture)`` -- the mixture a ``GaussianMixture`` or a
+    ``BayesianGaussianMixture`` with ``covariance_type='full'`` -- that the device needs for ``predict_proba``: what scikit-learn
+    computes once per model (``means_ @ precisions_cholesky_``, the log-determinants, ``log(weights_)``), formed with the very
+    numpy expressions of ``sklearn/mixture/_gaussian_mixture.py`` (``_estimate_log_gaussian_prob``, ``_compute_log_det_cholesky``).
+
+    PCA (``sklearn/decomposition/_base.py`` ``_BasePCA._transform``): ``components_.T`` (``pca_components_t``), the centring
+    term ``mean_ @ components_.T`` (``pca_shift``) and, with ``whiten``, the clipped ``sqrt(explained_variance_)``
+    (``pca_scale``).  ``n_inputs`` is the width of the table the model reads, ``n_features`` the dimension of the mixture.
+
+    Bayesian mixture (``sklearn/mixture/_bayesian_mixture.py`` ``_estimate_log_prob`` / ``_estimate_log_weights``): per
+    component it adds ``-0.5 F log(nu) + 0.5 (F log 2 + sum_i digamma(0.5 (nu - i)) - F / kappa)`` to the log-density -- kept
+    as ``bayes_log_prob_const`` and folded into ``log_det`` -- and takes the digamma form of the log-weights."""
 
     def __init__(self, model):
-        from sklearn.mixture import GaussianMixture
+        from sklearn.decomposition import PCA
+        from sklearn.mixture import BayesianGaussianMixture, GaussianMixture
         from sklearn.pipeline import Pipeline
         from sklearn.preprocessing import StandardScaler
-        steps = list(model.steps) if isinstance(model, Pipeline) else [('model', model)]
-        gmm = steps[-1][1]
-        if type(gmm) is not GaussianMixture or gmm.covariance_type != 'full' or not hasattr(gmm, 'precisions_cholesky_'):
-            raise TypeError('not a fitted full-covariance GaussianMixture')
-        if len(steps) > 2 or any(type(st) is not StandardScaler for _, st in steps[:-1]):
-            raise TypeError('only an optional StandardScaler in front of the mixture is evaluated on the device')
+        steps = [st for _, st in model.steps] if isinstance(model, Pipeline) else [model]
+        gmm = steps[-1]
+        if type(gmm) not in (GaussianMixture, BayesianGaussianMixture) or gmm.covariance_type != 'full' \
+                or not hasattr(gmm, 'precisions_cholesky_'):
+            raise TypeError('not a fitted full-covariance GaussianMixture / BayesianGaussianMixture')
+        front = steps[:-1]
+        scaler = front.pop(0) if front and type(front[0]) is StandardScaler else None
+        pca = front.pop(0) if front and type(front[0]) is PCA else None
+        if front:
+            raise TypeError('only an optional StandardScaler and an optional PCA, in that order, in front of the mixture are '
+                            'evaluated on the device')
         n_comp, n_feat = gmm.means_.shape
-        if n_feat > 256 or n_comp > 16:
+        n_in = int(pca.components_.shape[1]) if pca is not None else int(n_feat)
+        if pca is not None and pca.components_.shape[0] != n_feat:
+            raise TypeError('the PCA does not produce the columns the mixture was fitted on')
+        if n_in > 256 or n_comp > 16:
             raise TypeError('device class model: at most 256 features and 16 classes')
-        self.n_features, self.n_classes = int(n_feat), int(n_comp)
+        self.n_features, self.n_classes, self.n_inputs = int(n_feat), int(n_comp), n_in
         self.classes = getattr(model, 'classes_', None)
         par = GmmParams()
         par.n_features, par.n_classes = self.n_features, self.n_classes
+        par.n_inputs = n_in if pca is not None else 0
         self.scaler_mean = self.scaler_scale = None
-        if len(steps) == 2:
-            scaler = steps[0][1]
+        if scaler is not None:
             if scaler.with_mean:
                 self.scaler_mean = np.ascontiguousarray(scaler.mean_, dtype=np.float64)
             if scaler.with_std:
                 self.scaler_scale = np.ascontiguousarray(scaler.scale_, dtype=np.float64)
+        self.pca_components_t = self.pca_shift = self.pca_scale = None
+        if pca is not None:
+            components = np.asarray(pca.components_, dtype=np.float64)
+            self.pca_components_t = np.ascontiguousarray(components.T)
+            mean = np.zeros(n_in) if pca.mean_ is None else np.asarray(pca.mean_, dtype=np.float64)
+            self.pca_shift = np.ascontiguousarray((np.reshape(mean, (1, -1)) @ components.T)[0])
+            if pca.whiten:
+                scale = np.sqrt(np.asarray(pca.explained_variance_, dtype=np.float64))
+                min_scale = np.finfo(scale.dtype).eps
+                scale[scale < min_scale] = min_scale
+                self.pca_scale = np.ascontiguousarray(scale)
         chol = np.ascontiguousarray(gmm.precisions_cholesky_, dtype=np.float64)
         self.prec_chol = chol
         self.mu_proj = np.ascontiguousarray([np.dot(mu, pc) for mu, pc in zip(gmm.means_, chol)], dtype=np.float64)
-        self.log_det = np.ascontiguousarray(np.sum(np.log(chol.reshape(n_comp, -1)[:, ::n_feat + 1]), 1), dtype=np.float64)
-        self.log_weights = np.ascontiguousarray(np.log(gmm.weights_), dtype=np.float64)
+        log_det = np.sum(np.log(chol.reshape(n_comp, -1)[:, ::n_feat + 1]), 1)
+        self.bayes_log_prob_const = None
+        if type(gmm) is BayesianGaussianMixture:
+            from scipy.special import digamma
+            log_lambda = n_feat * np.log(2.0) + np.sum(
+                digamma(0.5 * (gmm.degrees_of_freedom_ - np.arange(0, n_feat)[:, np.newaxis])), 0)
+            self.bayes_log_prob_const = -0.5 * n_feat * np.log(gmm.degrees_of_freedom_) \
+                + 0.5 * (log_lambda - n_feat / gmm.mean_precision_)
+            log_det = log_det + self.bayes_log_prob_const
+            log_weights = gmm._estimate_log_weights()
+        else:
+            log_weights = np.log(gmm.weights_)
+        self.log_det = np.ascontiguousarray(log_det, dtype=np.float64)
+        self.log_weights = np.ascontiguousarray(log_weights, dtype=np.float64)
         self.const_term = float(n_feat * np.log(2 * np.pi))
-        for name in ('scaler_mean', 'scaler_scale', 'prec_chol', 'mu_proj', 'log_det', 'log_weights'):
+        for name in ('scaler_mean', 'scaler_scale', 'prec_chol', 'mu_proj', 'log_det', 'log_weights', 'pca_components_t',
+                     'pca_shift', 'pca_scale'):
             setattr(par, name, _ptr(getattr(self, name)))
         par.const_term = self.const_term
         self.params = par

@@ -369,10 +369,8 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         return -1;
     }
     const int F = need_features ? im->feat_F : 0;
-    if (gmm && (gmm->n_features != F || gmm->n_classes != C)) {
-        set_error("segment: class model does not match the resident features / number of classes");
-        return -1;
-    }
+    if (gmm && check_gmm(gmm, F, C)) return -1;
+    const int n_in = gmm ? gmm->n_inputs : 0, Fm = gmm ? gmm->n_features : F;       // (PCA: table columns it reads, mixture dimension)
     if (check_pairwise(pairwise, C)) return -1;
     // the graph: prepared ahead (imsegm_image2d_graph_prepare, same label map, room for the edges asked for) or built here
     const bool prepared = im->graph_ready && im->gplan.K == K && (edge_capacity <= 0 || im->gplan.Ecap >= edge_capacity);
@@ -384,9 +382,9 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
     hipStream_t st = ctx->stream;
     const size_t n = im->n;
     // ---- host -> device parameter block (one pinned staging copy), the scratch of the terms and the cut behind it
-    bh.C = C; bh.F = F;
-    bh.par = param_block(C, F, gmm ? 0 : K);
-    bh.scr = terms_scratch(bh.par, K, C, F, g.Ecap, gmm == nullptr);
+    bh.C = C; bh.F = F; bh.Fm = n_in ? Fm : 0;
+    bh.par = param_block(C, Fm, gmm ? 0 : K, n_in);
+    bh.scr = terms_scratch(bh.par, K, C, F, g.Ecap, gmm == nullptr, n_in ? Fm : 0);
     const size_t up_bytes = bh.par.bytes;
     if (im->seg.ensure(bh.scr.end + 256)) return -1;
     bh.base = im->seg.as<unsigned char>();

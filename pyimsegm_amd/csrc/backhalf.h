@@ -16,17 +16,25 @@ int decode_edge_type(int edge_type, int *edge_code, int *spatial_norm);
 // ---- host -> device parameter block of one image (offsets; all members size_t: the struct is part of a memcmp key)
 struct ParamBlock {
     size_t o_misc;      // K | E | status | gc status | energy (8) ... scalars[8] at +64: initialised by the same copy
-    size_t o_pw, o_sm, o_cl, o_sc, o_pc, o_mp, o_ld, o_lw, o_pr, bytes;
+    size_t o_pw, o_sm, o_cl, o_sc, o_pc, o_mp, o_ld, o_lw, o_pr, o_ct, o_ps, bytes;
 };
-// proba_rows: K when probabilities (at o_pr) are uploaded instead of a mixture, else 0
-ParamBlock param_block(int C, int F, int proba_rows);
+// F: dimension of the mixture; proba_rows: K when probabilities (at o_pr) are uploaded instead of a mixture, else 0;
+// n_inputs: columns the PCA in front of the mixture reads (scaler vectors of that length, components_.T at o_ct, shift | scale at
+// o_ps), 0 without one
+ParamBlock param_block(int C, int F, int proba_rows, int n_inputs = 0);
 
 // ---- device scratch of the terms and the cut behind the parameter block (offsets from the block's base, 64-byte aligned)
 struct TermsScratch {
-    size_t d_proba, d_unary, d_unary_i, d_w, d_wi, d_edist, d_elen, d_gl, d_lut, d_fstd, d_work, end;
+    size_t d_proba, d_unary, d_unary_i, d_w, d_wi, d_edist, d_elen, d_gl, d_lut, d_fstd, d_work, d_red, end;
 };
-// proba_in_params: d_proba is P.o_pr
-TermsScratch terms_scratch(const ParamBlock &P, int K, int C, int F, int Ecap, bool proba_in_params);
+// F: columns of the feature table; proba_in_params: d_proba is P.o_pr; reduced_cols: columns of the projected rows (d_red), 0
+// without a PCA
+TermsScratch terms_scratch(const ParamBlock &P, int K, int C, int F, int Ecap, bool proba_in_params, int reduced_cols = 0);
+
+// table width and mixture dimension a class model asks for
+inline int gmm_inputs(const imsegm_gmm *g) { return g->n_inputs ? g->n_inputs : g->n_features; }
+// limits of the model and of its PCA (sets the error text)
+int check_gmm(const imsegm_gmm *gmm, int table_columns, int C);
 
 // ---- the chain: launch_gc_terms -> launch_alpha_expansion / launch_unary_argmin -> launch_label_lut -> gathers
 struct BackHalf {
@@ -45,7 +53,8 @@ struct BackHalf {
     size_t n;
     int32_t *segm_out;               // [n]
     double *soft_out;                // [n][C] or null (one image only)
-    int K_cap, Ecap, C, F, ndim, edge_code, spatial_norm, use_graphcut;
+    int K_cap, Ecap, C, F, ndim, edge_code, spatial_norm, use_graphcut;      // F: columns of the feature table
+    int Fm = 0;                      // dimension of the mixture behind a PCA, 0: F
     double edge_cost;
     ZBatch zb;                       // zs != 0: a batch (the label counts differ: the cut reads K_dev)
 

@@ -25,7 +25,24 @@ int decode_edge_type(int edge_type, int *edge_code, int *spatial_norm)
     return 0;
 }
 
-ParamBlock param_block(int C, int F, int proba_rows)
+int check_gmm(const imsegm_gmm *gmm, int table_columns, int C)
+{
+    if (gmm_inputs(gmm) != table_columns || gmm->n_classes != C) {
+        set_error("class model does not match the resident features / number of classes");
+        return -1;
+    }
+    if (gmm->n_features < 1 || gmm->n_features > 256 || gmm->n_inputs < 0 || gmm->n_inputs > 256 || C > 16) {
+        set_error("device class model: at most 256 features and 16 classes");
+        return -1;
+    }
+    if (gmm->n_inputs && (gmm->n_features > gmm->n_inputs || !gmm->pca_components_t || !gmm->pca_shift)) {
+        set_error("class model with a PCA: 1 <= n_features <= n_inputs <= 256, components and shift are required");
+        return -1;
+    }
+    return 0;
+}
+
+ParamBlock param_block(int C, int F, int proba_rows, int n_inputs)
 {
     ParamBlock P;
     size_t o = 0;
@@ -34,12 +51,14 @@ ParamBlock param_block(int C, int F, int proba_rows)
     P.o_pw = take((size_t)C * C * 8);
     P.o_sm = take((size_t)C * C * 4);
     P.o_cl = take((size_t)C * 4);
-    P.o_sc = take((size_t)2 * F * 8);
+    P.o_sc = take((size_t)2 * (n_inputs ? n_inputs : F) * 8);
     P.o_pc = take((size_t)C * F * F * 8);
     P.o_mp = take((size_t)C * F * 8);
     P.o_ld = take((size_t)C * 8);
     P.o_lw = take((size_t)C * 8);
     P.o_pr = take((size_t)proba_rows * C * 8);
+    P.o_ct = take((size_t)n_inputs * F * 8);
+    P.o_ps = take(n_inputs ? (size_t)2 * F * 8 : 0);
     P.bytes = o;
     return P;
 }
@@ -48,7 +67,7 @@ void param_fill(BackHalf &b, unsigned char *row, int K, const double *pairwise, 
                 const double *proba)
 {
     const ParamBlock &P = b.par;
-    const int C = b.C, F = b.F;
+    const int C = b.C, F = b.Fm ? b.Fm : b.F, Fs = b.F;       // (mixture dimension, scaler length)
     reinterpret_cast<int32_t *>(row + P.o_misc)[0] = K;          // E = 0 | status = 0 | gc status = 0 | energy = 0 behind it
     memcpy(row + P.o_pw, pairwise, (size_t)C * C * 8);
     int32_t *si = reinterpret_cast<int32_t *>(row + P.o_sm);
@@ -61,8 +80,13 @@ void param_fill(BackHalf &b, unsigned char *row, int K, const double *pairwise, 
     b.metric = smooth_is_metric(si, C);
     if (classes_lut) memcpy(row + P.o_cl, classes_lut, (size_t)C * 4);
     if (gmm) {
-        if (gmm->scaler_mean) memcpy(row + P.o_sc, gmm->scaler_mean, (size_t)F * 8);
-        if (gmm->scaler_scale) memcpy(row + P.o_sc + (size_t)F * 8, gmm->scaler_scale, (size_t)F * 8);
+        if (gmm->scaler_mean) memcpy(row + P.o_sc, gmm->scaler_mean, (size_t)Fs * 8);
+        if (gmm->scaler_scale) memcpy(row + P.o_sc + (size_t)Fs * 8, gmm->scaler_scale, (size_t)Fs * 8);
+        if (gmm->n_inputs) {
+            memcpy(row + P.o_ct, gmm->pca_components_t, (size_t)Fs * F * 8);
+            memcpy(row + P.o_ps, gmm->pca_shift, (size_t)F * 8);
+            if (gmm->pca_scale) memcpy(row + P.o_ps + (size_t)F * 8, gmm->pca_scale, (size_t)F * 8);
+        }
         memcpy(row + P.o_pc, gmm->prec_chol, (size_t)C * F * F * 8);
         memcpy(row + P.o_mp, gmm->mu_proj, (size_t)C * F * 8);
         memcpy(row + P.o_ld, gmm->log_det, (size_t)C * 8);
@@ -72,7 +96,7 @@ void param_fill(BackHalf &b, unsigned char *row, int K, const double *pairwise, 
     }
 }
 
-TermsScratch terms_scratch(const ParamBlock &P, int K, int C, int F, int Ecap, bool proba_in_params)
+TermsScratch terms_scratch(const ParamBlock &P, int K, int C, int F, int Ecap, bool proba_in_params, int reduced_cols)
 {
     TermsScratch S;
     size_t d = P.bytes;
@@ -88,6 +112,7 @@ TermsScratch terms_scratch(const ParamBlock &P, int K, int C, int F, int Ecap, b
     S.d_lut = take((size_t)K * 4);
     S.d_fstd = take((size_t)2 * std::max(F, 1) * 8);
     S.d_work = take(alpha_expansion_work_bytes(K, Ecap));
+    S.d_red = take((size_t)K * reduced_cols * 8);
     S.end = d;
     return S;
 }
@@ -103,7 +128,7 @@ int backhalf_enqueue(imsegm_ctx *ctx, const BackHalf &b)
     TermsArgs a;
     memset(&a, 0, sizeof(a));
     a.zs = b.zb.zs;
-    a.Kp = b.K_dev; a.K_cap = b.K_cap; a.Ep = b.E_dev; a.edge_capacity = b.Ecap; a.F = b.F; a.C = b.C;
+    a.Kp = b.K_dev; a.K_cap = b.K_cap; a.Ep = b.E_dev; a.edge_capacity = b.Ecap; a.F = b.Fm ? b.Fm : b.F; a.F_tab = b.F; a.C = b.C;
     a.features = b.features;
     a.gmm = gmm ? 1 : 0;
     if (gmm) {
@@ -114,6 +139,12 @@ int backhalf_enqueue(imsegm_ctx *ctx, const BackHalf &b)
         a.log_det = b.at<double>(P.o_ld);
         a.log_w = b.at<double>(P.o_lw);
         a.const_term = gmm->const_term;
+        if (gmm->n_inputs) {
+            a.pca_ct = b.at<double>(P.o_ct);
+            a.pca_shift = b.at<double>(P.o_ps);
+            a.pca_scale = gmm->pca_scale ? b.at<double>(P.o_ps) + a.F : nullptr;
+            a.reduced = b.at<double>(S.d_red);
+        }
     }
     a.proba = b.at<double>(S.d_proba);
     a.edge_type = b.edge_code; a.spatial_norm = b.spatial_norm; a.edge_cost = b.edge_cost;

@@ -44,7 +44,8 @@ struct Layout {
     int Kb, Ecap;                    // most labels an image can end up with, edge table rows
 };
 
-Layout make_layout(int H, int W, size_t elem, int K_grid, size_t n_tiles, long min_size, int C, int F)
+// F: columns of the feature table; Fm / n_in: dimension of the mixture and columns its PCA reads (n_in 0: no PCA, Fm = F)
+Layout make_layout(int H, int W, size_t elem, int K_grid, size_t n_tiles, long min_size, int C, int F, int Fm, int n_in)
 {
     Layout L;
     memset(&L, 0, sizeof(L));        // (the bytes are compared: the key of the zeroed arena)
@@ -69,8 +70,8 @@ Layout make_layout(int H, int W, size_t elem, int K_grid, size_t n_tiles, long m
     L.featK = take(Kb * (size_t)std::max(F, 1) * 8 + 64);
     L.segm_out = take(n * 4);
     // ---- the back half, relative to L.seg
-    L.par = param_block(C, F, 0);
-    L.scr = terms_scratch(L.par, L.Kb, C, F, L.Ecap, false);
+    L.par = param_block(C, Fm, 0, n_in);
+    L.scr = terms_scratch(L.par, L.Kb, C, F, L.Ecap, false, n_in ? Fm : 0);
     size_t q = L.scr.end;
     auto sub = [&](size_t bytes) { size_t at = q; q += al64(bytes); return at; };
     L.d_edges = sub(E * 8);
@@ -186,10 +187,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
     BackHalf bh;
     if (decode_edge_type(edge_type, &bh.edge_code, &bh.spatial_norm)) return -1;
     const int F = color_feature_columns(feature_mask);
-    if (gmm->n_features != F || gmm->n_classes != C) {
-        set_error("segment: class model does not match the resident features / number of classes");
-        return -1;
-    }
+    if (check_gmm(gmm, F, C)) return -1;
     if (check_pairwise(pairwise, C)) return -1;
     Taps tz, ty, tx;
     if (fill_taps(tz, taps, radius) || fill_taps(ty, taps, radius) || fill_taps(tx, taps, radius)) return -1;
@@ -209,7 +207,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
         set_error("batch2d_run_color: superpixels of under two pixels take the single-image path");
         return -1;
     }
-    const Layout L = make_layout(H, W, es, K, geo.n_tiles, min_size, C, F);
+    const Layout L = make_layout(H, W, es, K, geo.n_tiles, min_size, C, F, gmm->n_features, gmm->n_inputs);
     const size_t slice = L.total;
     const size_t stage_row = al256(std::max<size_t>(L.par.bytes, 256));      // per image: parameter block in, counters out
     const size_t arena_bytes = slice * bt->B + stage_row * bt->B + 4096;
@@ -329,7 +327,7 @@ int imsegm_batch2d_run_color(imsegm_batch2d *bt, int n_images, const void *const
     if (batch_pinned(bt, stage_row * n_images + 64)) return -1;
     unsigned char *host = static_cast<unsigned char *>(bt->pinned);
     memset(host, 0, stage_row);
-    bh.par = L.par; bh.scr = L.scr; bh.C = C; bh.F = F;
+    bh.par = L.par; bh.scr = L.scr; bh.C = C; bh.F = F; bh.Fm = gmm->n_inputs ? gmm->n_features : 0;
     param_fill(bh, host, nl[0], pairwise, classes_lut, gmm, nullptr);
     for (int b = 1; b < n_images; ++b) {
         memcpy(host + (size_t)b * stage_row, host, stage_row);

@@ -346,11 +346,11 @@ struct TermsArgs {
     int K_cap;                     // upper bound of it known to the host (launch geometry)
     const int *Ep;                 // number of edges (device)
     int edge_capacity;
-    int F, C;
-    const double *features;        // [K][F]
-    // class model (gmm != 0): StandardScaler + full-covariance Gaussian mixture
+    int F, C;                      // F: the dimension the mixture works in
+    const double *features;        // [K][F_tab]
+    // class model (gmm != 0): StandardScaler + (PCA) + full-covariance Gaussian mixture
     int gmm;
-    const double *scaler_mean, *scaler_scale;   // [F] or null
+    const double *scaler_mean, *scaler_scale;   // [F_tab] or null
     const double *prec_chol;       // [C][F][F]
     const double *mu_proj;         // [C][F] = means @ prec_chol (host, as scikit-learn forms it)
     const double *log_det;         // [C]
@@ -374,7 +374,13 @@ struct TermsArgs {
     int smooth_max;                // max |int(pairwise * 100)|
     int32_t *status;               // bit 0: smoothness term above GCO_MAX_ENERGYTERM, bit 1: edge list overflow
     double *scalars;               // [8] debug: mean len, mean dist, std dist, umax, wmax, dwf
-    double *fstd;                  // [2][F] scratch (edge type 'features')
+    double *fstd;                  // [2][F_tab] scratch (edge type 'features')
+    // columns of the feature table: F, or with a PCA in front of the mixture (pca_ct != null) the inputs of the projection
+    int F_tab;
+    const double *pca_ct;          // [F_tab][F] components_.T
+    const double *pca_shift;       // [F] mean_ @ components_.T
+    const double *pca_scale;       // [F] whitening scale or null
+    double *reduced;               // [K][F] scratch: the projected rows k_gmm_proba reads in place of the table
     size_t zs;                     // several images per launch (ZBatch): bytes between the buffers of consecutive images
 };
 int launch_features_assemble(const double *mean, const double *energy, const double *var, int K, int mask, double *out,

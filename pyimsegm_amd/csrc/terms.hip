@@ -4,8 +4,10 @@
 // gathers  is enqueued on one stream without a host round trip (api.hip imsegm_image2d_segment).
 //
 // Replaces, in /root/reference/imsegm/graph_cuts.py:
-//   model.predict_proba(features)  for sklearn Pipeline([StandardScaler,] GaussianMixture(covariance_type='full'))
-//       (:73-163 estim_class_model builds exactly this; pipelines.py:96,232 call it)
+//   model.predict_proba(features)  for sklearn Pipeline([StandardScaler,] [PCA,] mixture), the mixture a GaussianMixture or a
+//       BayesianGaussianMixture with covariance_type='full' (:73-163 estim_class_model builds these from estim_model and
+//       pca_coef; pipelines.py:96,232 call it).  The PCA is k_pca_project in front of k_gmm_proba; the Bayesian mixture differs
+//       from the plain one by per-component constants the host folds into log_det and log_w (_hip.DeviceGmm).
 //   compute_unary_cost :523-540, compute_edge_model :383-439, compute_spatial_dist :303-336,
 //   compute_edge_weights :616-657 (edge types '', const, spatial, model[_l1|_l2|_lT], features), edge_cost :722
 // and the float -> integer conversion of gco-wrapper's pygco.cut_general_graph (down_weight_factor, truncation).
@@ -418,11 +420,82 @@ __global__ void __launch_bounds__(256) k_gmm_proba(TermsArgs a)
     }
 }
 
+// PCA.transform behind StandardScaler.transform, in front of the mixture (estim_class_model's pca_coef).  scikit-learn 1.7
+// sklearn/decomposition/_base.py:147-165 (_BasePCA._transform, called by transform :116-145 with x_is_centered=False):
+//     X_transformed = X @ self.components_.T                                      :148
+//     X_transformed -= xp.reshape(self.mean_, (1, -1)) @ self.components_.T      :155   (centring AFTER the projection)
+//     scale = sqrt(explained_variance_), clipped from below at eps; X_transformed /= scale      :161-164 (whiten only)
+// The host forms the second product (pca_shift) and the clipped scale (pca_scale) with those numpy expressions; here per row
+// y_j = sum_f x_f Ct[f][j] sequentially in ascending f (a plain dot product: the result does not depend on the launch shape), then
+// the subtraction, then the division.  Lanes and rows per wave as in k_gmm_proba: lane l keeps the inputs l, l + 64, ... of the
+// SPW rows of its wave and owns the output columns l, l + 64, ... (F <= F_tab <= 64 NF), so a row of components_.T is read once
+// for all of them, by consecutive lanes at consecutive addresses.  The K x F result is the table k_gmm_proba reads next.
+template <int NF, int SPW>
+__global__ void __launch_bounds__(256) k_pca_project(TermsArgs a)
+{
+    zshift_terms(a);
+    ZSHIFT(a.pca_ct, a.zs); ZSHIFT(a.pca_shift, a.zs); ZSHIFT(a.pca_scale, a.zs); ZSHIFT(a.reduced, a.zs);
+    const int K = *a.Kp, I = a.F_tab, F = a.F;
+    const int lane = threadIdx.x & 63;
+    const int k0 = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * SPW;
+    if (k0 >= K) return;
+    double xv[SPW][NF];
+#pragma unroll
+    for (int s = 0; s < SPW; ++s) {
+        const int k = min(k0 + s, K - 1);                // (the last wave repeats the last row; only k < K is written)
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int f = lane + 64 * i;
+            double v = 0.0;
+            if (f < I) {
+                v = a.features[(size_t)k * I + f];
+                if (a.scaler_mean) v = v - a.scaler_mean[f];
+                if (a.scaler_scale) v = v / a.scaler_scale[f];
+            }
+            xv[s][i] = v;
+        }
+    }
+    double y[SPW][NF];
+#pragma unroll
+    for (int s = 0; s < SPW; ++s)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) y[s][j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const int count = min(64, I - 64 * i);           // (uniform)
+        for (int l = 0; l < count; ++l) {
+            const double *row = a.pca_ct + (size_t)(64 * i + l) * F;
+            double pr[NF];
+#pragma unroll
+            for (int j = 0; j < NF; ++j) pr[j] = lane + 64 * j < F ? row[lane + 64 * j] : 0.0;
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) {
+                const double xf = __shfl(xv[s][i], l, 64);
+#pragma unroll
+                for (int j = 0; j < NF; ++j)
+                    if (lane + 64 * j < F) y[s][j] += xf * pr[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+        const int col = lane + 64 * j;
+        if (col >= F) continue;
+        const double shift = a.pca_shift[col], scale = a.pca_scale ? a.pca_scale[col] : 1.0;
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) {
+            double v = y[s][j] - shift;
+            if (a.pca_scale) v = v / scale;
+            if (k0 + s < K) a.reduced[(size_t)(k0 + s) * F + col] = v;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(TM_THREADS) k_gc_terms(TermsArgs a)
 {
     zshift_terms(a);
     __shared__ double scratch[TM_THREADS / 64];
-    const int K = *a.Kp, C = a.C, F = a.F;
+    const int K = *a.Kp, C = a.C, F = a.F_tab;           // (F: the columns of the table the 'features' edges read)
     int E = *a.Ep;
     if (E > a.edge_capacity) {
         if (threadIdx.x == 0) atomicOr(a.status, 2);
@@ -721,21 +794,35 @@ int launch_graph_csr(uint32_t *bitmap, const int *K_dev, int K_cap, int words, i
     return 0;
 }
 
+// rows per wave and the instantiation for `width` columns per row (k_gmm_proba: the mixture's dimension; k_pca_project: the table's)
+template <typename K1, typename K2, typename K3, typename K4>
+static void launch_rows_per_wave(int width, K1 k1, K2 k2, K3 k3, K4 k4, const TermsArgs &a, hipStream_t st, int nz)
+{
+    // (few features: a wave per superpixel -- the model is a few hundred bytes and more waves hide more latency: 13 against
+    // 22 us for 2 000 x 9; many features: four superpixels per wave share the rows of the precision factor)
+    const int spw = width <= 64 ? 1 : 4;
+    const dim3 grid(cdiv((long)cdiv(a.K_cap, spw) * 64, 256), 1, nz);
+    if (width <= 64) hipLaunchKernelGGL(k1, grid, 256, 0, st, a);
+    else if (width <= 128) hipLaunchKernelGGL(k2, grid, 256, 0, st, a);
+    else if (width <= 192) hipLaunchKernelGGL(k3, grid, 256, 0, st, a);
+    else hipLaunchKernelGGL(k4, grid, 256, 0, st, a);
+}
+
 int launch_gc_terms(const TermsArgs &a, hipStream_t st, int nz)
 {
-    if (a.F > 256 || a.C > 16) {
+    if (a.F > 256 || a.F_tab > 256 || a.C > 16 || (a.pca_ct && (a.F < 1 || a.F > a.F_tab || !a.reduced))) {
         set_error("device class model: at most 256 features and 16 classes");
         return -1;
     }
     if (a.gmm) {
-        // (few features: a wave per superpixel -- the model is a few hundred bytes and more waves hide more latency: 13 against
-        // 22 us for 2 000 x 9; many features: four superpixels per wave share the rows of the precision factor)
-        const int spw = a.F <= 64 ? 1 : 4;
-        const dim3 grid(cdiv((long)cdiv(a.K_cap, spw) * 64, 256), 1, nz);
-        if (a.F <= 64) hipLaunchKernelGGL((k_gmm_proba<1, 1>), grid, 256, 0, st, a);
-        else if (a.F <= 128) hipLaunchKernelGGL((k_gmm_proba<2, 4>), grid, 256, 0, st, a);
-        else if (a.F <= 192) hipLaunchKernelGGL((k_gmm_proba<3, 4>), grid, 256, 0, st, a);
-        else hipLaunchKernelGGL((k_gmm_proba<4, 4>), grid, 256, 0, st, a);
+        TermsArgs m = a;
+        if (a.pca_ct) {
+            // scaler + projection into a.reduced, then the mixture on that table with nothing left to scale
+            launch_rows_per_wave(a.F_tab, k_pca_project<1, 1>, k_pca_project<2, 4>, k_pca_project<3, 4>, k_pca_project<4, 4>, a, st, nz);
+            m.features = a.reduced;
+            m.scaler_mean = m.scaler_scale = nullptr;
+        }
+        launch_rows_per_wave(m.F, k_gmm_proba<1, 1>, k_gmm_proba<2, 4>, k_gmm_proba<3, 4>, k_gmm_proba<4, 4>, m, st, nz);
     }
     if (nz == 1 && a.zs == 0 && a.edge_type != 5 && a.K_cap >= TERMS_WIDE_FROM && a.edge_capacity >= 2 * TM_THREADS && !knobs().terms_one_workgroup) {
         // the graph of a volume: the element-wise steps on the whole device, the sums in k_gc_terms' order (see k_terms_elem)

@@ -39,20 +39,25 @@ _device_models = None
 
 
 def _device_gmm(model):
-    """:class:`_hip.DeviceGmm` of a fitted ``Pipeline([StandardScaler,] GaussianMixture('full'))`` (cached per model
-    object as long as its parameters are the same arrays), or None when the model has to be evaluated by scikit-learn"""
+    """:class:`_hip.DeviceGmm` of a fitted ``Pipeline([StandardScaler,] [PCA,] mixture)`` with a full-covariance Gaussian or
+    Bayesian Gaussian mixture -- what :func:`graph_cuts.estim_class_model` builds for 'GMM*' / 'BGM' with or without ``pca_coef``
+    -- (cached per model object as long as its parameters are the same arrays), or None when the model has to be evaluated by
+    scikit-learn"""
     global _device_models
     import weakref
     if _device_models is None:
         _device_models = weakref.WeakKeyDictionary()
     try:
-        last = model.steps[-1][1] if hasattr(model, 'steps') else model
-        chol = getattr(last, 'precisions_cholesky_', None)
+        # (every fitted array the device constants are formed from, of every step: a refit replaces them)
+        steps = [st for _, st in model.steps] if hasattr(model, 'steps') else [model]
+        key = [getattr(st, name, None) for st in steps
+               for name in ('mean_', 'scale_', 'components_', 'explained_variance_', 'precisions_cholesky_', 'means_', 'weights_',
+                            'degrees_of_freedom_', 'mean_precision_', 'weight_concentration_')]
         hit = _device_models.get(model)
-        if hit is not None and hit[0] is chol:
+        if hit is not None and len(hit[0]) == len(key) and all(a is b for a, b in zip(hit[0], key)):
             return hit[1]
         dev = _hip.DeviceGmm(model)
-        _device_models[model] = (chol, dev)
+        _device_models[model] = (key, dev)
         return dev
     except TypeError:
         return None
@@ -65,7 +70,8 @@ def _segment_color2d_one_call(image, model, dict_features, sp_size, sp_regul, gc
                               with_session=None):
     """``segment_color2d_slic_features_model_graphcut`` as ONE call into the library (:meth:`_hip.Image2D.run_color`) when
     everything it needs lives on the device: uint8 / float64 colour image, colour mean / std / energy features, a
-    scaler + full-covariance mixture, an edge type the device evaluates.  Returns None when the general path is needed.
+    scaler + (PCA) + full-covariance mixture reading exactly those columns, an edge type the device evaluates.  Returns None
+    when the general path is needed.
     ``with_session(sess)`` is called before the session is recycled (the label map is still in its HBM buffer then)."""
     from pyimsegm_amd.graph_cuts import compute_pairwise_cost
     from pyimsegm_amd.superpixels import SLIC_MAX_ITER, SLIC_START_LABEL, _slic_params
@@ -77,7 +83,7 @@ def _segment_color2d_one_call(image, model, dict_features, sp_size, sp_regul, gc
     if sp_regul <= 0.:
         raise ValueError('slic. regularisation must be positive')
     gmm = _device_gmm(model)
-    if gmm is None or gmm.n_features != 3 * len(set(flags)):
+    if gmm is None or gmm.n_inputs != 3 * len(set(flags)):
         return None
     if image.dtype != np.uint8 and not bool(np.isfinite(image.sum(dtype=np.float64))):
         return None
@@ -131,7 +137,7 @@ def _segment_color2d_batch_call(images, model, dict_features, sp_size, sp_regul,
     if sp_regul <= 0.:
         raise ValueError('slic. regularisation must be positive')
     gmm = _device_gmm(model)
-    if gmm is None or gmm.n_features != 3 * len(set(flags)):
+    if gmm is None or gmm.n_inputs != 3 * len(set(flags)):
         return None
     if first.dtype != np.uint8 and not all(bool(np.isfinite(im.sum(dtype=np.float64))) for im in images):
         return None
@@ -607,7 +613,7 @@ def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeli
 
 
 def pipe_gray3d_slic_features_model_graphcut(image, nb_classes, dict_features, spacing=(12, 1, 1), sp_size=15, sp_regul=0.2,
-                                             gc_regul=0.1, fit_on=None):
+                                             gc_regul=0.1, fit_on=None, pca_coef=None, estim_model='GMM'):
     """ complete pipeline on a gray volume: supervoxels, features, mixture model, GraphCut
     (reference ``pipelines.py:382-431``)
 
@@ -623,13 +629,17 @@ def pipe_gray3d_slic_features_model_graphcut(image, nb_classes, dict_features, s
     :param float sp_regul: regularisation in (0, 1): 0 elastic, 1 nearly cubic segments
     :param float gc_regul: GraphCut regularisation
     :param str fit_on: where the mixture is fitted, see :func:`graph_cuts.estim_class_model`
+    :param float pca_coef: (not in the reference's signature) range (0, 1) or None: a PCA step in front of the mixture, as in
+        :func:`pipe_color2d_slic_features_model_graphcut`
+    :param str estim_model: (not in the reference's signature) model family of :func:`graph_cuts.estim_class_model`
     :return ndarray: int32 class per voxel, D x H x W
     """
     logging.info('PIPELINE Superpixels-Features-GraphCut')
     image = np.asarray(image)
     sess = _open_volume(image, reuse=True)
     try:
-        segm = _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on)
+        segm = _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on, pca_coef,
+                                  estim_model)
     except Exception:
         sess.close()
         raise
@@ -674,7 +684,13 @@ def _result_array(shape, dtype=np.int32):
     return _touched_result(shape, dtype)
 
 
-def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on=None):
+def _reduced_or_bayesian(gmm):
+    """the device model has a PCA step or a Bayesian mixture -- the model shapes whose volume path has no pinned host result"""
+    return gmm is not None and (gmm.params.n_inputs != 0 or gmm.bayes_log_prob_const is not None)
+
+
+def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size, sp_regul, gc_regul, fit_on=None, pca_coef=None,
+                       estim_model='GMM'):
     segm_buf, segm_ready = _result_array(sess.shape)
     _run_slic3d(sess, sp_size, sp_regul, spacing)
     logging.info('extract segments/superpixels features.')
@@ -703,9 +719,20 @@ def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size,
         fused = False
         logging.info('volume graph by neighbour tables (%s)', ex)
 
-    model = estim_class_model(features, nb_classes, fit_on=fit_on, _ctx=sess.ctx)       # (a device fit: same stream, behind the graph)
-    proba = predict_proba(model, features)          # (scikit-learn's arithmetic without its per-call validation: same bits)
-    logging.debug('list of probabilities: %r', proba.shape)
+    model = estim_class_model(features, nb_classes, estim_model, pca_coef, fit_on=fit_on, _ctx=sess.ctx)    # (a device fit: same stream, behind the graph)
+    # a model with a PCA step or a Bayesian mixture is evaluated by the fused call itself: the NORMALISED table (what the model
+    # was fitted on) becomes the session's resident table -- K x F up instead of the table's way through scikit-learn and K x C
+    # up.  The scaler + plain mixture keeps the host evaluation its pinned class maps were produced with.
+    gmm = _device_gmm(model) if fused else None
+    on_device = _reduced_or_bayesian(gmm) and gmm.n_inputs == features.shape[1] and 3 <= features.shape[1] <= 256
+    proba = None
+
+    def host_proba():
+        nonlocal proba
+        if proba is None:
+            proba = predict_proba(model, features)      # (scikit-learn's arithmetic without its per-call validation: same bits)
+            logging.debug('list of probabilities: %r', proba.shape)
+        return proba
 
     segm = None
     if fused:
@@ -713,13 +740,16 @@ def _gray3d_on_session(sess, image, nb_classes, dict_features, spacing, sp_size,
             # fused: unary / edge terms ('model' edges), alpha-expansion and the gather in one call on the prepared graph
             from pyimsegm_amd.graph_cuts import compute_pairwise_cost
             use_gc = not (np.isscalar(gc_regul) and gc_regul <= 0)
+            pairwise = compute_pairwise_cost(gc_regul, (features.shape[0], gmm.n_classes if on_device else host_proba().shape[1]))
+            if on_device:
+                sess.put_features(np.ascontiguousarray(features, dtype=np.float64))
             segm_ready()
-            segm = sess.segment(compute_pairwise_cost(gc_regul, proba.shape), 'model', proba=proba, use_graphcut=use_gc,
-                                pinned=False, segm_out=segm_buf)['segm']
+            segm = sess.segment(pairwise, 'model', gmm=gmm if on_device else None, proba=None if on_device else host_proba(),
+                                use_graphcut=use_gc, pinned=False, segm_out=segm_buf)['segm']
         except _hip.HipFusedPathError as ex:            # (IMSEGM_E_FUSED_PATH only: any other error of the call is an error)
             logging.info('volume graph by neighbour tables (%s)', ex)
     if segm is None:
-        graph_labels = segment_graph_cut_general(_ShapeOnly(sess.shape), proba, image, features, gc_regul, _session=sess)
+        graph_labels = segment_graph_cut_general(_ShapeOnly(sess.shape), host_proba(), image, features, gc_regul, _session=sess)
         segm_ready()
         segm, _ = sess.gather(graph_labels, segm_out=segm_buf)     # (into the array touched above: no second result array)
     return segm
