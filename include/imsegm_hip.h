@@ -581,6 +581,29 @@ IMSEGM_API int imsegm_mixture_em_wide(imsegm_ctx *ctx, int n_restarts, int n_com
                                       double *covariances_out, double *prec_chol_out, double *lower_bound_out,
                                       int32_t *n_iter_out, int32_t *converged_out, int32_t *not_pd_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * RANSAC scoring of ellipse trials (imsegm/ellipse_fitting.py ransac_segm :228-254 with EllipseModelSegm.criterion :121-139 and
+ * skimage's EllipseModel.residuals), every trial of every egg candidate of an image in one launch chain; csrc/ellipse.hip
+ * ------------------------------------------------------------------------------------------- */
+/* Egg e owns the boundary points [point_offsets[e], point_offsets[e + 1]) of `points` (float64 x, y pairs; at least 5 per egg) and
+ * the trials t with trial_egg[t] == e (trial_egg must not decrease; an egg may have none).  params: n_trials x 5 float64 (xc, yc,
+ * a, b, theta), success: one byte per trial (0: the estimate failed, the trial is skipped).  points_all: n_all x 2 float64,
+ * point_value[n] = weights[labels[n]] * (q[0][labels[n]] - q[1][labels[n]]) with q = -log(table_prob), prepared by the caller.
+ * Per trial: criterion_out[t] = sum of point_value over the centres inside the ellipse (the reference's inside test; a fixed
+ * summation tree that depends on n_all alone; NaN for a failed trial).  Per (trial, point of the trial's egg): the distance to the
+ * closest point of the ellipse in the basin of the reference's starting parameter; the point is an inlier when |distance| <
+ * residual_threshold.  Per egg, by the reference's update rule over its trials in order: best_out[e] = the trial whose criterion
+ * was last found below the best so far, kept_out[e] = the trial whose inlier mask was kept, both counted among the egg's own
+ * trials, -1 for none; mask_out[point_offsets[e] ...] = the kept mask (zeros for none).  residuals_out (may be NULL): the distances
+ * of all pairs, trial after trial, each trial with one entry per point of its egg (NaN for a failed trial).
+ * All outputs are host arrays.  Returns -1 (no launch) for n_eggs, n_trials or n_all < 1, offsets that do not start at 0 or are
+ * not monotone, an egg with fewer than 5 points, or a trial_egg outside [0, n_eggs). */
+IMSEGM_API int imsegm_ellipse_ransac(imsegm_ctx *ctx, int n_eggs, const int32_t *point_offsets, const double *points, int n_trials,
+                                     const double *params, const uint8_t *success, const int32_t *trial_egg,
+                                     const double *points_all, const double *point_value, int n_all, double residual_threshold,
+                                     int32_t *best_out, int32_t *kept_out, uint8_t *mask_out, double *criterion_out,
+                                     double *residuals_out);
+
 #ifdef __cplusplus
 }
 #endif

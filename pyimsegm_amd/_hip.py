@@ -179,6 +179,8 @@ _SIGNATURES = {
     'imsegm_boundary_distances': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip]),
     'imsegm_image2d_boundary_distances': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ip]),
     'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
+    'imsegm_ellipse_ransac': (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
+                                        _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -1579,6 +1581,39 @@ def labels_overlap(seg1, seg2, n_labels1, n_labels2, ctx=None):
     out = np.empty((int(n_labels1), int(n_labels2)), dtype=np.int64)
     _check(load_library().imsegm_labels_overlap(ctx._h, _ptr(seg1), _ptr(seg2), seg1.size, int(n_labels1), int(n_labels2), _ptr(out)))
     return out
+
+
+def ellipse_ransac(point_offsets, points, params, success, trial_egg, points_all, point_value, residual_threshold,
+                   with_residuals=False, ctx=None):
+    """``imsegm_ellipse_ransac``: scores the RANSAC trials of all egg candidates of an image.  ``point_offsets`` int32 [E + 1] into
+    ``points`` float64 [P, 2]; ``params`` float64 [T, 5] with ``success`` uint8 [T] and ``trial_egg`` int32 [T] (not decreasing);
+    ``points_all`` float64 [N, 2] with ``point_value`` float64 [N].  Returns (best int32 [E], kept int32 [E], mask uint8 [P],
+    criterion float64 [T], residuals float64 [pairs] or None): see include/imsegm_hip.h."""
+    ctx = ctx or default_context()
+    point_offsets = np.ascontiguousarray(point_offsets, dtype=np.int32).ravel()
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 5)
+    success = np.ascontiguousarray(success, dtype=np.uint8).ravel()
+    trial_egg = np.ascontiguousarray(trial_egg, dtype=np.int32).ravel()
+    points_all = np.ascontiguousarray(points_all, dtype=np.float64).reshape(-1, 2)
+    point_value = np.ascontiguousarray(point_value, dtype=np.float64).ravel()
+    n_eggs, n_trials = len(point_offsets) - 1, len(params)
+    if len(success) != n_trials or len(trial_egg) != n_trials or len(point_value) != len(points_all):
+        raise ValueError('ellipse_ransac: one success flag and one egg per trial, one value per centre')
+    if n_eggs >= 1 and (point_offsets[0] != 0 or point_offsets[-1] != len(points)):
+        raise ValueError('ellipse_ransac: the point offsets must span the point list')
+    best, kept = np.empty(max(n_eggs, 0), dtype=np.int32), np.empty(max(n_eggs, 0), dtype=np.int32)
+    mask, criterion = np.empty(len(points), dtype=np.uint8), np.empty(n_trials, dtype=np.float64)
+    residuals = None
+    if with_residuals and n_eggs >= 1 and n_trials >= 1:
+        counts = np.diff(point_offsets.astype(np.int64))
+        inside = (trial_egg >= 0) & (trial_egg < n_eggs)
+        residuals = np.empty(int(counts[trial_egg[inside]].sum()) if inside.all() else 0, dtype=np.float64)
+    _check(load_library().imsegm_ellipse_ransac(ctx._h, n_eggs, _ptr(point_offsets), _ptr(points), n_trials, _ptr(params), _ptr(success),
+                                                _ptr(trial_egg), _ptr(points_all), _ptr(point_value), len(points_all),
+                                                float(residual_threshold), _ptr(best), _ptr(kept), _ptr(mask), _ptr(criterion),
+                                                _ptr(residuals)))
+    return best, kept, mask, criterion, residuals
 
 
 def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):
