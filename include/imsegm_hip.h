@@ -604,6 +604,51 @@ IMSEGM_API int imsegm_ellipse_ransac(imsegm_ctx *ctx, int n_eggs, const int32_t 
                                      int32_t *best_out, int32_t *kept_out, uint8_t *mask_out, double *criterion_out,
                                      double *residuals_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Region growing with a ray shape prior on superpixels (imsegm/region_growing.py region_growing_shape_slic_greedy :1155-1388,
+ * region_growing_shape_slic_graphcut :1482-1730): a resident state on top of a label session; csrc/region_growing.hip.  The host
+ * keeps the iteration, the thresholds, LAPACK's eigenvectors and the mixture weights (pyimsegm_amd/region_growing.py)
+ * ------------------------------------------------------------------------------------------- */
+typedef struct imsegm_rg imsegm_rg;             /* device-resident state of one growth */
+/* Replaces the set-up of both growth functions (:1297-1304, :1622-1629): on the label map of the session (imsegm_image2d_set_labels;
+ * it must stay as it is while the state is open) with its n_edges edges (the list imsegm_image2d_graph returned; its length is compared
+ * with the map's and every index is range-checked, the pairs themselves are taken as given) the state keeps
+ * np.round(superpixel_centers).astype(int) (half to even), np.bincount(slic) with the exact int64 row and column sums of every superpixel, the neighbour lists of get_neighboring_segments in CSR form, two K x (n_objects + 1) float64
+ * cost tables and K int32 labels.  Returns -1 for a volume session, no label map, n_objects < 1 or an edge outside the map.
+ * The state borrows the session: once the session is destroyed every imsegm_rg_* call on the state is undefined, EXCEPT
+ * imsegm_rg_close, which frees the state's own buffers without reading the session (the Python wrapper refuses the others). */
+IMSEGM_API int imsegm_rg_open(imsegm_image2d *im, const int32_t *edges, int n_edges, int n_objects, imsegm_rg **rg_out);
+IMSEGM_API void imsegm_rg_close(imsegm_rg *rg);
+/* what = 0: K x 3 int64 (pixel count = slic_weights :1299, row sum, column sum); 1: K x 2 int32 rounded centres (:1298);
+ * 2: the K x (n_objects + 1) float64 shape costs (for debug_history and prepare_graphcut_variables :1391) */
+IMSEGM_API int imsegm_rg_get(imsegm_rg *rg, int what, void *out);
+/* uploads lut_data_cost (compute_data_costs_points :993-1011) and / or lut_shape_cost with its background column (:1308-1310);
+ * either may be NULL */
+IMSEGM_API int imsegm_rg_set_costs(imsegm_rg *rg, const double *lut_data, const double *lut_shape);
+/* Replaces the inner loop of compute_update_shape_costs_points_table_cdf / _close_mean_cdf (:845-851, :984-989) for the objects
+ * that passed the threshold tests: lut_shape[:, objects[j] + 1] = -log(compute_shape_prior_table_cdf(point, table_j, centres[j],
+ * shifts[j]) + MIN_SHAPE_PROB) (:591-652, bilinear on the 2 x 2 cell where the reference calls interp2d; +-inf replaced by
+ * GC_REPLACE_INF) for every superpixel.  dims: n_selected x 2 (angles, distances) of each object's table, the tables one after the
+ * other in `tables`.  proba_out (may be NULL): the n_selected x K priors.  Centres and shifts must be finite. */
+IMSEGM_API int imsegm_rg_shape_costs(imsegm_rg *rg, int n_selected, const int32_t *objects, const double *centres, const double *shifts,
+                                     const int32_t *dims, const double *tables, double *proba_out);
+/* Replaces compute_ray_features_segm_2d(labels[slic] == i + 1, centre_i, edge='down') of compute_segm_object_shape (:259-286,
+ * called at :943) for every object at once, the mask read through the label vector: positions n_objects x 2 int32 (the rounded
+ * centres of mass, which the caller forms from the int64 sums of imsegm_rg_get), directions n_angles x 2 float32 (the table of
+ * imsegm_ray_features_binary2d), rays_out n_objects x n_angles float32 (-1: no edge met).  labels: K int32 in [0, n_objects], or
+ * NULL to keep the resident vector (also below). */
+IMSEGM_API int imsegm_rg_object_shapes(imsegm_rg *rg, const int32_t *labels, const int32_t *positions, const float *directions,
+                                       int n_angles, float *rays_out);
+/* Replaces the candidate search and scoring of one greedy iteration (get_neighboring_candidates :1088-1111 per object,
+ * :1346-1371): the (object, superpixel) pairs in the reference's order (object-major, superpixels ascending; objects count from
+ * 1) and, when changes_out is not NULL, crit - crit_new of each pair in its delta form.  coefs: coef_data, coef_shape,
+ * coef_pairwise, -log(prob_label_trans[0]), -log(prob_label_trans[1]) (inf replaced by the caller).  The result arrays hold
+ * n_objects x K entries. */
+IMSEGM_API int imsegm_rg_greedy_step(imsegm_rg *rg, const int32_t *labels, int allow_obj_swap, const double *coefs, int *n_out,
+                                     int32_t *objects_out, int32_t *superpixels_out, double *changes_out);
+/* Replaces compute_rg_crit (:1114-1133) on the resident tables: a fixed summation tree, the same labels give the same bytes */
+IMSEGM_API int imsegm_rg_criterion(imsegm_rg *rg, const int32_t *labels, const double *coefs, double *criterion_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,14 @@ _SIGNATURES = {
     'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
     'imsegm_ellipse_ransac': (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                         _vp]),
+    'imsegm_rg_open': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    'imsegm_rg_close': (None, [_vp]),
+    'imsegm_rg_get': (C.c_int, [_vp, C.c_int, _vp]),
+    'imsegm_rg_set_costs': (C.c_int, [_vp, _vp, _vp]),
+    'imsegm_rg_shape_costs': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'imsegm_rg_object_shapes': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
+    'imsegm_rg_greedy_step': (C.c_int, [_vp, _vp, C.c_int, _vp, _ip, _vp, _vp, _vp]),
+    'imsegm_rg_criterion': (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -1682,3 +1690,120 @@ def ray_features_labels2d(segm, border_labels, positions, directions, edge, smoo
                                                        _ptr(positions), len(positions), _ptr(directions), len(directions), int(edge),
                                                        _ptr(taps), 0 if taps is None else len(taps) - 1, _ptr(out)))
     return out
+
+
+class RegionGrowing(object):
+    """resident state of one region growing on a label session (``imsegm_rg_*``, csrc/region_growing.hip): the label map of
+    ``sess`` with the ``edges`` its :meth:`Image2D.graph` returned, for ``n_objects`` objects.  The session must keep its label map
+    while the state is open."""
+
+    def __init__(self, sess, edges, n_objects):
+        self.sess, self.n_objects, self.n_labels = sess, int(n_objects), int(sess.n_labels)
+        edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        self._h = _vp()
+        _check(load_library().imsegm_rg_open(sess._h, _ptr(edges), len(edges), self.n_objects, C.byref(self._h)))
+        size = max(self.n_objects * self.n_labels, 1)
+        self._cand = (np.empty(size, dtype=np.int32), np.empty(size, dtype=np.int32), np.empty(size, dtype=np.float64))
+
+    def close(self):
+        # (the state frees its own buffers without reading the session: either may be closed first)
+        if self._h:
+            load_library().imsegm_rg_close(self._h)
+        self._h = None
+
+    def _handle(self):
+        if not self._h or not self.sess._h:
+            raise HipError('the region-growing state or its label session is closed')
+        return self._h
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _get(self, what, shape, dtype):
+        out = np.empty(shape, dtype=dtype)
+        _check(load_library().imsegm_rg_get(self._handle(), what, _ptr(out)))
+        return out
+
+    def sums(self):
+        """int64 [K, 3]: pixel count, row sum and column sum of every superpixel"""
+        return self._get(0, (self.n_labels, 3), np.int64)
+
+    def points(self):
+        """int32 [K, 2]: ``np.round(superpixel_centers(slic)).astype(int)``"""
+        return self._get(1, (self.n_labels, 2), np.int32)
+
+    def shape_costs(self):
+        """float64 [K, n_objects + 1]: the resident ``lut_shape_cost``"""
+        return self._get(2, (self.n_labels, self.n_objects + 1), np.float64)
+
+    def set_costs(self, lut_data=None, lut_shape=None):
+        tables = []
+        for table in (lut_data, lut_shape):
+            if table is not None:
+                table = np.ascontiguousarray(table, dtype=np.float64)
+                if table.shape != (self.n_labels, self.n_objects + 1):
+                    raise ValueError('cost table %r, expected %r' % (table.shape, (self.n_labels, self.n_objects + 1)))
+            tables.append(table)
+        _check(load_library().imsegm_rg_set_costs(self._handle(), _ptr(tables[0]), _ptr(tables[1])))
+
+    def _labels(self, labels):
+        if labels is None:
+            return None
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if len(labels) != self.n_labels:
+            raise ValueError('%d labels for %d superpixels' % (len(labels), self.n_labels))
+        return labels
+
+    @staticmethod
+    def _coefs(coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg):
+        return np.array([coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg], dtype=np.float64)
+
+    def update_shape_costs(self, objects, centres, shifts, tables, with_proba=False):
+        """``lut_shape_cost[:, objects[j] + 1]`` from table ``tables[j]`` (float64 A_j x D_j) around ``centres[j]`` turned by
+        ``shifts[j]``; with_proba: returns the priors float64 [len(objects), K]"""
+        objects = np.ascontiguousarray(objects, dtype=np.int32).ravel()
+        if len(objects) == 0:
+            return np.empty((0, self.n_labels)) if with_proba else None
+        centres = np.ascontiguousarray(centres, dtype=np.float64).reshape(-1, 2)
+        shifts = np.ascontiguousarray(shifts, dtype=np.float64).ravel()
+        tables = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        if not len(objects) == len(centres) == len(shifts) == len(tables) or any(t.ndim != 2 for t in tables):
+            raise ValueError('one centre, one shift and one 2-D table per object')
+        dims = np.array([t.shape for t in tables], dtype=np.int32)
+        flat = np.concatenate([t.ravel() for t in tables])
+        proba = np.empty((len(objects), self.n_labels), dtype=np.float64) if with_proba else None
+        _check(load_library().imsegm_rg_shape_costs(self._handle(), len(objects), _ptr(objects), _ptr(centres), _ptr(shifts), _ptr(dims),
+                                                    _ptr(flat), _ptr(proba)))
+        return proba
+
+    def object_rays(self, labels, positions, directions):
+        """'down' ray distances float32 [n_objects, A] of every object's mask ``labels[slic] == i + 1`` from ``positions``"""
+        labels = self._labels(labels)
+        positions = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1, 2)
+        directions = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 2)
+        if len(positions) != self.n_objects:
+            raise ValueError('one position per object')
+        out = np.empty((self.n_objects, len(directions)), dtype=np.float32)
+        _check(load_library().imsegm_rg_object_shapes(self._handle(), _ptr(labels), _ptr(positions), _ptr(directions), len(directions), _ptr(out)))
+        return out
+
+    def greedy_step(self, labels, allow_obj_swap, coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg, with_scores=True):
+        """(objects int32, superpixels int32, changes float64 or None) of the candidates of ``labels``"""
+        labels = self._labels(labels)
+        coefs = self._coefs(coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg)
+        count = C.c_int(0)
+        objs, sps, changes = self._cand
+        _check(load_library().imsegm_rg_greedy_step(self._handle(), _ptr(labels), int(bool(allow_obj_swap)), _ptr(coefs), C.byref(count),
+                                                    _ptr(objs), _ptr(sps), _ptr(changes) if with_scores else None))
+        n = count.value
+        return objs[:n].copy(), sps[:n].copy(), changes[:n].copy() if with_scores else None
+
+    def criterion(self, labels, coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg):
+        labels = self._labels(labels)
+        coefs = self._coefs(coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg)
+        out = np.empty(1, dtype=np.float64)
+        _check(load_library().imsegm_rg_criterion(self._handle(), _ptr(labels), _ptr(coefs), _ptr(out)))
+        return float(out[0])

@@ -1070,3 +1070,28 @@ def compute_ray_features_positions(segm, list_positions, angle_step=5., border_l
     feature_names = ['ray-lb_%s-agl_%i' % (''.join(map(str, border_labels)), int(a))
                      for a in np.linspace(0, 360 - angle_step, rays.shape[1])]
     return rays, pos_shift, feature_names
+
+
+def interpolate_ray_dist(ray_dists, order='spline'):
+    """the ray distances with those that met no edge (``-1``) filled in from the others (reference ``descriptors.py:1898-1962``; its
+    examples are in tests/doctests/region_growing.py).  On the host: it is reached only when a ray leaves the image.
+
+    :param list(float) ray_dists: one distance per angle
+    :param str|int order: degree of a polynomial through the known rays (``np.polyfit``), or 'spline' for an interpolating spline
+        through three turns of them (``InterpolatedUnivariateSpline``)
+    :return ndarray: a copy; unchanged when no ray is known
+    """
+    rays = np.array(ray_dists)
+    known, holes = np.nonzero(rays != -1)[0], np.nonzero(rays == -1)[0]
+    if len(known) == 0:
+        return rays
+    if isinstance(order, int):
+        rays[holes] = np.polyval(np.polyfit(known, rays[known], order), holes)
+    elif order == 'spline':
+        from scipy.interpolate import InterpolatedUnivariateSpline
+        # the angle is periodic: the known rays once more a turn before and a turn after
+        turns = np.concatenate([known - len(rays), known, known + len(rays)])
+        rays[holes] = InterpolatedUnivariateSpline(turns, np.tile(rays[known], 3))(holes)
+    elif order == 'cos':
+        raise NotImplementedError("interpolate_ray_dist: order 'cos' (a least-squares sine fit) is not provided")
+    return rays

@@ -1,0 +1,809 @@
+"""Region growing with a ray shape prior on superpixels: the growth loop of the reference's ``imsegm/region_growing.py``
+(``region_growing_shape_slic_greedy``, ``region_growing_shape_slic_graphcut`` and what they call) with the per-iteration work on
+the device.
+
+* The host keeps the iteration (``list_swap_shift`` and its shaking rule, ``enforce_center_labels``, ``debug_history``, the
+  threshold tests on centre, shift and volume, the stable sort and the apply loop of the greedy variant), centre and orientation
+  of an object (``np.cov`` + ``np.linalg.eig``: the sign of LAPACK's eigenvector decides between theta and theta + 180), the
+  mixture weights and the mixing of the cdf tables, and the assembly of the graph that is cut.
+* ``on='device'`` keeps a resident state (``_hip.RegionGrowing``, csrc/region_growing.hip) on the label session: the shape cost of
+  every (object, superpixel) pair, the ray distances of every object's mask, the candidates of an iteration with their energy
+  changes, and the criterion.  Per iteration K labels go up and the candidates come down.
+* ``on='host'`` evaluates the same definitions in numpy (:class:`_HostState`) -- the CPU statement the kernels are tested against.
+  The cut of the graph-cut variant always runs on the device (``graph_cuts.cut_general_graph``).
+
+Definitions ("Region growing"): the shape prior is bilinear on the 2 x 2 cell where the reference builds an
+``interp2d`` object; the energy change of a candidate is the delta of the criterion, not the difference of two full sums.
+"""
+import os
+
+import numpy as np
+
+from pyimsegm_amd import _hip
+from pyimsegm_amd.descriptors import _ray_directions, interpolate_ray_dist, shift_ray_features
+from pyimsegm_amd.graph_cuts import MAX_PAIRWISE_COST, compute_spatial_dist, cut_general_graph
+from pyimsegm_amd.labeling import histogram_regions_labels_norm
+
+#: stands in for an infinite cost wherever a cost table or a graph-cut term would hold one
+GC_REPLACE_INF = 1e5
+#: added to every shape prior before its logarithm: a prior of 0 still has a finite cost
+MIN_SHAPE_PROB = 0.01
+#: the largest probability a unary term may express (its cost is never below -log of this)
+MAX_UNARY_PROB = 1 - 0.01
+#: when the shape cost of an object is computed anew during a growth, and how far its centre may wander
+RG2SP_THRESHOLDS = {
+    'centre': 30,           # pixels between the centre and the one its cost column was computed for
+    'shift': 15,            # degrees between the orientation and the one of the column
+    'volume': 0.1,          # relative change of the number of superpixels since the column ('set_cdfs')
+    'centre_init': 50,      # pixels: the radius around the initial centre within which a centre is kept
+}
+
+
+def _place(on):
+    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_RG_ON, unset: 'device' when a device is
+    present"""
+    if on is None:
+        on = os.environ.get('IMSEGM_RG_ON') or None
+    if on is None:
+        try:
+            on = 'device' if _hip.device_count() > 0 else 'host'
+        except _hip.HipUnavailableError:
+            on = 'host'
+    if on not in ('host', 'device'):
+        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
+    return on
+
+
+def _replace_inf(values):
+    values[np.isinf(values)] = GC_REPLACE_INF
+    return values
+
+
+def _penalties(prob_label_trans):
+    """-log of the two transition probabilities with inf replaced (``compute_rg_crit`` :1130-1131)"""
+    with np.errstate(divide='ignore'):
+        pen = _replace_inf(-np.log(np.asarray(prob_label_trans[:2], dtype=np.float64)))
+    return float(pen[0]), float(pen[1])
+
+
+# ------------------------------------------------------------------------------------------------
+# the definitions the kernels implement, in numpy
+# ------------------------------------------------------------------------------------------------
+
+
+def shape_prior_points(points, cum_distribution, centre, angle_shift=0):
+    """:func:`compute_shape_prior_table_cdf` for points [N, 2] at once: the numpy statement of ``k_rg_shape_cost``, operation by
+    operation.  Row A of the table is row 0 again; a modulus that rounds to 360.0 itself takes row 0 with weight 0."""
+    table = np.asarray(cum_distribution, dtype=np.float64)
+    nb_angles, nb_dists = table.shape
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    dx, dy = points[:, 0] - float(centre[0]), points[:, 1] - float(centre[1])
+    dist = np.sqrt(dx * dx + dy * dy)
+    angle = np.rad2deg(np.arctan2(dy, dx))
+    angle = np.mod((810.0 - angle) - float(angle_shift), 360.0)
+    angle_norm = angle / (360. / nb_angles)
+    prior = np.empty(len(points))
+    far = dist >= (nb_dists - 1)
+    row = np.rint(angle_norm[far]).astype(int)
+    row[row >= nb_angles] = 0
+    prior[far] = table[row, nb_dists - 1]
+    near = ~far
+    if near.any():
+        a_norm, d = angle_norm[near], dist[near]
+        a0 = np.floor(a_norm).astype(int)
+        ta = a_norm - a0
+        wrapped = a0 >= nb_angles
+        a0[wrapped], ta[wrapped] = 0, 0.
+        a1 = np.where(a0 + 1 >= nb_angles, 0, a0 + 1)
+        d0 = np.floor(d).astype(int)
+        td = d - d0
+        low = table[a0, d0] + (table[a0, d0 + 1] - table[a0, d0]) * td
+        high = table[a1, d0] + (table[a1, d0 + 1] - table[a1, d0]) * td
+        prior[near] = low + (high - low) * ta
+    return prior
+
+
+def compute_shape_prior_table_cdf(point, cum_distribution, centre, angle_shift=0):
+    """shape prior of one point: the cumulative table read at the point's distance from ``centre`` and at its direction turned by
+    ``angle_shift`` degrees (reference :591-652); :func:`shape_prior_points` for a single point.  The reference's examples are in
+    tests/doctests/region_growing.py.
+
+    :param tuple(int,int) point: (row, col)
+    :param cum_distribution: table [angles, distances]
+    :param tuple(float,float) centre: (row, col) of the object
+    :param float angle_shift: orientation of the object in degrees
+    :return float:
+    """
+    return shape_prior_points([point], cum_distribution, centre, angle_shift)[0]
+
+
+def _shape_cost(prior):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return _replace_inf(-np.log(prior + MIN_SHAPE_PROB))
+
+
+def ray_distances_down(mask, position, directions):
+    """``computeRayFeaturesBinary2d(mask, position, edge='down')`` in numpy, all angles at once: float32 positions advanced by the
+    float32 ``directions`` [A, 2], the walk of ``k_rg_object_rays`` / ``k_ray_features_binary2d`` operation by operation"""
+    mask = np.asarray(mask, dtype=bool)
+    height, width = mask.shape
+    directions = np.asarray(directions, dtype=np.float32)
+    rays = np.full(len(directions), -1, dtype=np.float32)
+    py, px = int(position[0]), int(position[1])
+    if not (0 <= py < height and 0 <= px < width):
+        return rays
+    pos0 = np.full(len(directions), py, dtype=np.float32)
+    pos1 = np.full(len(directions), px, dtype=np.float32)
+    last = np.full(len(directions), mask[py, px], dtype=bool)
+    active = np.ones(len(directions), dtype=bool)
+    for _ in range(int(np.sqrt(float(width) * width + float(height) * height))):
+        if not active.any():
+            break
+        pos0 = pos0 + directions[:, 0]
+        pos1 = pos1 + directions[:, 1]
+        r0, r1 = np.floor(pos0.astype(np.float64) + 0.5), np.floor(pos1.astype(np.float64) + 0.5)
+        active &= ~((pos0 < 0) | (r0 >= height) | (pos1 < 0) | (r1 >= width))
+        idx = np.nonzero(active)[0]
+        actual = mask[r0[idx].astype(int), r1[idx].astype(int)]
+        hit = last[idx] & ~actual
+        dx, dy = pos0[idx[hit]] - np.float32(py), pos1[idx[hit]] - np.float32(px)
+        rays[idx[hit]] = np.sqrt(((dx * dx) + (dy * dy)).astype(np.float64)).astype(np.float32)
+        last[idx] = actual
+        active[idx[hit]] = False
+    return rays
+
+
+def _delta_scores(objects, superpixels, labels, weights, lut_data, lut_shape, nb_off, nb_flat, coef_data, coef_shape, coef_pairwise,
+                  pen_bg, pen_fg):
+    """energy change of every candidate in its delta form: the numpy statement of ``k_rg_scores``"""
+    old = labels[superpixels]
+    unary = (coef_data * (lut_data[superpixels, old] - lut_data[superpixels, objects])
+             + coef_shape * (lut_shape[superpixels, old] - lut_shape[superpixels, objects]))
+    change = weights[superpixels].astype(np.float64) * unary
+    if coef_pairwise > 0:
+        def penalty(own, other):
+            return np.where(own == other, 0., np.where((own == 0) | (other == 0), pen_bg, pen_fg))
+
+        pair = np.zeros(len(objects))
+        degree = nb_off[superpixels + 1] - nb_off[superpixels]
+        for step in range(int(degree.max()) if len(degree) else 0):              # neighbour after neighbour, in list order
+            has = np.nonzero(degree > step)[0]
+            other = labels[nb_flat[nb_off[superpixels[has]] + step]]
+            pair[has] += penalty(old[has], other) - penalty(objects[has], other)
+        change = change + coef_pairwise * pair
+    return change
+
+
+def _tree_sum(values):
+    """the fixed tree of ``k_rg_crit``: lane i adds entries i, i + 256, ... in order, the 64 lanes of a wave meet in an xor
+    butterfly, the four waves as (w0 + w1) + (w2 + w3)"""
+    values = np.asarray(values, dtype=np.float64)
+    lanes = np.zeros(256)
+    for start in range(0, len(values), 256):
+        chunk = values[start:start + 256]
+        lanes[:len(chunk)] += chunk
+    waves = lanes.reshape(4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        waves = waves + waves[:, np.arange(64) ^ off]
+    return (waves[0, 0] + waves[1, 0]) + (waves[2, 0] + waves[3, 0])
+
+
+class _HostState(object):
+    """what ``_hip.RegionGrowing`` keeps on the device, in numpy, with the same methods"""
+
+    def __init__(self, slic, n_objects):
+        slic = np.asarray(slic)
+        self.slic, self.n_objects = slic, int(n_objects)
+        self.n_labels = int(slic.max()) + 1
+        rows, cols = np.indices(slic.shape)
+        count = np.bincount(slic.ravel(), minlength=self.n_labels)
+        self._sums = np.stack([count, np.bincount(slic.ravel(), rows.ravel(), self.n_labels).astype(np.int64),
+                               np.bincount(slic.ravel(), cols.ravel(), self.n_labels).astype(np.int64)], axis=1).astype(np.int64)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            centres = np.where(count[:, None] > 0, self._sums[:, 1:] / count[:, None].astype(np.float64), -1.)
+        self._points = np.round(centres).astype(np.int32)
+        pairs = np.vstack([np.stack([slic[:, :-1].ravel(), slic[:, 1:].ravel()], axis=1),
+                           np.stack([slic[:-1, :].ravel(), slic[1:, :].ravel()], axis=1)])
+        pairs = np.sort(pairs[pairs[:, 0] != pairs[:, 1]], axis=1)
+        codes = np.unique(pairs[:, 0] + self.n_labels * pairs[:, 1].astype(np.int64))
+        self.edges = np.stack([codes % self.n_labels, codes // self.n_labels], axis=1).astype(np.int32)      # ordered by (b, a)
+        self.lut_data = self.lut_shape = None
+        self._labels = np.zeros(self.n_labels, dtype=int)
+
+    def close(self):
+        pass
+
+    def sums(self):
+        return self._sums
+
+    def points(self):
+        return self._points
+
+    def attach(self, nb_off, nb_flat):
+        self.nb_off, self.nb_flat = nb_off, nb_flat
+
+    def set_costs(self, lut_data=None, lut_shape=None):
+        if lut_data is not None:
+            self.lut_data = np.array(lut_data, dtype=np.float64)
+        if lut_shape is not None:
+            self.lut_shape = np.array(lut_shape, dtype=np.float64)
+
+    def shape_costs(self):
+        return self.lut_shape.copy()
+
+    def update_shape_costs(self, objects, centres, shifts, tables, with_proba=False):
+        proba = np.empty((len(objects), self.n_labels))
+        for j, obj in enumerate(objects):
+            proba[j] = shape_prior_points(self._points, tables[j], centres[j], shifts[j])
+            self.lut_shape[:, obj + 1] = _shape_cost(proba[j])
+        return proba if with_proba else None
+
+    def object_rays(self, labels, positions, directions):
+        self._labels = np.asarray(labels if labels is not None else self._labels)
+        segm = self._labels[self.slic]
+        return np.array([ray_distances_down(segm == i + 1, positions[i], directions) for i in range(self.n_objects)],
+                        dtype=np.float32).reshape(self.n_objects, len(directions))
+
+    def greedy_step(self, labels, allow_obj_swap, coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg, with_scores=True):
+        labels = self._labels = np.asarray(labels if labels is not None else self._labels)
+        owner = np.repeat(np.arange(self.n_labels), np.diff(self.nb_off))
+        objects, superpixels = [], []
+        for obj in range(1, self.n_objects + 1):
+            touched = np.zeros(self.n_labels, dtype=bool)
+            touched[owner[labels[self.nb_flat] == obj]] = True
+            near = np.nonzero(touched & ((labels != obj) if allow_obj_swap else (labels == 0)))[0]
+            superpixels.append(near)
+            objects.append(np.full(len(near), obj))
+        objects, superpixels = np.concatenate(objects).astype(np.int32), np.concatenate(superpixels).astype(np.int32)
+        if not with_scores:
+            return objects, superpixels, None
+        return objects, superpixels, _delta_scores(objects, superpixels, labels, self._sums[:, 0], self.lut_data, self.lut_shape,
+                                                   self.nb_off, self.nb_flat, coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg)
+
+    def criterion(self, labels, coef_data, coef_shape, coef_pairwise, pen_bg, pen_fg):
+        labels = self._labels = np.asarray(labels if labels is not None else self._labels)
+        every = np.arange(len(labels))
+        crit = _tree_sum(self._sums[:, 0].astype(np.float64)
+                         * (coef_data * self.lut_data[every, labels] + coef_shape * self.lut_shape[every, labels]))
+        if coef_pairwise > 0:
+            first, second = labels[self.edges[:, 0]], labels[self.edges[:, 1]]
+            pen = np.where(first == second, 0., np.where((first == 0) | (second == 0), pen_bg, pen_fg))
+            crit = crit + coef_pairwise * _tree_sum(pen)
+        return float(crit)
+
+
+class _DeviceState(object):
+    """the resident state of csrc/region_growing.hip behind the methods of :class:`_HostState`"""
+
+    def __init__(self, slic, n_objects):
+        from pyimsegm_amd.superpixels import _session_for_labels
+        self.sess = _session_for_labels(np.asarray(slic))
+        try:
+            self.edges = self.sess.graph()[0]
+            self.rg = _hip.RegionGrowing(self.sess, self.edges, n_objects)
+        except Exception:
+            self.sess.close()
+            raise
+        self.n_objects, self.n_labels = int(n_objects), self.rg.n_labels
+        for name in ('sums', 'points', 'set_costs', 'shape_costs', 'update_shape_costs', 'object_rays', 'greedy_step', 'criterion'):
+            setattr(self, name, getattr(self.rg, name))
+
+    def attach(self, nb_off, nb_flat):
+        pass
+
+    def close(self):
+        self.rg.close()
+        self.sess.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# the small functions of the reference
+# ------------------------------------------------------------------------------------------------
+
+
+def compute_segm_prob_fg(slic, segm, labels_prob):
+    """foreground probability of every superpixel: ``labels_prob`` of the class of ``segm`` that covers most of it (reference
+    :1136-1152; the histogram on the device)
+
+    :param ndarray slic: superpixel map
+    :param ndarray segm: class map of the same shape
+    :param list(float) labels_prob: foreground probability of every class
+    :return ndarray: one probability per superpixel
+    """
+    majority = np.argmax(histogram_regions_labels_norm(slic, segm), axis=1)
+    return np.asarray(labels_prob)[majority]
+
+
+def compute_centre_moment_points(points):
+    """mean of a point set and the direction of its largest spread in whole degrees, 0 .. 359 (reference :704-747).  ``np.cov`` and
+    ``np.linalg.eig`` are called on the centred points as the reference calls them: the sign LAPACK gives the eigenvector decides
+    between an angle and the opposite one.
+
+    :param points: [N, 2] (row, col)
+    :return tuple(ndarray,float): mean, angle
+    """
+    coords = np.asarray(points)
+    mean = np.mean(coords, axis=0)
+    degrees = 0.
+    if len(coords) > 1:
+        values, vectors = np.linalg.eig(np.cov((coords - mean).T))
+        main = vectors[:, np.argmax(values)]
+        degrees = np.rad2deg(np.arctan2(main[0], main[1]))
+    return mean, float((360 + round(degrees)) % 360)
+
+
+def compute_segm_object_shape(img_object, ray_step=5, interp_order=3, smooth_coef=0, shift_method='phase'):
+    """ray distances of the one object in a binary image, cast from its rounded centre of mass to where the object ends; rays that
+    leave the image are filled in, the vector is optionally smoothed and then rotated to its main phase (reference :259-286; the
+    rays on the device)
+
+    :return tuple(list(float),float): rays, rotation
+    """
+    from scipy import ndimage
+    from pyimsegm_amd.descriptors import compute_ray_features_segm_2d
+    start = [int(round(c)) for c in ndimage.center_of_mass(img_object)]
+    return _finish_rays(compute_ray_features_segm_2d(img_object, start, ray_step, 0, edge='down'), interp_order, smooth_coef,
+                        shift_method)
+
+
+def _finish_rays(rays, interp_order=3, smooth_coef=0, shift_method='phase'):
+    """what follows the ray walk of :func:`compute_segm_object_shape`: fill, smooth, rotate"""
+    if interp_order is not None and np.any(np.asarray(rays) == -1):
+        rays = interpolate_ray_dist(rays, interp_order)
+    if smooth_coef > 0:
+        from scipy.ndimage import gaussian_filter1d
+        rays = gaussian_filter1d(rays, smooth_coef)
+    rays, rotation = shift_ray_features(rays, shift_method)
+    return rays.tolist(), rotation
+
+
+def compute_data_costs_points(slic, slic_prob_fg, centres, labels):
+    """data cost of every (superpixel, label) pair -- ``-log`` of the background probability in column 0 and of the foreground
+    probability in the column of every object -- and ``labels`` with the superpixel under every centre given to its object
+    (reference :993-1011)
+
+    :return tuple(ndarray,ndarray): costs [K, objects + 1], labels
+    """
+    foreground = np.asarray(slic_prob_fg, dtype=np.float64)
+    proba = np.repeat(foreground[:, None], len(centres) + 1, axis=1)
+    proba[:, 0] = 1. - foreground
+    for number, position in enumerate(centres, start=1):
+        labels[slic[position[0], position[1]]] = number
+    return _replace_inf(-np.log(proba + 1e-9)), labels
+
+
+def compute_pairwise_penalty(edges, labels, prob_bg_fg=0.05, prob_fg1_fg2=0.01):
+    """cost of every edge for the labels at its two ends: nothing where they agree, ``-log(prob_bg_fg)`` where one of them is the
+    background, ``-log(prob_fg1_fg2)`` between two objects (reference :1065-1085)
+
+    :return ndarray: one cost per edge
+    """
+    first, second = np.asarray(labels)[np.asarray(edges)].T
+    differ = first != second
+    at_background = differ & ((first == 0) | (second == 0))
+    return np.where(at_background, -np.log(prob_bg_fg), -np.log(prob_fg1_fg2) * differ)
+
+
+def get_neighboring_candidates(slic_neighbours, labels, object_idx, use_other_obj=True):
+    """the superpixels next to object ``object_idx`` that it could take, ascending: those of any other label, or of the background
+    alone when ``use_other_obj`` is off (reference :1088-1111)
+
+    :return list(int):
+    """
+    label_of = np.asarray(labels)
+    around = set()
+    for member in np.nonzero(label_of == object_idx)[0]:
+        around.update(int(n) for n in slic_neighbours[member])
+    if use_other_obj:
+        return [n for n in sorted(around) if label_of[n] != object_idx]
+    return [n for n in sorted(around) if label_of[n] == 0]
+
+
+def compute_rg_crit(labels, lut_data_cost, lut_shape_cost, slic_weights, edges, coef_data, coef_shape, coef_pairwise,
+                    prob_label_trans):
+    """energy of a labelling: the weighted data and shape cost of every superpixel under its label, plus the penalty of every edge
+    (reference :1114-1133)
+
+    :return float:
+    """
+    rows = np.arange(len(labels))
+    unary = coef_data * lut_data_cost[rows, labels] + coef_shape * lut_shape_cost[rows, labels]
+    energy = np.sum(slic_weights * unary)
+    if coef_pairwise > 0:
+        penalty = compute_pairwise_penalty(edges, labels, prob_label_trans[0], prob_label_trans[1])
+        energy += coef_pairwise * np.sum(_replace_inf(penalty))
+    return energy
+
+
+def enforce_center_labels(slic, labels, centres):
+    """gives the superpixel under every centre to the object of that centre, so that no object can vanish (reference :1467-1479)"""
+    for number, position in enumerate(centres, start=1):
+        labels[slic[int(position[0]), int(position[1])]] = number
+    return labels
+
+
+def _csr_neighbours(slic_neighbours, nb_labels):
+    degree = np.zeros(nb_labels, dtype=np.int64)
+    degree[:len(slic_neighbours)] = [len(near) for near in slic_neighbours]
+    nb_off = np.concatenate([[0], np.cumsum(degree)])
+    nb_flat = np.array([n for near in slic_neighbours for n in near], dtype=np.int64)
+    return nb_off, nb_flat
+
+
+def prepare_graphcut_variables(candidates, slic_points, slic_neighbours, slic_weights, labels, nb_centres, lut_data_cost,
+                               lut_shape_cost, coef_data, coef_shape, coef_pairwise, prob_label_trans):
+    """the graph that is cut around the candidates, with its potentials (reference :1391-1464): a candidate may take the label of
+    any of its neighbours at its weighted data and shape cost, a neighbour that is no candidate keeps its label at no cost, and
+    everything else costs ``GC_REPLACE_INF``.  Vectorised, with the reference's vertex order: the candidates first (duplicates kept), then their
+    neighbours in order of first appearance; one edge (i, j) per (candidate, neighbour) pair in that order, j the FIRST position of
+    the neighbour among the vertexes
+
+    :return: vertexes, edges, edge_weights, unary, pairwise
+    """
+    slic_points, labels = np.asarray(slic_points), np.asarray(labels)
+    if np.max(candidates) >= len(slic_points):
+        raise ValueError('max candidate idx: %d for %d centres' % (np.max(candidates), len(slic_points)))
+    largest = max(max(near) for near in slic_neighbours if len(near))
+    if largest >= len(slic_points):
+        raise ValueError('max slic neighbours idx: %d for %d centres' % (largest, len(slic_points)))
+    cand = np.asarray(candidates, dtype=np.int64)
+    nb_off, nb_flat = _csr_neighbours(slic_neighbours, len(slic_points))
+    degree = nb_off[cand + 1] - nb_off[cand]
+    owner = np.repeat(np.arange(len(cand)), degree)
+    near = nb_flat[np.repeat(nb_off[cand], degree) + (np.arange(degree.sum()) - np.repeat(np.cumsum(degree) - degree, degree))]
+    position = np.full(len(slic_points), -1, dtype=np.int64)
+    uniq, first = np.unique(cand, return_index=True)
+    position[uniq] = first
+    fresh = near[position[near] < 0]
+    uniq, first = np.unique(fresh, return_index=True)
+    added = uniq[np.argsort(first, kind='stable')]
+    position[added] = len(cand) + np.arange(len(added))
+    vertexes = np.concatenate([cand, added])
+    edges = np.stack([owner, position[near]], axis=1)
+
+    nb_labels = nb_centres + 1
+    unary = np.full((len(vertexes), nb_labels), GC_REPLACE_INF, dtype=np.float64)
+    cost = coef_data * lut_data_cost[cand] + coef_shape * lut_shape_cost[cand]
+    seen = np.zeros((len(cand), nb_labels), dtype=bool)
+    seen[owner, labels[near]] = True
+    unary[:len(cand)] = np.where(seen, np.asarray(slic_weights)[cand][:, None] * cost, GC_REPLACE_INF)
+    unary[len(cand) + np.arange(len(added)), labels[added]] = 0
+    np.maximum(unary, -np.log(MAX_UNARY_PROB), out=unary)                  # no unary term claims more than MAX_UNARY_PROB
+    # an edge weighs the inverse of its length, lengths relative to their mean
+    edge_weights = 1. / compute_spatial_dist(slic_points[vertexes], edges, relative=True)
+    pen_bg, pen_fg = -np.log(prob_label_trans[0]), -np.log(prob_label_trans[1])
+    pairwise = np.full((nb_labels, nb_labels), pen_bg, dtype=np.float64)
+    pairwise[1:, 1:] = pen_fg
+    np.fill_diagonal(pairwise, 0)
+    pairwise = np.minimum(pairwise * coef_pairwise, MAX_PAIRWISE_COST)
+    return vertexes.tolist(), edges, edge_weights, unary, pairwise
+
+
+# ------------------------------------------------------------------------------------------------
+# cost updates: the threshold tests on the host, the columns by whoever holds the table
+# ------------------------------------------------------------------------------------------------
+
+
+def _update_decisions(points, labels, init_centres, centres, shifts, volumes, shape_model, shape_type, swap_shift, thresholds,
+                      object_rays):
+    """the per-object part of the two cost updates of the reference (:815-843, :938-982) without the columns: which objects get
+    a new column, with which centre, shift and table.  ``centres`` / ``shifts`` / ``volumes`` are updated in place as the reference
+    does.  ``object_rays()`` -> the raw 'down' rays [n_objects, A] and is asked for only when an object survives."""
+    labels = np.asarray(labels)
+    if shape_type not in ('cdf', 'set_cdfs'):
+        raise NameError('Not supported type of shape model "%s"' % shape_type)
+    mixture = shape_type == 'set_cdfs'
+    if mixture:
+        model = shape_model[0]
+        tables = [np.asarray(table, dtype=np.float64) for _, table in shape_model[1]]
+        widest = np.max([table.shape for table in tables], axis=0)
+    else:
+        single = np.asarray(shape_model[1], dtype=np.float64)
+    limit_centre, limit_shift, limit_volume = thresholds['centre']**2, thresholds['shift'], thresholds['volume']
+    reach = thresholds['centre_init']
+    jobs, rays_all = [], None
+    for i in range(len(centres)):
+        member = labels == i + 1
+        previous = np.array(centres[i])
+        position, turn = compute_centre_moment_points(points[member])
+        position = np.round(position).astype(int)
+        if swap_shift:                                                     # the shake: a quarter turn, taken at once
+            turn = (turn + 90) % 360
+            shifts[i] = turn
+        growth = 0
+        if mixture:
+            size = np.sum(member)
+            growth = np.abs(size - volumes[i]) / float(volumes[i]) if volumes[i] != 0 else 0
+        # a centre further than `reach` from where it began is pulled back onto that circle (and is no integer then)
+        offset = np.asarray(position) - np.asarray(init_centres[i])
+        from_start = np.sum(offset**2)
+        if from_start > reach**2:
+            position = init_centres[i] + (reach / np.sqrt(from_start)) * offset
+        moved = np.sum((np.array(position) - previous)**2)
+        settled = moved <= limit_centre and np.abs(turn - shifts[i]) <= limit_shift and growth <= limit_volume
+        if settled and not swap_shift:
+            continue                                                       # the column of this object stays
+        if moved > limit_centre:
+            centres[i] = position.tolist()
+        if np.abs(turn - shifts[i]) > limit_shift:
+            shifts[i] = turn
+        if mixture:
+            if growth > limit_volume:
+                volumes[i] = size
+            if rays_all is None:
+                rays_all = object_rays()
+            share = model.predict_proba([_finish_rays(rays_all[i])[0]]).ravel()
+            table = np.zeros(widest)
+            for weight, one in zip(share, tables):
+                table[:, :one.shape[1]] += weight * one
+        else:
+            table = single
+        jobs.append((i, [float(c) for c in centres[i]], float(shifts[i]), table))
+    return jobs
+
+
+def _mass_centres(sums, labels, n_objects):
+    """rounded centre of mass of every object's mask ``labels[slic] == i + 1`` from the exact sums of its superpixels"""
+    positions = np.zeros((n_objects, 2), dtype=np.int32)
+    for i in range(n_objects):
+        count, rows, cols = (int(v) for v in sums[np.asarray(labels) == i + 1].sum(axis=0))
+        # (an object without pixels has no centre: the position outside the map gives rays of -1)
+        positions[i] = [int(round(rows / float(count))), int(round(cols / float(count)))] if count else [-1, -1]
+    return positions
+
+
+def _public_update(lut_shape_cost, slic, points, labels, init_centres, centres, shifts, volumes, shape_model, shape_type,
+                   selected_idx, swap_shift, thresholds):
+    """the cost update on a table of the caller: the decisions of :func:`_update_decisions`, the columns in numpy"""
+    points, labels = np.asarray(points), np.asarray(labels)
+    if len(points) != len(labels):
+        raise ValueError('number of points (%i) and labels (%i) should match' % (len(points), len(labels)))
+    selected = np.arange(len(points)) if selected_idx is None else np.asarray(list(selected_idx), dtype=int)
+
+    def object_rays():
+        from pyimsegm_amd.descriptors import hip_ray_features_positions
+        from scipy.ndimage import center_of_mass
+        segm = labels.astype(int)[np.asarray(slic)]
+        step = 360 / len(shape_model[1][0][1])
+        rays = []
+        for number in range(1, len(centres) + 1):
+            start = [int(round(c)) for c in center_of_mass(segm == number)]
+            rays.append(hip_ray_features_positions(segm == number, [start], step, 'down')[0])
+        return rays
+
+    jobs = _update_decisions(points, labels, init_centres, centres, shifts, volumes, shape_model, shape_type, swap_shift, thresholds,
+                             object_rays)
+    for i, centre, shift, table in jobs:
+        prior = np.zeros(len(points))                                      # (a point that is not selected has prior 0)
+        prior[selected] = shape_prior_points(points[selected], table, centre, shift)
+        lut_shape_cost[:, i + 1] = _shape_cost(prior)
+    _replace_inf(lut_shape_cost)
+    return lut_shape_cost, np.array(centres), np.array(shifts, dtype=float), volumes
+
+
+def compute_update_shape_costs_points_table_cdf(lut_shape_cost, points, labels, init_centres, centres, shifts, volumes, shape_chist,
+                                                selected_idx=None, swap_shift=False, dict_thresholds=None):
+    """shape cost columns for the objects whose centre or orientation moved past the thresholds, from one cumulative table
+    ``shape_chist = (None, table)`` (reference :750-852; its example is in tests/doctests/region_growing.py)
+
+    :return tuple: lut_shape_cost, centres, shifts, volumes
+    """
+    return _public_update(lut_shape_cost, None, points, labels, init_centres, centres, shifts, volumes, shape_chist, 'cdf',
+                          selected_idx, swap_shift, dict_thresholds or RG2SP_THRESHOLDS)
+
+
+def compute_update_shape_costs_points_close_mean_cdf(lut_shape_cost, slic, points, labels, init_centres, centres, shifts, volumes,
+                                                     shape_model_cdfs, selected_idx=None, swap_shift=False, dict_thresholds=None):
+    """as :func:`compute_update_shape_costs_points_table_cdf` for ``shape_model_cdfs = (mixture, [(mean rays, table), ...])``: the
+    table of an object is the tables mixed by the mixture's responsibilities for the object's rays, and a change of its size also
+    asks for a new column (reference :855-990; the rays of the objects' masks on the device)
+
+    :return tuple: lut_shape_cost, centres, shifts, volumes
+    """
+    return _public_update(lut_shape_cost, slic, points, labels, init_centres, centres, shifts, volumes, shape_model_cdfs, 'set_cdfs',
+                          selected_idx, swap_shift, dict_thresholds or RG2SP_THRESHOLDS)
+
+
+def update_shape_costs_points(lut_shape_cost, slic, points, labels, init_centres, centres, shifts, volumes, shape_model, shape_type,
+                              selected_idx=None, swap_shift=False, dict_thresholds=None):
+    """the cost update for either kind of shape model, 'cdf' or 'set_cdfs' (reference :1014-1062)
+
+    :return tuple: lut_shape_cost, centres, shifts, volumes
+    """
+    if shape_type not in ('cdf', 'set_cdfs'):
+        raise NameError('Not supported type of shape model "%s"' % shape_type)
+    return _public_update(lut_shape_cost, slic if shape_type == 'set_cdfs' else None, points, labels, init_centres, centres, shifts,
+                          volumes, shape_model, shape_type, selected_idx, swap_shift, dict_thresholds or RG2SP_THRESHOLDS)
+
+
+# ------------------------------------------------------------------------------------------------
+# the two growth loops
+# ------------------------------------------------------------------------------------------------
+
+
+class _Growth(object):
+    """what both growth functions set up (:1294-1330, :1619-1665) and the steps of an iteration"""
+
+    def __init__(self, slic, slic_prob_fg, centres, shape_model, shape_type, coefs, prob_label_trans, dict_thresholds, on,
+                 background_offset):
+        slic = np.asarray(slic)
+        slic_prob_fg = np.asarray(slic_prob_fg, dtype=np.float64)
+        if len(slic_prob_fg) < np.max(slic):
+            raise ValueError('dims of probs %s and slic %s not match' % (len(slic_prob_fg), np.max(slic)))
+        if shape_type not in ('cdf', 'set_cdfs'):
+            raise NameError('Not supported type of shape model "%s"' % shape_type)
+        place = _place(on)
+        slic_prob_fg = slic_prob_fg[:int(np.max(slic)) + 1]             # (the reference reads no entry past the last label)
+        if slic.ndim != 2 or slic.min() < 0 or len(slic_prob_fg) != int(slic.max()) + 1:
+            raise ValueError('a 2-D map of labels 0 .. %i is expected for %i probabilities' % (len(slic_prob_fg) - 1, len(slic_prob_fg)))
+        self.slic, self.shape_model, self.shape_type = slic, shape_model, shape_type
+        self.thresholds = dict_thresholds or RG2SP_THRESHOLDS
+        self.init_centres = np.round(centres).astype(int).reshape(-1, 2)
+        if len(self.init_centres) == 0:
+            raise ValueError('at least one centre is required')
+        for centre in self.init_centres:
+            if not (0 <= centre[0] < slic.shape[0] and 0 <= centre[1] < slic.shape[1]):
+                raise ValueError('centre %r lies outside the map %r' % (tuple(centre.tolist()), slic.shape))
+        self.coef_data, self.coef_shape, self.coef_pairwise = coefs
+        self.prob_label_trans = prob_label_trans
+        self.terms = tuple(coefs) + _penalties(prob_label_trans)
+        n_objects = len(self.init_centres)
+        self.state = (_DeviceState if place == 'device' else _HostState)(slic, n_objects)
+        try:
+            sums = self.state.sums()
+            self.sums, self.slic_weights = sums, sums[:, 0].copy()
+            self.slic_points = self.state.points().astype(int)
+            self.edges = np.asarray(self.state.edges).reshape(-1, 2)
+            self.slic_neighbours = [[] for _ in range(len(self.slic_points))]
+            for a, b in self.edges.tolist():
+                self.slic_neighbours[a].append(b)
+                self.slic_neighbours[b].append(a)
+            self.state.attach(*_csr_neighbours(self.slic_neighbours, len(self.slic_points)))
+            labels = np.zeros(len(self.slic_points), dtype=int)
+            self.lut_data_cost, self.labels = compute_data_costs_points(slic, slic_prob_fg, self.init_centres, labels)
+            lut_shape_cost = np.zeros((len(labels), n_objects + 1))
+            with np.errstate(divide='ignore'):
+                lut_shape_cost[:, 0] = -np.log(1 - slic_prob_fg + background_offset)
+            self.state.set_costs(self.lut_data_cost, _replace_inf(lut_shape_cost))
+            self.centres = np.ones(self.init_centres.shape) * np.inf
+            self.shifts = np.zeros(n_objects)
+            self.volumes = [1] * n_objects
+            self.update(self.labels, False)
+        except Exception:
+            self.state.close()
+            raise
+
+    def _object_rays(self, labels):
+        nb_angles = len(self.shape_model[1][0][1])
+        positions = _mass_centres(self.sums, labels, len(self.init_centres))
+        return self.state.object_rays(labels, positions, _ray_directions(float(360 / nb_angles)))
+
+    def update(self, labels, swap_shift):
+        """``update_shape_costs_points`` on the resident table"""
+        centres = self.centres
+        jobs = _update_decisions(self.slic_points, labels, self.init_centres, centres, self.shifts, self.volumes, self.shape_model,
+                                 self.shape_type, swap_shift, self.thresholds, lambda: self._object_rays(labels))
+        self.centres, self.shifts = np.array(centres), np.array(self.shifts, dtype=float)
+        if jobs:
+            self.state.update_shape_costs([j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs], [j[3] for j in jobs])
+
+    def start_history(self, debug_history):
+        if debug_history is not None:
+            debug_history.update({'criteria': [], 'labels': [], 'centres': [], 'shifts': [],
+                                  'lut_data_cost': self.lut_data_cost.copy(), 'lut_shape_cost': []})
+
+    def record(self, debug_history, labels):
+        if debug_history is not None:
+            debug_history['labels'].append(labels.copy())
+            debug_history['criteria'].append(self.state.criterion(labels, *self.terms))
+            debug_history['centres'].append(self.centres.copy())
+            debug_history['shifts'].append(self.shifts.tolist())
+            debug_history['lut_shape_cost'].append(self.state.shape_costs())
+
+
+def region_growing_shape_slic_greedy(slic, slic_prob_fg, centres, shape_model, shape_type='cdf', coef_data=1., coef_shape=1,
+                                     coef_pairwise=1, prob_label_trans=(.1, .01), allow_obj_swap=True, greedy_tol=1e-3,
+                                     dict_thresholds=None, nb_iter=999, debug_history=None, on=None):
+    """grows one object per centre over the superpixels, greedily: every iteration scores each superpixel next to an object by how
+    much the energy falls if the object takes it, and applies the best changes together.  The energy weighs the foreground
+    probability, a ray shape prior around the object's centre and orientation, and the labels of neighbours.  When nothing improves
+    the orientations are turned by a quarter once (the shake); the growth ends when that does not help either
+    (reference :1155-1388; its examples are in tests/doctests/region_growing.py).
+
+    :param ndarray slic: superpixel map, labels 0 .. K - 1
+    :param list(float) slic_prob_fg: foreground probability of every superpixel
+    :param list(tuple(int,int)) centres: (row, col) where every object starts
+    :param shape_model: ``(None, table)`` for 'cdf'; ``(mixture, [(mean rays, table), ...])`` for 'set_cdfs'
+    :param str shape_type: 'cdf' or 'set_cdfs'
+    :param float coef_data: weight of the data cost
+    :param float coef_shape: weight of the shape cost
+    :param float coef_pairwise: weight of the edge penalties
+    :param prob_label_trans: probability of an edge between background and object, and between two objects
+    :param bool allow_obj_swap: an object may take superpixels of another object, not only of the background
+    :param float greedy_tol: changes within this relative distance of the best one are applied with it
+    :param dict dict_thresholds: in place of ``RG2SP_THRESHOLDS``
+    :param int nb_iter: at most this many iterations
+    :param dict debug_history: filled with the criteria, labels, centres, shifts and cost tables of every iteration
+    :param str on: 'device' or 'host' (default: the environment variable IMSEGM_RG_ON, else the device when one is present)
+    :return ndarray: label of every superpixel
+    """
+    growth = _Growth(slic, slic_prob_fg, centres, shape_model, shape_type, (coef_data, coef_shape, coef_pairwise), prob_label_trans,
+                     dict_thresholds, on, 0.)
+    try:
+        labels, state = growth.labels, growth.state
+        shakes = [False]                                   # per iteration: is the next cost update a shake (the reference's list_swap_shift)
+        growth.start_history(debug_history)
+        for _ in range(nb_iter):
+            labels = enforce_center_labels(growth.slic, labels, growth.centres)
+            growth.record(debug_history, labels)
+            growth.update(labels, shakes[-1])
+            objects, superpixels, changes = state.greedy_step(labels, allow_obj_swap, *growth.terms)
+            # falling change, equal changes in the order of the candidates (a stable sort, as the reference's sorted(reverse=True))
+            order = np.argsort(-np.asarray(changes, dtype=np.float64), kind='stable')
+            stuck = len(order) == 0 or changes[order[0]] < 0
+            if stuck and any(shakes[-7:]):
+                break                                          # a shake within the last seven iterations did not help
+            shakes.append(stuck)
+            if len(order) == 0:
+                continue
+            ranked = changes[order]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                applied = ((ranked[0] - ranked) / ranked[0] < greedy_tol) & (ranked > 0)
+            for i in order[applied]:                           # in rank order: the last change of a superpixel stays
+                labels[superpixels[i]] = objects[i]
+        return labels
+    finally:
+        growth.state.close()
+
+
+def region_growing_shape_slic_graphcut(slic, slic_prob_fg, centres, shape_model, shape_type='cdf', coef_data=1., coef_shape=1,
+                                       coef_pairwise=2, prob_label_trans=(0.1, 0.03), optim_global=True, allow_obj_swap=True,
+                                       dict_thresholds=None, nb_iter=999, debug_history=None, on=None):
+    """as :func:`region_growing_shape_slic_greedy`, with a graph cut in place of the greedy step: every iteration cuts the graph
+    of the superpixels next to an object and their neighbours (:func:`prepare_graphcut_variables`), for all objects at once or
+    object after object.  It ends when a cut changes nothing although the orientations were just shaken, or when the labelling has
+    been seen before (reference :1482-1730; its examples are in tests/doctests/region_growing.py).
+
+    :param bool optim_global: one cut for all objects; off: a cost update and a cut per object
+    :return ndarray: label of every superpixel
+    """
+    growth = _Growth(slic, slic_prob_fg, centres, shape_model, shape_type, (coef_data, coef_shape, coef_pairwise), prob_label_trans,
+                     dict_thresholds, on, 1e-9)
+    try:
+        labels, state = growth.labels, growth.state
+        seen = [np.zeros(len(labels), dtype=int)]           # every labelling so far, the empty one first
+        shakes = [False]
+        growth.start_history(debug_history)
+        nb_objects = len(growth.init_centres)
+
+        def cut(candidates, result):
+            if not len(candidates):
+                raise ValueError('no candidate for the graph cut')
+            vertexes, links, link_weights, unary, pairwise = prepare_graphcut_variables(
+                candidates, growth.slic_points, growth.slic_neighbours, growth.slic_weights, labels, nb_objects, growth.lut_data_cost,
+                state.shape_costs(), coef_data, coef_shape, coef_pairwise, prob_label_trans)
+            if len(links):
+                result[vertexes] = cut_general_graph(np.sort(links, axis=1), link_weights, unary, pairwise, n_iter=999)
+                # (a superpixel that is a candidate twice takes the label of its last vertex)
+
+        for _ in range(nb_iter):
+            labels = enforce_center_labels(growth.slic, labels, growth.centres)
+            growth.record(debug_history, labels)
+            after = labels.copy()
+            objects, superpixels, _ = state.greedy_step(labels, allow_obj_swap, *growth.terms, with_scores=False)
+            if optim_global:
+                growth.update(labels, shakes[-1])
+                cut(superpixels, after)
+            else:
+                for number in range(1, nb_objects + 1):
+                    growth.update(labels, shakes[-1])
+                    cut(superpixels[objects == number], after)
+            unchanged = np.array_equal(labels, after)
+            if unchanged and (any(shakes[-2:]) or any(np.array_equal(after, old) for old in seen[:-1])):
+                break                                          # shaken already, or back at an earlier labelling
+            shakes.append(unchanged)
+            labels = after
+            seen.append(labels.copy())
+        return labels
+    finally:
+        growth.state.close()
