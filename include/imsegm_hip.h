@@ -388,7 +388,9 @@ IMSEGM_API int imsegm_batch2d_run_color(imsegm_batch2d *batch, int n_images, con
                                         const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
                                         const int32_t *classes_lut, int32_t *const *segm_out, int *n_labels_out);
 /* device address of a result of image `image` of the last batch: which = 0 label map, 1 segmentation (int32 H x W each),
- * 2 feature table (float64, n_labels_out[image] rows of 3 x (number of feature_mask bits) columns: mean | std | energy) */
+ * 2 feature table (float64, n_labels_out[image] rows of 3 x (number of feature_mask bits) columns: mean | std | energy),
+ * 3 the pre-processed planes SLIC ran on (float64 3 x H x W), 4 {min, max} of the image and the largest |value| of those planes
+ * (three float64) */
 IMSEGM_API int imsegm_batch2d_device_ptr(imsegm_batch2d *batch, int image, int which, void **ptr_out);
 
 /* The 'median' and 'meanGrad' statistics of compute_image2d_color_statistic / compute_image3d_gray_statistic

@@ -1427,6 +1427,21 @@ class Batch2D(object):
             self.ctx.copy(out.ctypes.data, ptr.value, out.nbytes, synchronize=True)
         return out
 
+    def _get_f64(self, image, which, shape):
+        ptr = _vp()
+        _check(load_library().imsegm_batch2d_device_ptr(self._h, int(image), which, C.byref(ptr)))
+        out = np.empty(shape, dtype=np.float64)
+        self.ctx.copy(out.ctypes.data, ptr.value, out.nbytes, synchronize=True)
+        return out
+
+    def get_lab(self, image):
+        """the pre-processed planes of image ``image`` of the last batch on the host (float64 3 x H x W), as :meth:`Image2D.get_lab`"""
+        return self._get_f64(image, 3, (3, ) + self.shape)
+
+    def get_pre_scalars(self, image):
+        """(min, max, premax) of image ``image`` of the last batch, as :meth:`Image2D.get_pre_scalars`"""
+        return tuple(float(v) for v in self._get_f64(image, 4, (3, )))
+
     def get_labels(self, image):
         """superpixel map of image ``image`` of the last batch on the host (int64, the dtype scikit-image leaks)"""
         arr = self.labels_device_array(image)

@@ -149,8 +149,10 @@ int imsegm_batch2d_device_ptr(imsegm_batch2d *bt, int image, int which, void **p
     if (which == 0) *ptr_out = base + L.labels;
     else if (which == 1) *ptr_out = base + L.segm_out;
     else if (which == 2) *ptr_out = base + L.featK;
+    else if (which == 3) *ptr_out = base + L.lab;
+    else if (which == 4) *ptr_out = base + L.small + 2 * sizeof(unsigned long long);     // (behind the two key words, as run_color places them)
     else {
-        set_error("batch2d_device_ptr: which = 0 (label map), 1 (segmentation) or 2 (feature table)");
+        set_error("batch2d_device_ptr: which = 0 (label map), 1 (segmentation), 2 (feature table), 3 (pre-processed planes) or 4 (min, max, premax)");
         return -1;
     }
     return 0;

@@ -317,19 +317,229 @@ k_blur_axis(const double *__restrict__ src, double *__restrict__ dst, int H, int
 
 // ---------------------------------------------------------------------------------------------
 // fused pre-processing: the three passes above in one kernel (same operations in the same order, so the
-// planes are bit-identical), 27 B/px of HBM traffic instead of 96.  A workgroup produces a 64 x 16 tile:
-// Lab (+ z tap) of the tile and its blur halo goes to LDS (the halo is converted redundantly, x1.7), the y
-// pass runs LDS -> LDS one channel at a time, the x pass LDS -> HBM with the final 1/compactness.
+// planes are bit-identical), 27 B/px of HBM traffic instead of 96.  A workgroup converts its tile and the blur
+// halo to Lab (+ z tap) into LDS (the halo redundantly), blurs along y inside LDS and along x from LDS to HBM
+// with the final 1/compactness.  Two kernels share the conversion: k_pre_fused for the radius 4 of sigma = 1
+// (every 2-D SLIC call of the pipelines), k_pre_fused_any for every other radius up to PF_MAXR.
 // ---------------------------------------------------------------------------------------------
-// (tile geometry, measured: a 32 x 32 tile converts 40 x 40 pixels per 32 x 32 outputs, x1.56 instead of x1.69, in 48 KB of LDS:
-// 125.8 against 129.0 us)
-constexpr int PF_TX = 64, PF_TY = 16, PF_MAXR = 8, PF_THREADS = 512;
-static_assert(PF_THREADS % PF_TX == 0 && PF_TY % (PF_THREADS / PF_TX) == 0, "x pass: whole rows per pass");
+constexpr int PF_TX = 64, PF_MAXR = 8, PF_THREADS = 512;
+
+// uint8 input: the sRGB linearisation collapses to a 256-entry table (threads 0 .. 255 fill it; the caller's barrier follows)
+__device__ __forceinline__ void pf_fill_lut(double *lut, bool norm, const double *__restrict__ minmax)
+{
+    if (threadIdx.x < 256) {
+        const int v = threadIdx.x;
+        double x;
+        if (norm) {
+            double vmin = minmax[0], range = minmax[1] - minmax[0];
+            x = (double)(uint8_t)(v - (int)vmin) / range;
+        } else {
+            x = (double)v * (1.0 / 255);
+        }
+        lut[v] = (x > 0.04045) ? det_pow24((x + 0.055) / 1.055) : x / 12.92;
+    }
+}
+
+// the three bytes of pixel p in bits 0 .. 23: one unaligned 32-bit load (the fourth byte belongs to the next pixel; the last
+// pixel of the image has none and is read byte by byte)
+__device__ __forceinline__ uint32_t pf_load_u8(const uint8_t *__restrict__ img, size_t p, size_t n_pixels)
+{
+    uint32_t w;
+    if (p + 1 < n_pixels)
+        __builtin_memcpy(&w, img + 3 * p, 4);
+    else
+        w = (uint32_t)img[3 * p] | ((uint32_t)img[3 * p + 1] << 8) | ((uint32_t)img[3 * p + 2] << 16);
+    return w;
+}
+
+// the z tap of the fused kernels: ZR >= 0 is the radius known at compile time (no tap beyond it is formed and thrown away), ZR < 0
+// any radius up to PF_MAXR
+template <int ZR>
+__device__ __forceinline__ double pf_ztap(double v, const Taps &tz)
+{
+    if constexpr (ZR < 0) {
+        return zblur_point_unrolled<PF_MAXR>(v, tz);
+    } else {
+        double tmp = v * tz.w[0];
+        const double vv = v + v;
+#pragma unroll
+        for (int j = ZR; j >= 1; --j) tmp += vv * tz.w[j];
+        return tmp;
+    }
+}
+
+// Lab + z tap of a uint8 pixel (`w` from pf_load_u8)
+template <int ZR>
+__device__ __forceinline__ void pf_lab_u8(uint32_t w, const double *lut, const Taps &tz, double &L, double &A, double &B)
+{
+    double lin0 = lut[w & 0xffu], lin1 = lut[(w >> 8) & 0xffu], lin2 = lut[(w >> 16) & 0xffu];
+    double X = lin0 * 0.412453 + lin1 * 0.357580 + lin2 * 0.180423;
+    double Y = lin0 * 0.212671 + lin1 * 0.715160 + lin2 * 0.072169;
+    double Z = lin0 * 0.019334 + lin1 * 0.119193 + lin2 * 0.950227;
+    // (uint8 pixels: X, Z are 0 or >= 5.9e-6, far inside 2^+-500 -- the exact three-instruction quotient; Y / 1.0 = Y)
+    double f[3] = { DIV_CONST_IN_RANGE(X, 0.95047), Y, DIV_CONST_IN_RANGE(Z, 1.08883) };
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double t = f[c];
+        f[c] = (t > 0.008856) ? det_cbrt(t) : 7.787 * t + 16.0 / 116.0;
+    }
+    L = pf_ztap<ZR>((116.0 * f[1]) - 16.0, tz);
+    A = pf_ztap<ZR>(500.0 * (f[0] - f[1]), tz);
+    B = pf_ztap<ZR>(200.0 * (f[1] - f[2]), tz);
+}
+
+// Lab + z tap of a float / double pixel
+template <int ZR, typename T>
+__device__ __forceinline__ void pf_lab_f(const T *__restrict__ img, size_t p, bool norm, const double *__restrict__ minmax, const Taps &tz,
+                                         double &L, double &A, double &B)
+{
+    double rgb[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double v = (double)img[3 * p + c];
+        if (norm) v = (v - minmax[0]) / (minmax[1] - minmax[0]);
+        rgb[c] = v;
+    }
+    rgb2lab_px(rgb[0], rgb[1], rgb[2], L, A, B);
+    L = pf_ztap<ZR>(L, tz);
+    A = pf_ztap<ZR>(A, tz);
+    B = pf_ztap<ZR>(B, tz);
+}
+
+// ---- radius 4 on the three axes ----
+// A workgroup of 1 024 threads produces a 64 x 32 tile from ONE LDS image of [3][40][72] doubles (68 KB: two workgroups a CU,
+// eight waves a SIMD).  72 x 40 pixels are converted per 64 x 32 outputs (x1.41), 2 880 = 45 whole waves of them, so no lane
+// idles in the conversion; the z tap has its radius at compile time (no tap beyond it is formed and thrown away).  The y pass
+// blurs the three channels together and out of registers: a thread owns a column and P4_RUN consecutive rows, loads the
+// P4_RUN + 8 values of that window once and forms every output from it (lanes = adjacent columns: conflict-free); all windows
+// are in registers at the next barrier, after which the outputs go back IN PLACE (rows 0 .. 31 of each channel).  The x pass
+// reads rows of LDS with lane = column -- whole 512-byte rows, conflict-free, and whole rows to HBM.  (A run of adjacent columns
+// per thread was not built for x: lanes 64 bytes apart meet four at a time on the same banks, 16 LDS cycles per 16-byte read,
+// and every store instruction would touch 32 cache lines.)  Three barriers after the table's.  Each sum keeps its order, j from
+// 4 down to 1.  Shapes measured and not kept: profiles/README_pre.md.
+constexpr int P4_R = 4, P4_TY = 32, P4_RUN = 8, P4_THREADS = 1024;
+constexpr int P4_TW = PF_TX + 2 * P4_R, P4_TH = P4_TY + 2 * P4_R, P4_PLANE = P4_TH * P4_TW;
+constexpr int P4_NCONV = (P4_PLANE + P4_THREADS - 1) / P4_THREADS;         // conversions per thread (the last round is partial)
+constexpr int P4_G = P4_TY / P4_RUN, P4_NY = 3 * P4_G * P4_TW;             // y pass: windows per column and channel, windows in all
+constexpr int P4_YITEMS = (P4_NY + P4_THREADS - 1) / P4_THREADS;
+constexpr int P4_ROWS = P4_THREADS / PF_TX;                                // x pass: rows per round
+constexpr size_t P4_LDS = (size_t)3 * P4_PLANE * sizeof(double);
+static_assert(P4_TY % P4_RUN == 0 && P4_TY % P4_ROWS == 0 && P4_THREADS % PF_TX == 0, "whole windows, whole rows per round");
+static_assert(2 * (P4_LDS + 256 * sizeof(double) + 16 * sizeof(unsigned long long)) <= 160 * 1024, "two workgroups a CU");
+
+template <typename T>
+__global__ void __launch_bounds__(P4_THREADS, 8)      // (two workgroups a CU are eight waves a SIMD)
+k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double *__restrict__ minmax, Taps tz, Taps ty,
+            Taps tx, double ratio, double *__restrict__ out, double *premax, size_t zs)
+{
+    ZSHIFT(img, zs); ZSHIFT(minmax, zs); ZSHIFT(out, zs); ZSHIFT(premax, zs);
+    extern __shared__ double pf_sm[];                     // [3][P4_TH][P4_TW]: Lab + z tap, then (rows 0 .. P4_TY - 1) y-blurred
+    __shared__ double lut[256];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * PF_TX, y0 = blockIdx.y * P4_TY;
+    const size_t plane = (size_t)H * W;
+    const bool norm = normalize == 1 || (normalize == 2 && (minmax[0] != 0.0 || minmax[1] != 1.0));
+    if constexpr (sizeof(T) == 1) {
+        pf_fill_lut(lut, norm, minmax);
+        __syncthreads();
+        // every pixel word of the thread requested before the first conversion waits for one
+        uint32_t px[P4_NCONV];
+#pragma unroll
+        for (int k = 0; k < P4_NCONV; ++k) {
+            const int i = tid + k * P4_THREADS;
+            if (i < P4_PLANE) {
+                const int ly = i / P4_TW, lx = i - ly * P4_TW;
+                const int gy = reflect_idx(y0 + ly - P4_R, H), gx = reflect_idx(x0 + lx - P4_R, W);
+                px[k] = pf_load_u8(img, (size_t)gy * W + gx, plane);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < P4_NCONV; ++k) {
+            const int i = tid + k * P4_THREADS;
+            if (i < P4_PLANE) {
+                double L, A, B;
+                pf_lab_u8<P4_R>(px[k], lut, tz, L, A, B);
+                pf_sm[i] = L;
+                pf_sm[P4_PLANE + i] = A;
+                pf_sm[2 * P4_PLANE + i] = B;
+            }
+        }
+    } else {
+        for (int i = tid; i < P4_PLANE; i += P4_THREADS) {
+            const int ly = i / P4_TW, lx = i - ly * P4_TW;
+            const int gy = reflect_idx(y0 + ly - P4_R, H), gx = reflect_idx(x0 + lx - P4_R, W);
+            double L, A, B;
+            pf_lab_f<P4_R>(img, (size_t)gy * W + gx, norm, minmax, tz, L, A, B);
+            pf_sm[i] = L;
+            pf_sm[P4_PLANE + i] = A;
+            pf_sm[2 * P4_PLANE + i] = B;
+        }
+    }
+    __syncthreads();
+    // y pass, the three channels at once: window `item` is (channel, row group, column), columns fastest
+    double yo[P4_YITEMS][P4_RUN];
+#pragma unroll
+    for (int k = 0; k < P4_YITEMS; ++k) {
+        const int item = tid + k * P4_THREADS;
+        if (item < P4_NY) {
+            const int cg = item / P4_TW, lx = item - cg * P4_TW;
+            const double *col = pf_sm + ((cg / P4_G) * P4_TH + (cg % P4_G) * P4_RUN) * P4_TW + lx;
+            double win[P4_RUN + 2 * P4_R];
+#pragma unroll
+            for (int m = 0; m < P4_RUN + 2 * P4_R; ++m) win[m] = col[m * P4_TW];
+#pragma unroll
+            for (int q = 0; q < P4_RUN; ++q) {
+                double v = win[q + P4_R] * ty.w[0];
+#pragma unroll
+                for (int j = P4_R; j >= 1; --j) v += (win[q + P4_R - j] + win[q + P4_R + j]) * ty.w[j];
+                yo[k][q] = v;
+            }
+        }
+    }
+    __syncthreads();                                      // every window is in registers: the outputs may overwrite the inputs
+#pragma unroll
+    for (int k = 0; k < P4_YITEMS; ++k) {
+        const int item = tid + k * P4_THREADS;
+        if (item < P4_NY) {
+            const int cg = item / P4_TW, lx = item - cg * P4_TW;
+            double *col = pf_sm + ((cg / P4_G) * P4_TH + (cg % P4_G) * P4_RUN) * P4_TW + lx;
+#pragma unroll
+            for (int q = 0; q < P4_RUN; ++q) col[q * P4_TW] = yo[k][q];
+        }
+    }
+    __syncthreads();
+    // x pass: lane = column, a wave per row
+    double vmax = 0.0;                                    // max |value written| by this thread
+    const int ox = tid % PF_TX, oy0 = tid / PF_TX;
+    const int gx = x0 + ox;
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int q = 0; q < P4_TY / P4_ROWS; ++q) {
+            const int oy = oy0 + P4_ROWS * q;
+            const double *row = pf_sm + (c * P4_TH + oy) * P4_TW + ox + P4_R;
+            double v = row[0] * tx.w[0];
+#pragma unroll
+            for (int j = P4_R; j >= 1; --j) v += (row[-j] + row[j]) * tx.w[j];
+            v = v * ratio;
+            const int gy = y0 + oy;
+            if (gy < H && gx < W) {
+                out[(size_t)c * plane + (size_t)gy * W + gx] = v;
+                vmax = fmax(vmax, fabs(v));
+            }
+        }
+    }
+    block_absmax_to(vmax, premax);
+}
+
+// ---- any radius up to PF_MAXR (and none: r < 0) ----
+// A 64 x 16 tile; the y pass runs LDS -> LDS one channel at a time, the x pass LDS -> HBM, every tap read from LDS.
+constexpr int PF_TY = 16;
+static_assert(PF_TY % (PF_THREADS / PF_TX) == 0, "x pass: whole rows per pass");
 
 template <typename T>
 __global__ void __launch_bounds__(PF_THREADS)
-k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double *__restrict__ minmax, Taps tz, Taps ty,
-            Taps tx, double ratio, double *__restrict__ out, double *premax, size_t zs)
+k_pre_fused_any(const T *__restrict__ img, int H, int W, int normalize, const double *__restrict__ minmax, Taps tz, Taps ty,
+                Taps tx, double ratio, double *__restrict__ out, double *premax, size_t zs)
 {
     ZSHIFT(img, zs); ZSHIFT(minmax, zs); ZSHIFT(out, zs); ZSHIFT(premax, zs);
     double vmax = 0.0;                                    // max |value written| by this thread
@@ -343,18 +553,7 @@ k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double
     double *L2 = pf_sm + (size_t)3 * th * tw;             // [PF_TY][tw]  y-blurred, one channel at a time
     const bool norm = normalize == 1 || (normalize == 2 && (minmax[0] != 0.0 || minmax[1] != 1.0));
     if (sizeof(T) == 1) {
-        // uint8 input: the sRGB linearisation collapses to a 256-entry table
-        if (tid < 256) {
-            const int v = tid;
-            double x;
-            if (norm) {
-                double vmin = minmax[0], range = minmax[1] - minmax[0];
-                x = (double)(uint8_t)(v - (int)vmin) / range;
-            } else {
-                x = (double)v * (1.0 / 255);
-            }
-            lut[v] = (x > 0.04045) ? det_pow24((x + 0.055) / 1.055) : x / 12.92;
-        }
+        pf_fill_lut(lut, norm, minmax);
         __syncthreads();
     }
     const int x0 = blockIdx.x * PF_TX, y0 = blockIdx.y * PF_TY;
@@ -364,34 +563,13 @@ k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double
         const int gy = reflect_idx(y0 + ly - ry, H), gx = reflect_idx(x0 + lx - rx, W);
         const size_t p = (size_t)gy * W + gx;
         double L, A, B;
-        if (sizeof(T) == 1) {
-            double lin0 = lut[(int)img[3 * p + 0]], lin1 = lut[(int)img[3 * p + 1]], lin2 = lut[(int)img[3 * p + 2]];
-            double X = lin0 * 0.412453 + lin1 * 0.357580 + lin2 * 0.180423;
-            double Y = lin0 * 0.212671 + lin1 * 0.715160 + lin2 * 0.072169;
-            double Z = lin0 * 0.019334 + lin1 * 0.119193 + lin2 * 0.950227;
-            // (uint8 pixels: X, Z are 0 or >= 5.9e-6, far inside 2^+-500 -- the exact three-instruction quotient; Y / 1.0 = Y)
-            double f[3] = { DIV_CONST_IN_RANGE(X, 0.95047), Y, DIV_CONST_IN_RANGE(Z, 1.08883) };
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double t = f[c];
-                f[c] = (t > 0.008856) ? det_cbrt(t) : 7.787 * t + 16.0 / 116.0;
-            }
-            L = (116.0 * f[1]) - 16.0;
-            A = 500.0 * (f[0] - f[1]);
-            B = 200.0 * (f[1] - f[2]);
-        } else {
-            double rgb[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double v = (double)img[3 * p + c];
-                if (norm) v = (v - minmax[0]) / (minmax[1] - minmax[0]);
-                rgb[c] = v;
-            }
-            rgb2lab_px(rgb[0], rgb[1], rgb[2], L, A, B);
-        }
-        L1[i] = zblur_point_unrolled<PF_MAXR>(L, tz);
-        L1[th * tw + i] = zblur_point_unrolled<PF_MAXR>(A, tz);
-        L1[2 * th * tw + i] = zblur_point_unrolled<PF_MAXR>(B, tz);
+        if constexpr (sizeof(T) == 1)
+            pf_lab_u8<-1>(pf_load_u8(img, p, plane), lut, tz, L, A, B);
+        else
+            pf_lab_f<-1>(img, p, norm, minmax, tz, L, A, B);
+        L1[i] = L;
+        L1[th * tw + i] = A;
+        L1[2 * th * tw + i] = B;
     }
     __syncthreads();
     const int ox = tid % PF_TX, oy0 = tid / PF_TX;
@@ -438,6 +616,28 @@ k_pre_fused(const T *__restrict__ img, int H, int W, int normalize, const double
     block_absmax_to(vmax, premax);
 }
 
+template <typename T>
+static int launch_pre_fused(const T *img, int H, int W, int normalize, const double *minmax_dev, const Taps &tz, const Taps &ty,
+                            const Taps &tx, double ratio, double *out, double *premax_dev, hipStream_t st, ZBatch zb, int dtype)
+{
+    const bool r4 = tz.r == P4_R && ty.r == P4_R && tx.r == P4_R;
+    const int ry = ty.r < 0 ? 0 : ty.r, rx = tx.r < 0 ? 0 : tx.r;
+    const size_t lds = r4 ? P4_LDS : ((size_t)3 * (PF_TY + 2 * ry) + PF_TY) * (PF_TX + 2 * rx) * sizeof(double);
+    const auto fn = r4 ? k_pre_fused<T> : k_pre_fused_any<T>;
+    // the opt-in above 48 KB is per device: remembered per (device, kernel, dtype); (benign race: the attribute only ever grows)
+    static size_t lds_set[IMSEGM_MAX_DEVICES][2][3];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= IMSEGM_MAX_DEVICES || lds_set[dev][r4][dtype] < lds) {
+        HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < IMSEGM_MAX_DEVICES) lds_set[dev][r4][dtype] = lds;
+    }
+    const dim3 grid(cdiv(W, PF_TX), cdiv(H, r4 ? P4_TY : PF_TY), zb.nz);
+    hipLaunchKernelGGL(fn, grid, r4 ? P4_THREADS : PF_THREADS, lds, st, img, H, W, normalize, minmax_dev, tz, ty, tx, ratio, out, premax_dev, zb.zs);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int launch_preprocess_color2d(const void *img, int dtype, int H, int W, int normalize, const double *minmax_dev,
                               const Taps &tz, const Taps &ty, const Taps &tx, double ratio, double *bufA,
                               double *bufB, double *premax_dev, hipStream_t st, bool premax_zeroed, ZBatch zb)
@@ -445,19 +645,6 @@ int launch_preprocess_color2d(const void *img, int dtype, int H, int W, int norm
     int n = H * W;
     int grid = cdiv(n, 256);
     if (tz.r <= PF_MAXR && ty.r <= PF_MAXR && tx.r <= PF_MAXR && !knobs().pre_3pass) {
-        const int ry = ty.r < 0 ? 0 : ty.r, rx = tx.r < 0 ? 0 : tx.r;
-        const size_t lds = ((size_t)3 * (PF_TY + 2 * ry) + PF_TY) * (PF_TX + 2 * rx) * sizeof(double);
-        const void *fn = dtype == DT_U8 ? (const void *)k_pre_fused<uint8_t>
-                       : dtype == DT_F32 ? (const void *)k_pre_fused<float> : (const void *)k_pre_fused<double>;
-        // the opt-in above 48 KB is per device: remembered per (device, dtype); (benign race: the attribute only ever grows)
-        static size_t lds_set[IMSEGM_MAX_DEVICES][3];
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        if (dev < 0 || dev >= IMSEGM_MAX_DEVICES || lds_set[dev][dtype] < lds) {
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < IMSEGM_MAX_DEVICES) lds_set[dev][dtype] = lds;
-        }
-        dim3 gf(cdiv(W, PF_TX), cdiv(H, PF_TY), zb.nz);
         if (!premax_zeroed) {
             if (zb.nz > 1) {
                 set_error("preprocess: a batch needs its premax words zeroed by the caller");
@@ -465,17 +652,12 @@ int launch_preprocess_color2d(const void *img, int dtype, int H, int W, int norm
             }
             HIP_TRY(hipMemsetAsync(premax_dev, 0, sizeof(double), st));
         }
+        // result in bufA
         if (dtype == DT_U8)
-            hipLaunchKernelGGL(k_pre_fused<uint8_t>, gf, PF_THREADS, lds, st, (const uint8_t *)img, H, W, normalize, minmax_dev, tz, ty, tx,
-                               ratio, bufA, premax_dev, zb.zs);
-        else if (dtype == DT_F32)
-            hipLaunchKernelGGL(k_pre_fused<float>, gf, PF_THREADS, lds, st, (const float *)img, H, W, normalize, minmax_dev, tz, ty, tx,
-                               ratio, bufA, premax_dev, zb.zs);
-        else
-            hipLaunchKernelGGL(k_pre_fused<double>, gf, PF_THREADS, lds, st, (const double *)img, H, W, normalize, minmax_dev, tz, ty, tx,
-                               ratio, bufA, premax_dev, zb.zs);
-        HIP_TRY(hipGetLastError());
-        return 0;   // result in bufA
+            return launch_pre_fused((const uint8_t *)img, H, W, normalize, minmax_dev, tz, ty, tx, ratio, bufA, premax_dev, st, zb, dtype);
+        if (dtype == DT_F32)
+            return launch_pre_fused((const float *)img, H, W, normalize, minmax_dev, tz, ty, tx, ratio, bufA, premax_dev, st, zb, dtype);
+        return launch_pre_fused((const double *)img, H, W, normalize, minmax_dev, tz, ty, tx, ratio, bufA, premax_dev, st, zb, dtype);
     }
     if (zb.nz > 1) {
         set_error("preprocess: the three-pass path (blur radius > 8) does not take a batch");
