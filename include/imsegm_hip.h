@@ -607,6 +607,30 @@ IMSEGM_API int imsegm_ellipse_ransac(imsegm_ctx *ctx, int n_eggs, const int32_t 
                                      double *residuals_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * From an egg class map with centre candidates to the rays the boundary points of the RANSAC are made of (imsegm/ellipse_fitting.py
+ * split_segm_background_foreground :400-443 and the ray casting of prepare_boundary_points_ray_join / _edge / _mean / _dist
+ * :352-597); csrc/morphology.hip.  Integers only up to the ray walk: same call, same bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_MORPH_MAX_RADIUS 64         /* the 64 x 64 tile of the disc kernels with its halo fits 48 KiB of LDS */
+/* Replaces split_segm_background_foreground(seg, sel_bg, sel_fg) (ellipse_fitting.py:400-443) for integer radii: seg_bg = 1 -
+ * scipy.ndimage.binary_fill_holes(segm > 0) and seg_fg = (segm == 1), each opened with skimage.morphology.disk(sel) when sel > 0
+ * (opening :438, :442 = grey erosion and dilation with scipy's boundary mode 'reflect', which for a disc equals "pixels outside
+ * the image do not count").  segm: host int32, height x width; the outputs host uint8 of the same shape, either may be NULL (a NULL
+ * seg_fg_out skips the foreground opening).  Returns -1 (no launch) for a radius above IMSEGM_MORPH_MAX_RADIUS, a non-positive
+ * height or width, more than 65535 rows or 2^31 pixels. */
+IMSEGM_API int imsegm_split_background_foreground(imsegm_ctx *ctx, const int32_t *segm, int height, int width, int sel_bg, int sel_fg,
+                                                  uint8_t *seg_bg_out, uint8_t *seg_fg_out);
+/* Replaces the split and the two compute_ray_features_segm_2d calls per centre of prepare_boundary_points_ray_* (:381-390, :476-482,
+ * :527-533, :577-581): the masks above stay on the device, the rays of all positions (row, col) on seg_bg with edge 'up' go to
+ * rays_bg_out and on seg_fg with edge 'down' to rays_fg_out (n_positions x n_angles float32, -1: no edge met, also for a position
+ * outside the map), both from one launch; directions as imsegm_ray_features_binary2d.  Either output may be NULL; a NULL
+ * rays_fg_out skips the foreground opening entirely.  Returns -1 (no launch) as imsegm_split_background_foreground does and for
+ * n_angles outside [1, IMSEGM_RAY_MAX_ANGLES]. */
+IMSEGM_API int imsegm_boundary_rays(imsegm_ctx *ctx, const int32_t *segm, int height, int width, int sel_bg, int sel_fg,
+                                    const int32_t *positions, int n_positions, const float *directions, int n_angles,
+                                    float *rays_bg_out, float *rays_fg_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Region growing with a ray shape prior on superpixels (imsegm/region_growing.py region_growing_shape_slic_greedy :1155-1388,
  * region_growing_shape_slic_graphcut :1482-1730): a resident state on top of a label session; csrc/region_growing.hip.  The host
  * keeps the iteration, the thresholds, LAPACK's eigenvectors and the mixture weights (pyimsegm_amd/region_growing.py)

@@ -181,6 +181,8 @@ _SIGNATURES = {
     'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
     'imsegm_ellipse_ransac': (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                         _vp]),
+    'imsegm_split_background_foreground': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    'imsegm_boundary_rays': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     'imsegm_rg_open': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     'imsegm_rg_close': (None, [_vp]),
     'imsegm_rg_get': (C.c_int, [_vp, C.c_int, _vp]),
@@ -1637,6 +1639,35 @@ def ellipse_ransac(point_offsets, points, params, success, trial_egg, points_all
                                                 float(residual_threshold), _ptr(best), _ptr(kept), _ptr(mask), _ptr(criterion),
                                                 _ptr(residuals)))
     return best, kept, mask, criterion, residuals
+
+
+#: ``IMSEGM_MORPH_MAX_RADIUS``: the largest disc radius of the opening kernels
+MORPH_MAX_RADIUS = 64
+
+
+def split_background_foreground(segm, sel_bg, sel_fg, ctx=None):
+    """``imsegm_split_background_foreground`` on a 2-D class map and integer radii: (seg_bg, seg_fg) uint8 H x W"""
+    ctx = ctx or default_context()
+    segm = np.ascontiguousarray(segm, dtype=np.int32)
+    seg_bg, seg_fg = np.empty(segm.shape, dtype=np.uint8), np.empty(segm.shape, dtype=np.uint8)
+    _check(load_library().imsegm_split_background_foreground(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], int(sel_bg), int(sel_fg),
+                                                             _ptr(seg_bg), _ptr(seg_fg)))
+    return seg_bg, seg_fg
+
+
+def boundary_rays(segm, sel_bg, sel_fg, positions, directions, with_fg=True, ctx=None):
+    """``imsegm_boundary_rays``: the rays of all positions on the smoothed background mask (edge 'up') and, ``with_fg``, on the
+    smoothed foreground mask (edge 'down') of a 2-D class map, the masks staying on the device: (float32 [P, A], float32 [P, A] or
+    None)"""
+    ctx = ctx or default_context()
+    segm = np.ascontiguousarray(segm, dtype=np.int32)
+    positions = np.ascontiguousarray(positions, dtype=np.int32).reshape(-1, 2)
+    directions = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 2)
+    rays_bg = np.empty((len(positions), len(directions)), dtype=np.float32)
+    rays_fg = np.empty_like(rays_bg) if with_fg else None
+    _check(load_library().imsegm_boundary_rays(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], int(sel_bg), int(sel_fg), _ptr(positions),
+                                               len(positions), _ptr(directions), len(directions), _ptr(rays_bg), _ptr(rays_fg)))
+    return rays_bg, rays_fg
 
 
 def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):

@@ -1,0 +1,25 @@
+// morphology.h -- what api_morphology.hip launches from morphology.hip: hole filling, disc erosion / dilation of uint8 masks and the
+// rays of all centres on the two smoothed masks of imsegm/ellipse_fitting.py split_segm_background_foreground (:400-443)
+#pragma once
+#include "common.h"
+
+namespace imsegm {
+
+// the largest disc radius the tiles of k_disc_morph hold with their halo (IMSEGM_MORPH_MAX_RADIUS of include/imsegm_hip.h)
+constexpr int MORPH_MAX_RADIUS = 64;
+
+// seg_bg[p] = 1 - binary_fill_holes(segm > 0)[p] and seg_fg[p] = (segm[p] == 1): ONE labelling of the 4-connected components of the
+// pixels with segm <= 0 (union-find, smallest index = root), a flag per root that a border pixel raised, one write pass.
+// parent: H * W words, touches: H * W bytes of scratch.  H <= 65535 and H * W < 2^31 (morph_size_ok)
+int morph_size_ok(int H, int W);
+int launch_fill_holes_split(const int32_t *segm, int H, int W, int32_t *parent, uint8_t *touches, uint8_t *seg_bg, uint8_t *seg_fg,
+                            hipStream_t st);
+// out = erosion (dilate == 0) or dilation (dilate == 1) of the mask `in` by the disc dy^2 + dx^2 <= r^2, pixels outside the image
+// not counted (1 <= r <= MORPH_MAX_RADIUS; in != out)
+int launch_disc_morph(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, hipStream_t st);
+// rays of P positions on seg_bg with edge 'up' into rays_bg and on seg_fg with edge 'down' into rays_fg (P x A float32 each, either
+// may be null), one launch
+int launch_boundary_rays(const uint8_t *seg_bg, const uint8_t *seg_fg, int H, int W, const int32_t *positions, int P, const float *grad,
+                         int A, float *rays_bg, float *rays_fg, hipStream_t st);
+
+}  // namespace imsegm

@@ -1,0 +1,239 @@
+// morphology.hip -- the smoothing of an egg class map and the rays on its two masks, on the device:
+//   split_segm_background_foreground     imsegm/ellipse_fitting.py:400-443 (scipy.ndimage binary_fill_holes, skimage.morphology
+//                                        opening with disk(r) for integer r)
+//   compute_ray_features_segm_2d         per centre on seg_bg ('up') and seg_fg ('down'), ellipse_fitting.py:385-390, :480-482,
+//                                        :531-533, :581 (the walk of k_ray_features_binary2d, natives.hip)
+// Integers only up to the ray walk: a pixel survives the erosion when no 0 of the image lies within dy^2 + dx^2 <= r^2 of it, and is
+// set by the dilation when a surviving pixel does; pixels outside the image never count ("Boundary points").
+#include "morphology.h"
+#include "unionfind.h"
+
+namespace imsegm {
+
+// ---- hole filling: one labelling of the zero pixels (segm <= 0), 4-connected -------------------------------------------------
+// A wave covers 64 consecutive pixels of a row (the segments start at multiples of 64 in every row).  Every zero pixel starts out
+// pointing at the first pixel of its run INSIDE its segment, so the unions that are left lie where a run crosses a segment and
+// where a run meets the row above for the first time.
+__global__ void __launch_bounds__(256) k_holes_init(const int32_t *__restrict__ segm, int32_t *__restrict__ parent, int W)
+{
+    const int lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const size_t row = (size_t)blockIdx.y * W;
+    const bool inx = x < W;
+    const bool zero = inx && segm[row + x] <= 0;
+    const unsigned long long z = __ballot(zero);
+    if (!inx) return;
+    int start = lane;
+    if (zero) {
+        const unsigned long long starts = z & ~(z << 1);
+        const unsigned long long below = starts & ((2ULL << lane) - 1ULL);
+        start = 63 - __clzll((long long)below);
+    }
+    parent[row + x] = (int)(row + x) - (lane - start);
+}
+
+// p and the pixel above it are tied when p starts a run of its segment or the pixel above p - 1 is no zero: otherwise p - 1 is tied
+// to the pixel above it, which shares a run (and a segment) with the pixel above p
+__global__ void __launch_bounds__(256) k_holes_merge(const int32_t *__restrict__ segm, int32_t *parent, int W)
+{
+    const int lane = threadIdx.x & 63;
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    const size_t row = (size_t)y * W;
+    const bool inx = x < W;
+    const bool zero = inx && segm[row + x] <= 0;
+    const bool up = zero && y > 0 && segm[row - W + x] <= 0;
+    const bool up_any = inx && y > 0 && segm[row - W + x] <= 0;
+    const unsigned long long z = __ballot(zero), zu = __ballot(up_any);
+    if (!zero) return;
+    const int p = (int)(row + x);
+    const bool first = lane == 0 || !((z >> (lane - 1)) & 1ULL);
+    if (lane == 0 && x > 0 && segm[p - 1] <= 0) uf_union_pair(parent, p, p - 1);
+    if (up && (first || !((zu >> (lane - 1)) & 1ULL))) uf_union_pair(parent, p, p - W);
+}
+
+// the border pixels, one lane each: top row, bottom row, left column, right column
+__global__ void __launch_bounds__(256)
+k_holes_touch(const int32_t *__restrict__ segm, const int32_t *__restrict__ parent, int H, int W, uint8_t *touches)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * W + 2 * H) return;
+    int y, x;
+    if (t < W) {
+        y = 0, x = t;
+    } else if (t < 2 * W) {
+        y = H - 1, x = t - W;
+    } else if (t < 2 * W + H) {
+        y = t - 2 * W, x = 0;
+    } else {
+        y = t - 2 * W - H, x = W - 1;
+    }
+    const int p = y * W + x;
+    if (segm[p] <= 0) touches[uf_find(parent, p)] = 1;
+}
+
+__global__ void __launch_bounds__(256)
+k_holes_write(const int32_t *__restrict__ segm, const int32_t *__restrict__ parent, const uint8_t *__restrict__ touches, int n,
+              uint8_t *__restrict__ seg_bg, uint8_t *__restrict__ seg_fg)
+{
+    const unsigned int p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= (unsigned int)n) return;
+    const int l = segm[p];
+    seg_bg[p] = l <= 0 ? touches[uf_find(parent, (int)p)] : (uint8_t)0;
+    seg_fg[p] = l == 1;
+}
+
+// ---- disc erosion / dilation ------------------------------------------------------------------------------------------------
+// A workgroup of 256 lanes makes a 64 x 64 tile of the output.  It reads the tile with a halo of r pixels into LDS as "is this a
+// pixel the search looks for" (a 0 of the image for the erosion, a 1 for the dilation; outside the image: no), then
+//   * run[ty][c] = distance along column c from tile row ty to the nearest such pixel, capped at r + 1: a lane takes a column and 16
+//     rows and walks down and up once, r + 16 steps each way, carrying the run length;
+//   * a pixel has one within the disc when run[ty][c + k]^2 + k^2 <= r^2 for some |k| <= r: at most 2 r + 1 bytes of LDS, leaving at
+//     the first hit.
+// LDS: (64 + 2 r)^2 + 64 (64 + 2 r) bytes: 14 852 at r = 15, 49 152 at r = 64 (DESIGN.md section 4 on the tile and the occupancy).
+constexpr int MO_TILE = 64, MO_SEG = 16;
+
+template <int TARGET>
+__global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out)
+{
+    extern __shared__ uint8_t morph_lds[];
+    const int LW = MO_TILE + 2 * r;
+    uint8_t *hit = morph_lds;                          // [LW][LW]
+    uint8_t *run = morph_lds + LW * LW;                // [MO_TILE][LW]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * MO_TILE - r, y0 = blockIdx.y * MO_TILE - r;
+    for (int ly = wave; ly < LW; ly += 4) {
+        const int y = y0 + ly;
+        const bool iny = y >= 0 && y < H;
+        for (int lx = lane; lx < LW; lx += 64) {
+            const int x = x0 + lx;
+            uint8_t v = 0;
+            if (iny && x >= 0 && x < W) v = (in[(size_t)y * W + x] != 0) == (TARGET != 0);
+            hit[ly * LW + lx] = v;
+        }
+    }
+    __syncthreads();
+    const int cap = r + 1;
+    for (int i = threadIdx.x; i < LW * (MO_TILE / MO_SEG); i += 256) {
+        const int seg = i / LW, c = i - seg * LW;
+        const int t0 = seg * MO_SEG;                   // first tile row of the lane; LDS row of tile row t is t + r
+        int d = cap;
+        for (int ly = t0; ly < t0 + r + MO_SEG; ++ly) {
+            d = hit[ly * LW + c] ? 0 : min(d + 1, cap);
+            if (ly >= t0 + r) run[(ly - r) * LW + c] = (uint8_t)d;
+        }
+        d = cap;
+        for (int ly = t0 + MO_SEG - 1 + 2 * r; ly >= t0 + r; --ly) {
+            d = hit[ly * LW + c] ? 0 : min(d + 1, cap);
+            if (ly <= t0 + MO_SEG - 1 + r) run[(ly - r) * LW + c] = (uint8_t)min(d, (int)run[(ly - r) * LW + c]);
+        }
+    }
+    __syncthreads();
+    const int x = blockIdx.x * MO_TILE + lane;
+    if (x >= W) return;
+    const int r2 = r * r;
+    for (int ty = wave; ty < MO_TILE; ty += 4) {
+        const int y = blockIdx.y * MO_TILE + ty;
+        if (y >= H) break;
+        const uint8_t *line = run + ty * LW + lane + r;
+        bool found = false;
+        for (int k = 0; k <= r && !found; ++k) {
+            const int lim = r2 - k * k, a = line[-k], b = line[k];
+            found = a * a <= lim || b * b <= lim;
+        }
+        out[(size_t)y * W + x] = TARGET ? found : !found;
+    }
+}
+
+// ---- rays of all centres on both masks ----------------------------------------------------------------------------------------
+// blockIdx.y = 0: seg_bg with edge 'up', 1: seg_fg with edge 'down'; the walk is k_ray_features_binary2d's (natives.hip), the same
+// float32 / float64 operations in the same order.  One wave per (position, mask), one lane per angle.
+__global__ void __launch_bounds__(64)
+k_boundary_rays(const uint8_t *__restrict__ seg_bg, const uint8_t *__restrict__ seg_fg, int H, int W,
+                const int32_t *__restrict__ positions, int P, const float *__restrict__ grad, int A, float *__restrict__ rays_bg,
+                float *__restrict__ rays_fg)
+{
+    const int p = blockIdx.x;
+    const int edge = blockIdx.y == 0 ? 1 : -1;
+    const uint8_t *seg = blockIdx.y == 0 ? seg_bg : seg_fg;
+    float *out = blockIdx.y == 0 ? rays_bg : rays_fg;
+    if (p >= P || !out) return;
+    const int py = positions[2 * p], px = positions[2 * p + 1];
+    const bool inside = py >= 0 && py < H && px >= 0 && px < W;
+    const uint8_t start = inside ? seg[(size_t)py * W + px] : 0;
+    const int diag = (int)sqrt((double)W * W + (double)H * H);
+    for (int a = threadIdx.x; a < A; a += blockDim.x) {
+        float res = -1.f;
+        if (start && edge == 1) {
+            res = 0.f;                                       // the position lies on the mask
+        } else if (inside) {
+            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
+            float pos0 = (float)py, pos1 = (float)px;
+            uint8_t last = start;
+            for (int it = 0; it < diag; ++it) {
+                pos0 += g0;
+                pos1 += g1;
+                const double r0 = round((double)pos0), r1 = round((double)pos1);
+                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
+                const uint8_t actual = seg[(size_t)(int)r0 * W + (int)r1];
+                if ((edge == 1 && actual) || (edge == -1 && last && !actual)) {
+                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
+                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
+                    break;
+                }
+                last = actual;
+            }
+        }
+        out[(size_t)p * A + a] = res;
+    }
+}
+
+int morph_size_ok(int H, int W)
+{
+    if (H > 65535 || (size_t)H * (size_t)W >= ((size_t)1 << 31)) {
+        set_error("morphology: more than 65535 rows or 2^31 pixels");
+        return 0;
+    }
+    return 1;
+}
+
+int launch_fill_holes_split(const int32_t *segm, int H, int W, int32_t *parent, uint8_t *touches, uint8_t *seg_bg, uint8_t *seg_fg,
+                            hipStream_t st)
+{
+    const int n = H * W;
+    const dim3 rows(cdiv(W, 256), H);
+    HIP_TRY(hipMemsetAsync(touches, 0, (size_t)n, st));
+    hipLaunchKernelGGL(k_holes_init, rows, 256, 0, st, segm, parent, W);
+    hipLaunchKernelGGL(k_holes_merge, rows, 256, 0, st, segm, parent, W);
+    hipLaunchKernelGGL(k_holes_touch, cdiv(2L * W + 2L * H, 256), 256, 0, st, segm, parent, H, W, touches);
+    hipLaunchKernelGGL(k_holes_write, cdiv(n, 256), 256, 0, st, segm, parent, touches, n, seg_bg, seg_fg);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_disc_morph(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, hipStream_t st)
+{
+    if (r < 1 || r > MORPH_MAX_RADIUS) {
+        set_error("disc morphology: the radius must lie in [1, IMSEGM_MORPH_MAX_RADIUS]");
+        return -1;
+    }
+    const int LW = MO_TILE + 2 * r;
+    const size_t lds = (size_t)LW * LW + (size_t)MO_TILE * LW;
+    const dim3 grid(cdiv(W, MO_TILE), cdiv(H, MO_TILE));
+    if (dilate)
+        hipLaunchKernelGGL(k_disc_morph<1>, grid, 256, lds, st, in, H, W, r, out);
+    else
+        hipLaunchKernelGGL(k_disc_morph<0>, grid, 256, lds, st, in, H, W, r, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_boundary_rays(const uint8_t *seg_bg, const uint8_t *seg_fg, int H, int W, const int32_t *positions, int P, const float *grad,
+                         int A, float *rays_bg, float *rays_fg, hipStream_t st)
+{
+    if (P > 0 && (rays_bg || rays_fg))
+        hipLaunchKernelGGL(k_boundary_rays, dim3(P, 2), 64, 0, st, seg_bg, seg_fg, H, W, positions, P, grad, A, rays_bg, rays_fg);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace imsegm

@@ -1072,6 +1072,33 @@ def compute_ray_features_positions(segm, list_positions, angle_step=5., border_l
     return rays, pos_shift, feature_names
 
 
+def reduce_close_points(points, dist_thr):
+    """ drop points until no two are closer than ``dist_thr`` (reference ``descriptors.py:2005-2041``): of the closest pair (the first
+    in row-major order of the distance matrix) the point with the larger index goes.  numpy on the host: at most a few dozen points
+
+    >>> reduce_close_points(np.array([range(10), range(10)]).T, 2).tolist()
+    [[0, 0], [2, 2], [4, 4], [6, 6], [8, 8]]
+    >>> reduce_close_points(np.array([[0, 0], [1, 1], [0, 2]]), 2).tolist()
+    [[0, 0], [0, 2]]
+    >>> reduce_close_points(np.ones((10, 2)), 2).tolist()
+    [[1.0, 1.0]]
+
+    :param ndarray points: N x 2, more than 2, in their order along the contour
+    :param float dist_thr: the smallest distance that may remain
+    :return ndarray: the points kept
+    """
+    from scipy.spatial.distance import cdist
+    if len(points) <= 2:
+        raise ValueError('too few point to be reduced')
+    dist = cdist(points, points, metric='euclidean')
+    np.fill_diagonal(dist, np.inf)
+    while dist.size and np.min(dist) < dist_thr:
+        worse = max(np.unravel_index(dist.argmin(), dist.shape))
+        points = np.delete(points, worse, axis=0)
+        dist = np.delete(np.delete(dist, worse, axis=0), worse, axis=1)
+    return points
+
+
 def interpolate_ray_dist(ray_dists, order='spline'):
     """the ray distances with those that met no edge (``-1``) filled in from the others (reference ``descriptors.py:1898-1962``; its
     examples are in tests/doctests/region_growing.py).  On the host: it is reached only when a ray leaves the image.

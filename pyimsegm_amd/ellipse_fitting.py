@@ -10,6 +10,10 @@
   of every (trial, point) pair and the reference's update rule per egg.  ``on='host'`` computes the same three definitions in
   numpy (:func:`score_trials_host`) -- the CPU statement the kernels are tested against.
 * The winner is re-estimated from the kept inliers on the host, as the reference does.
+* The step in front of the RANSAC -- ``split_segm_background_foreground`` and ``prepare_boundary_points_ray_join`` / ``_edge`` /
+  ``_mean`` / ``_dist`` -- smooths the class map and casts the rays of all centres on the device (``imsegm_boundary_rays``,
+  csrc/morphology.hip); what follows the rays (at most 72 values per centre) is the reference's numpy in float64.  ``on='host'`` is
+  the scipy / numpy statement of the same definitions (:func:`split_host`, :func:`ray_walk_host`).
 
 Definitions ("Ellipse RANSAC"): the criterion keeps the reference's ``weights[labels_in]`` -- the weight is
 looked up by the CLASS LABEL of a centre inside the ellipse, not by the centre; the residual is the distance to the closest
@@ -21,6 +25,11 @@ import numpy as np
 
 from pyimsegm_amd import _hip
 
+#: what the reference's rays are clamped to from below (its spelling)
+MIN_ELLIPSE_DAIM = 25.
+#: radius of the disc the background / the foreground mask is opened with
+STRUC_ELEM_BG = 15
+STRUC_ELEM_FG = 5
 #: cap of the closest-point iteration (``ER_ITERATIONS`` of csrc/ellipse.hip)
 DISTANCE_ITERATIONS = 128
 _CONSTRAINT_INV = np.linalg.inv(np.array([[0., 0., 2.], [0., -1., 0.], [2., 0., 0.]]))
@@ -392,3 +401,319 @@ def get_slic_points_labels(segm, img=None, slic_size=20, slic_regul=0.1):
     slic_centers = np.array(superpixel_centers(slic)).astype(int)
     labels = segm[slic_centers[:, 0], slic_centers[:, 1]]
     return slic, slic_centers, labels
+
+
+# ------------------------------------------------------------------------------------------------
+# from a class map with centre candidates to the boundary points of every centre (reference ellipse_fitting.py:352-597)
+# ------------------------------------------------------------------------------------------------
+
+
+def _points_place(on):
+    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_BOUNDARY_POINTS_ON, unset: 'device' when a
+    device is present"""
+    if on is None:
+        on = os.environ.get('IMSEGM_BOUNDARY_POINTS_ON') or None
+    if on is None:
+        try:
+            on = 'device' if _hip.device_count() > 0 else 'host'
+        except _hip.HipUnavailableError:
+            on = 'host'
+    if on not in ('host', 'device'):
+        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
+    return on
+
+
+def _integer_radii(*radii):
+    return all(float(r) == int(r) for r in radii)
+
+
+def fill_holes_host(mask):
+    """``scipy.ndimage.binary_fill_holes(mask)`` as the device states it: the mask plus every 4-connected component of its zero
+    pixels that has no pixel on the image border"""
+    from scipy import ndimage
+    mask = np.asarray(mask, dtype=bool)
+    zeros, _ = ndimage.label(~mask)                                # the default structure: 4-connected
+    border = np.concatenate([zeros[0], zeros[-1], zeros[:, 0], zeros[:, -1]])
+    return mask | ((zeros > 0) & ~np.isin(zeros, border[border > 0]))
+
+
+def opening_host(mask, radius):
+    """``skimage.morphology.opening(mask, disk(radius))`` for an integer radius (scikit-image 0.18.3: scipy's grey erosion and
+    dilation with boundary mode 'reflect') as two thresholds of exact distances inside the image: a pixel survives the erosion
+    when its squared distance to the nearest 0 is > radius^2 (a mask without a 0 stays as it is), and is set by the dilation when
+    its squared distance to the nearest survivor is <= radius^2.  A mirrored pixel is never nearer than its original, so the
+    reflected border adds nothing.  (``distance_transform_edt`` returns the correctly rounded root of an integer, and
+    sqrt(n) > radius exactly when n > radius^2.)"""
+    from scipy import ndimage
+    mask = np.asarray(mask, dtype=bool)
+    radius = int(radius)
+    if not mask.all():
+        mask = ndimage.distance_transform_edt(mask) > radius
+    if not mask.any():
+        return mask
+    return ndimage.distance_transform_edt(~mask) <= radius
+
+
+def split_host(seg, sel_bg=STRUC_ELEM_BG, sel_fg=STRUC_ELEM_FG, with_fg=True):
+    """the scipy / numpy statement of ``imsegm_split_background_foreground`` for integer radii: (seg_bg, seg_fg) bool"""
+    seg = np.asarray(seg)
+    seg_bg = ~fill_holes_host(seg > 0)
+    if sel_bg > 0:
+        seg_bg = opening_host(seg_bg, sel_bg)
+    seg_fg = None
+    if with_fg:
+        seg_fg = seg == 1
+        if sel_fg > 0:
+            seg_fg = opening_host(seg_fg, sel_fg)
+    return seg_bg, seg_fg
+
+
+def ray_walk_host(mask, positions, directions, edge):
+    """``computeRayFeaturesBinary2d(mask, position, edge)`` in numpy for all positions and angles: float32 [P, A]; float32 positions
+    advanced by the float32 ``directions`` [A, 2], the walk of ``k_boundary_rays`` / ``k_ray_features_binary2d`` operation by
+    operation.  ``edge`` is 1 ('up': the first mask pixel) or -1 ('down': the first pixel off the mask after one on it)."""
+    mask = np.asarray(mask, dtype=bool)
+    height, width = mask.shape
+    directions = np.asarray(directions, dtype=np.float32).reshape(-1, 2)
+    positions = np.asarray(positions, dtype=np.int64).reshape(-1, 2)
+    rays = np.full((len(positions), len(directions)), -1, dtype=np.float32)
+    steps = int(np.sqrt(float(width) * width + float(height) * height))
+    for p, (py, px) in enumerate(positions):
+        if not (0 <= py < height and 0 <= px < width):
+            continue
+        if edge == 1 and mask[py, px]:
+            rays[p] = 0
+            continue
+        pos0 = np.full(len(directions), py, dtype=np.float32)
+        pos1 = np.full(len(directions), px, dtype=np.float32)
+        last = np.full(len(directions), mask[py, px], dtype=bool)
+        active = np.ones(len(directions), dtype=bool)
+        for _ in range(steps):
+            if not active.any():
+                break
+            pos0 = pos0 + directions[:, 0]
+            pos1 = pos1 + directions[:, 1]
+            r0, r1 = np.floor(pos0.astype(np.float64) + 0.5), np.floor(pos1.astype(np.float64) + 0.5)
+            active &= ~((pos0 < 0) | (r0 >= height) | (pos1 < 0) | (r1 >= width))
+            idx = np.nonzero(active)[0]
+            actual = mask[r0[idx].astype(int), r1[idx].astype(int)]
+            hit = actual if edge == 1 else last[idx] & ~actual
+            dx, dy = pos0[idx[hit]] - np.float32(py), pos1[idx[hit]] - np.float32(px)
+            rays[p, idx[hit]] = np.sqrt(((dx * dx) + (dy * dy)).astype(np.float64)).astype(np.float32)
+            last[idx] = actual
+            active[idx[hit]] = False
+    return rays
+
+
+def boundary_rays_host(seg, sel_bg, sel_fg, positions, directions, with_fg=True):
+    """the scipy / numpy statement of ``imsegm_boundary_rays`` (same arguments and results as ``_hip.boundary_rays``)"""
+    seg_bg, seg_fg = split_host(seg, sel_bg, sel_fg, with_fg)
+    return ray_walk_host(seg_bg, positions, directions, 1), (ray_walk_host(seg_fg, positions, directions, -1) if with_fg else None)
+
+
+def _on_device(place, *radii):
+    """the device takes the call: asked for (or present) and every radius within ``IMSEGM_MORPH_MAX_RADIUS``"""
+    return place == 'device' and max(radii) <= _hip.MORPH_MAX_RADIUS
+
+
+def _split_skimage(seg, sel_bg, sel_fg):
+    """the reference's statement itself, for radii that are no integers (``disk(1.5)`` is an even-sided footprint that
+    scikit-image shifts by its own rules)"""
+    from scipy import ndimage
+    from skimage import morphology
+    seg_bg = 1 - ndimage.binary_fill_holes(seg > 0)
+    if sel_bg > 0:
+        seg_bg = morphology.opening(seg_bg, morphology.disk(sel_bg))
+    seg_fg = seg == 1
+    if sel_fg > 0:
+        seg_fg = morphology.opening(seg_fg, morphology.disk(sel_fg))
+    return seg_bg, seg_fg
+
+
+def split_segm_background_foreground(seg, sel_bg=STRUC_ELEM_BG, sel_fg=STRUC_ELEM_FG, on=None):
+    """ smooth a class map into the mask of the background around the filled objects and the mask of class 1 (reference
+    ``ellipse_fitting.py:400-443``): ``seg_bg = 1 - binary_fill_holes(seg > 0)`` and ``seg_fg = (seg == 1)``, each opened with
+    ``disk(sel)`` when ``sel > 0``.
+
+    Integer radii up to ``IMSEGM_MORPH_MAX_RADIUS`` run on the device (``imsegm_split_background_foreground``: one union-find
+    labelling of the zero pixels, tiled disc erosion and dilation in integers); ``on='host'`` (or the environment variable
+    ``IMSEGM_BOUNDARY_POINTS_ON=host``, no device, a larger radius) runs the scipy / numpy statement of the same definitions,
+    :func:`split_host`.  A radius that is no integer (the reference's docstring uses ``sel_bg=1.5``) goes to scikit-image, which is
+    imported in that branch only.
+
+    :param ndarray seg: class map H x W
+    :param int|float sel_bg: radius of the disc the background is opened with
+    :param int|float sel_fg: radius of the disc class 1 is opened with
+    :return tuple(ndarray,ndarray): seg_bg (int), seg_fg (bool)
+    """
+    seg = np.asarray(seg)
+    if seg.ndim != 2:
+        raise ValueError('the class map has to be 2-D, not %r' % (seg.shape, ))
+    if not _integer_radii(sel_bg, sel_fg):
+        return _split_skimage(seg, sel_bg, sel_fg)
+    if seg.size and _on_device(_points_place(on), sel_bg, sel_fg):
+        seg_bg, seg_fg = _hip.split_background_foreground(_class_map_i32(seg), int(sel_bg), int(sel_fg))
+    else:
+        seg_bg, seg_fg = split_host(seg, int(sel_bg), int(sel_fg))
+    return seg_bg.astype(int), seg_fg.astype(bool)
+
+
+def _class_map_i32(seg):
+    """the class map as the device reads it: what matters is ``seg > 0`` and ``seg == 1``, which a map that int32 does not hold
+    (or a float map) keeps as 0 / 1 / 2"""
+    info = np.iinfo(np.int32)
+    if seg.dtype.kind in 'iub' and (seg.dtype.itemsize <= 2 or seg.dtype == np.int32 or (info.min <= seg.min() and seg.max() <= info.max)):
+        return seg
+    return np.where(seg == 1, 1, np.where(seg > 0, 2, 0)).astype(np.int32)
+
+
+def reconstruct_ray_features_2d(position, ray_features, shift=0):
+    """ the end points of the rays of ``position`` (reference ``descriptors.py:1965-2002``): ray a of A points at the angle
+    ``pi / 2 - 2 pi a / A - deg2rad(shift)``; rays that are negative or infinite are left out.  numpy on the host, float64.  It
+    lives here, where the reference's ``ellipse_fitting`` imports it to, and not in ``pyimsegm_amd.descriptors``: that name of
+    ``imsegm.descriptors`` is the overlay's pinned example of a name only an installed reference answers (imsegm/__init__.py).
+
+    >>> reconstruct_ray_features_2d((10., 10), np.array([1] * 4)).round(12).tolist()
+    [[10.0, 11.0], [11.0, 10.0], [10.0, 9.0], [9.0, 10.0]]
+    >>> reconstruct_ray_features_2d((10., 10), np.array([-1, 0, 1, np.inf])).round(12).tolist()
+    [[10.0, 10.0], [10.0, 9.0]]
+
+    :param tuple(float,float) position: (row, col)
+    :param ndarray ray_features: one distance per angle, more than 2
+    :param float shift: rotation in degrees
+    :return ndarray: points N x 2
+    """
+    if len(position) != 2:
+        raise ValueError('positions has to have 2 coordinates')
+    if len(ray_features) <= 2:
+        raise ValueError('required at least 2 features')
+    ray_features = np.asarray(ray_features)
+    angles = np.linspace(0, 2 * np.pi, len(ray_features), endpoint=False)
+    angles = (np.pi / 2.) - angles - np.deg2rad(shift)
+    mask = np.logical_and(ray_features >= 0, ~np.isinf(ray_features))
+    angles, ray_features = angles[mask], ray_features[mask]
+    dx = np.cos(angles) * ray_features
+    dy = np.sin(angles) * ray_features
+    return np.tile(position, (len(ray_features), 1)) + np.array([dx, dy]).T
+
+
+def _centre_rays(seg, centers, sel_bg, sel_fg, with_fg, on, angle_step=5.):
+    """float32 rays [P, A] of all centres on seg_bg (edge 'up') and, ``with_fg``, on seg_fg (edge 'down')"""
+    from pyimsegm_amd.descriptors import _ray_directions
+    seg = np.asarray(seg)
+    if seg.ndim != 2:
+        raise ValueError('the class map has to be 2-D, not %r' % (seg.shape, ))
+    for center in centers:
+        if len(center) != 2:
+            raise ValueError('Segmentation dim of %r and position (%i) does not match' % (seg.ndim, len(center)))
+    positions = np.array([[int(v) for v in center] for center in centers], dtype=np.int64).reshape(-1, 2)
+    directions = _ray_directions(angle_step)
+    place = _points_place(on)
+    if not _integer_radii(sel_bg, sel_fg):
+        seg_bg, seg_fg = _split_skimage(seg, sel_bg, sel_fg)
+        if place == 'device':
+            return (_hip.ray_features_binary2d(seg_bg != 0, positions, directions, 1),
+                    _hip.ray_features_binary2d(seg_fg != 0, positions, directions, -1) if with_fg else None)
+        return ray_walk_host(seg_bg, positions, directions, 1), (ray_walk_host(seg_fg, positions, directions, -1) if with_fg else None)
+    info = np.iinfo(np.int32)
+    if seg.size and len(positions) and _on_device(place, sel_bg, sel_fg):
+        return _hip.boundary_rays(_class_map_i32(seg), int(sel_bg), int(sel_fg), np.clip(positions, info.min, info.max), directions,
+                                  with_fg)
+    return boundary_rays_host(seg, int(sel_bg), int(sel_fg), positions, directions, with_fg)
+
+
+def prepare_boundary_points_ray_join(seg, centers, close_points=5, min_diam=MIN_ELLIPSE_DAIM, sel_bg=STRUC_ELEM_BG,
+                                     sel_fg=STRUC_ELEM_FG, on=None):
+    """ per centre the ends of its rays to the smoothed background and of its rays to the end of class 1, one list after the other
+    (reference ``ellipse_fitting.py:352-397``): rays below ``min_diam`` (those that met no edge too) are set to it, each list is
+    thinned with ``reduce_close_points``.  Masks and rays of all centres: :func:`split_segm_background_foreground` and one launch on
+    the device (``imsegm_boundary_rays``), or the host statement with ``on='host'``; radii that are no integers import scikit-image.
+
+    :param ndarray seg: class map H x W
+    :param list(tuple(int,int)) centers: (row, col)
+    :param float close_points: smallest distance between two points kept
+    :param float min_diam: smallest ray
+    :param int sel_bg: radius of the disc the background is opened with
+    :param int sel_fg: radius of the disc class 1 is opened with
+    :return list(ndarray): points per centre
+    """
+    from pyimsegm_amd.descriptors import reduce_close_points
+    rays_bg, rays_fg = _centre_rays(seg, centers, sel_bg, sel_fg, True, on)
+    points_centers = []
+    for center, ray_bg, ray_fc in zip(centers, rays_bg, rays_fg):
+        both = []
+        for ray in (ray_bg, ray_fc):
+            ray = np.array(ray)
+            ray[ray < min_diam] = min_diam
+            both.append(reduce_close_points(reconstruct_ray_features_2d(center, ray), close_points))
+        points_centers.append(np.vstack(both))
+    return points_centers
+
+
+def _closest_rays(ray_bg, ray_fc, min_diam):
+    """both rays in float64 with those that met no edge at infinity and the others clamped from below (:485-487)"""
+    rays = np.array([ray_bg, ray_fc], dtype=float)
+    rays[rays < 0] = np.inf
+    rays[rays < min_diam] = min_diam
+    return rays
+
+
+def prepare_boundary_points_ray_edge(seg, centers, close_points=5, min_diam=MIN_ELLIPSE_DAIM, sel_bg=STRUC_ELEM_BG,
+                                     sel_fg=STRUC_ELEM_FG, on=None):
+    """ per centre the ends of the shorter of its two rays per angle -- to the smoothed background, to the end of class 1 --
+    (reference ``ellipse_fitting.py:446-494``); arguments, places and the scikit-image branch as
+    :func:`prepare_boundary_points_ray_join`
+
+    :return list(ndarray): points per centre
+    """
+    from pyimsegm_amd.descriptors import reduce_close_points
+    rays_bg, rays_fg = _centre_rays(seg, centers, sel_bg, sel_fg, True, on)
+    points_centers = []
+    for center, ray_bg, ray_fc in zip(centers, rays_bg, rays_fg):
+        ray_close = np.min(_closest_rays(ray_bg, ray_fc, min_diam), axis=0)
+        points_centers.append(reduce_close_points(reconstruct_ray_features_2d(center, ray_close), close_points))
+    return points_centers
+
+
+def prepare_boundary_points_ray_mean(seg, centers, close_points=5, min_diam=MIN_ELLIPSE_DAIM, sel_bg=STRUC_ELEM_BG,
+                                     sel_fg=STRUC_ELEM_FG, on=None):
+    """ per centre the ends of the mean of its two rays per angle, of the one that met an edge where only one did (reference
+    ``ellipse_fitting.py:497-549``); arguments, places and the scikit-image branch as :func:`prepare_boundary_points_ray_join`
+
+    :return list(ndarray): points per centre
+    """
+    from pyimsegm_amd.descriptors import reduce_close_points
+    rays_bg, rays_fg = _centre_rays(seg, centers, sel_bg, sel_fg, True, on)
+    points_centers = []
+    for center, ray_bg, ray_fc in zip(centers, rays_bg, rays_fg):
+        rays = _closest_rays(ray_bg, ray_fc, min_diam)
+        ray_min, ray_mean = np.min(rays, axis=0), np.mean(rays, axis=0)
+        ray_mean[np.isinf(ray_mean)] = ray_min[np.isinf(ray_mean)]
+        points_centers.append(reduce_close_points(reconstruct_ray_features_2d(center, ray_mean), close_points))
+    return points_centers
+
+
+def prepare_boundary_points_ray_dist(seg, centers, close_points=1, sel_bg=STRUC_ELEM_BG, sel_fg=STRUC_ELEM_FG, on=None):
+    """ the ends of the rays of all centres to the smoothed background, each given to the centre nearest to it (reference
+    ``ellipse_fitting.py:552-597``, with its quirks: coordinates in (-1e-3, 0) become 0, and the list ends at the last centre that
+    got a point).  The foreground mask is never opened (``imsegm_boundary_rays`` with a NULL foreground output); places and the
+    scikit-image branch as :func:`prepare_boundary_points_ray_join`.  These lists are what :func:`ransac_segm_batch` takes.
+
+    :param ndarray seg: class map H x W
+    :param list(tuple(int,int)) centers: (row, col)
+    :param float close_points: smallest distance between two points kept
+    :param int sel_bg: radius of the disc the background is opened with
+    :param int sel_fg: unused, as in the reference
+    :return list(ndarray): points per centre
+    """
+    from scipy.spatial.distance import cdist
+
+    from pyimsegm_amd.descriptors import reduce_close_points
+    rays_bg, _ = _centre_rays(seg, centers, sel_bg, 0, False, on)
+    points = []
+    for center, ray in zip(centers, rays_bg):
+        points += reduce_close_points(reconstruct_ray_features_2d(center, np.array(ray), 0), close_points).tolist()
+    points = np.array(points)
+    points[(points < 0) & (points > -1e-3)] = 0.
+    close_center = np.argmin(cdist(points, centers, metric='euclidean'), axis=1)
+    return [points[close_center == i] for i in range(close_center.max() + 1)]
