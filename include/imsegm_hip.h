@@ -536,6 +536,41 @@ IMSEGM_API int imsegm_labels_overlap(imsegm_ctx *ctx, const int32_t *seg1, const
 IMSEGM_API int imsegm_cut_general_graph(imsegm_ctx *ctx, const int32_t *edges, int n_edges, const double *edge_weights,
                              const double *unary_cost, int n_sites, int n_labels, const double *pairwise_cost,
                              int n_iter, int32_t *labels_out, int64_t *energy_out);
+/* imsegm_cut_general_graph with pyGCO's scaling maximum of |edge_weights| stated by the caller: weight_max >= 0 enters the
+ * maximum next to the weights of the edges handed over, weight_max < 0 is imsegm_cut_general_graph itself.  For callers that drop
+ * edges joining a site with itself (imsegm/region_growing.py:117-122 sets the edges at a seed to (0, 0)): such an edge adds nothing
+ * to any labelling, but pyGCO takes its maximum over all weights before GCO sees an edge. */
+IMSEGM_API int imsegm_cut_general_graph_scaled(imsegm_ctx *ctx, const int32_t *edges, int n_edges, const double *edge_weights,
+                                               const double *unary_cost, int n_sites, int n_labels, const double *pairwise_cost,
+                                               double weight_max, int n_iter, int32_t *labels_out, int64_t *energy_out);
+/* (tests) The arcs the grid entries build on the device for a height x width grid: edges E x 2, arc_start height * width + 1,
+ * arc_to 2 E, arc_rev 2 E, edge_arc E x 2, E = (height - 1) * width + height * (width - 1); the arrays the host loop of
+ * imsegm_cut_general_graph builds for pyGCO's edge list of that grid. */
+IMSEGM_API int imsegm_debug_grid_arcs(imsegm_ctx *ctx, int height, int width, int32_t *edges_out, int32_t *arc_start_out,
+                                      int32_t *arc_to_out, int32_t *arc_rev_out, int32_t *edge_arc_out);
+/* Replaces gco.cut_grid_graph(unary_cost, pairwise_cost, cost_v, cost_h, n_iter, algorithm='expansion') as called at
+ * imsegm/region_growing.py:246-248: the 4-connected height x width grid, unary height x width x n_labels, cost_v (height - 1) x
+ * width, cost_h height x (width - 1), pairwise n_labels x n_labels symmetric -- gco's own float arguments.  The float costs go up
+ * as they are; pyGCO's down-weight factor, its truncation to integers and the arcs of the grid (pyGCO's edge order: all vertical
+ * edges row-major, then the horizontal ones) are computed on the device.  Labels and energy are those of imsegm_cut_general_graph
+ * on the same graph.  Limits as there, and height * width <= 2^29. */
+IMSEGM_API int imsegm_cut_grid_graph(imsegm_ctx *ctx, const double *unary, int height, int width, int n_labels,
+                                     const double *pairwise, const double *cost_v, const double *cost_h, int n_iter,
+                                     int32_t *labels_out, int64_t *energy_out);
+/* Replaces the numpy in front of the cut and the cut of imsegm/region_growing.py:202-249 object_segmentation_graphcut_pixels:
+ * the unary cost of class l at integer distance d from centre i is a_fg[l] - coef_shape * b[d] (label i + 1) and a_bg[l] -
+ * coef_shape * s_bg[l] (label 0) when coef_shape > 0, a_fg[l] / a_bg[l] otherwise; 0 at the seeds (seed_size > 0: the disc of that
+ * radius around the seed where segm > 0, else the seed pixel).  segm: height x width int32 with -n_table_labels <= segm <
+ * n_table_labels (a negative class counts from the end, as numpy indexes); centres: n_centres x 4 int32 = row, column the
+ * distance is taken from, row, column of the seed; b: n_dist entries, n_dist above every integer distance that occurs.  Edge
+ * weights are 1, pairwise = (1 - eye) * gc_regul.  Only segm, the centres and the tables go up, only the labels come down.
+ * unary_int_out (height * width * (n_centres + 1) int32) and dwf_out: pyGCO's integers and down-weight factor, or NULL (tests).
+ * Limits: n_centres <= 63, tables of (3 n_table_labels + n_dist) * 8 + 16 n_centres <= 61440 bytes, height * width <= 2^29. */
+IMSEGM_API int imsegm_object_cut_pixels(imsegm_ctx *ctx, const int32_t *segm, int height, int width, const int32_t *centres,
+                                        int n_centres, const double *a_bg, const double *a_fg, const double *s_bg,
+                                        int n_table_labels, const double *b, int n_dist, double coef_shape, double gc_regul,
+                                        int seed_size, int n_iter, int32_t *labels_out, int64_t *energy_out,
+                                        int32_t *unary_int_out, double *dwf_out);
 
 /* ---------------------------------------------------------------------------------------------
  * the class model's fit (imsegm/graph_cuts.py:73-163 estim_class_model: scikit-learn's GaussianMixture.fit on the host in the

@@ -167,6 +167,12 @@ _SIGNATURES = {
                                                _vp]),
     'imsegm_cut_general_graph': (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp,
                                            C.POINTER(C.c_int64)]),
+    'imsegm_cut_general_graph_scaled': (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_double, C.c_int, _vp,
+                                                  C.POINTER(C.c_int64)]),
+    'imsegm_debug_grid_arcs': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'imsegm_cut_grid_graph': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_int64)]),
+    'imsegm_object_cut_pixels': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_double,
+                                           C.c_double, C.c_int, C.c_int, _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_double)]),
     'imsegm_kmeans_lloyd': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'imsegm_mixture_em': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
@@ -1522,23 +1528,92 @@ def cut_general_graph(edges, edge_weights, unary_cost, pairwise_cost, n_iter=-1,
     return (labels, energy.value) if return_energy else labels
 
 
-def cut_grid_graph(unary_cost, pairwise_cost, cost_v, cost_h, n_iter=-1, algorithm='expansion', ctx=None):
+def cut_general_graph_scaled(edges, edge_weights, unary_cost, pairwise_cost, weight_max, n_iter=-1, return_energy=False, ctx=None):
+    """:func:`cut_general_graph` whose scaling maximum of ``|edge_weights|`` also covers ``weight_max``: for a caller that has
+    dropped edges joining a site with itself, whose weights pyGCO still sees when it scales (``imsegm_cut_general_graph_scaled``)"""
+    ctx = ctx or default_context()
+    edges = np.ascontiguousarray(np.asarray(edges).reshape(-1, 2), dtype=np.int32)
+    ew = np.ascontiguousarray(edge_weights, dtype=np.float64)
+    un = np.ascontiguousarray(unary_cost, dtype=np.float64)
+    pw = np.ascontiguousarray(pairwise_cost, dtype=np.float64)
+    if un.ndim != 2 or pw.shape != (un.shape[1], un.shape[1]) or len(ew) != len(edges):
+        raise ValueError('shape mismatch among edges %r, weights %r, unary %r, pairwise %r' %
+                         (edges.shape, ew.shape, un.shape, pw.shape))
+    labels = np.empty(un.shape[0], dtype=np.int32)
+    energy = C.c_int64(0)
+    _check(load_library().imsegm_cut_general_graph_scaled(ctx._h, _ptr(edges), len(edges), _ptr(ew), _ptr(un), un.shape[0],
+                                                          un.shape[1], _ptr(pw), float(weight_max), int(n_iter), _ptr(labels),
+                                                          C.byref(energy)))
+    return (labels, energy.value) if return_energy else labels
+
+
+def cut_grid_graph(unary_cost, pairwise_cost, cost_v, cost_h, n_iter=-1, algorithm='expansion', return_energy=False, ctx=None):
     """drop-in for ``gco.cut_grid_graph`` (gco-wrapper, reference ``region_growing.py:248``): 4-connected pixel grid with
-    vertical / horizontal edge costs ``cost_v`` (H-1 x W) / ``cost_h`` (H x W-1); pygco hands GCO the vertical edges followed
-    by the horizontal ones of the general graph, which is what happens here.  Returns int32 labels of the H*W sites."""
-    unary_cost = np.asarray(unary_cost, dtype=np.float64)
+    vertical / horizontal edge costs ``cost_v`` (H-1 x W) / ``cost_h`` (H x W-1).  The float costs go to the device as they are
+    (``imsegm_cut_grid_graph``): pyGCO's conversion to integers and the arcs of the grid -- pygco hands GCO the vertical edges
+    followed by the horizontal ones of the general graph -- are computed there.  Returns int32 labels of the H*W sites.  With a
+    ``ctx`` that is not a :class:`Context` (a stand-in, no device behind it) the graph goes through ``cut_general_graph``."""
+    if algorithm != 'expansion':
+        raise NotImplementedError('only algorithm="expansion" is implemented on the HIP path')
+    unary_cost = np.ascontiguousarray(unary_cost, dtype=np.float64)
     if unary_cost.ndim != 3:
         raise ValueError('unary_cost must be height x width x labels')
     height, width, n_labels = unary_cost.shape
-    cost_v, cost_h = np.asarray(cost_v, dtype=np.float64), np.asarray(cost_h, dtype=np.float64)
+    cost_v, cost_h = np.ascontiguousarray(cost_v, dtype=np.float64), np.ascontiguousarray(cost_h, dtype=np.float64)
     if cost_v.shape != (height - 1, width) or cost_h.shape != (height, width - 1):
         raise ValueError('cost_v / cost_h do not match the grid %d x %d' % (height, width))
-    index = np.arange(height * width, dtype=np.int32).reshape(height, width)
-    edges = np.concatenate([np.stack([index[:-1].ravel(), index[1:].ravel()], axis=1),
-                            np.stack([index[:, :-1].ravel(), index[:, 1:].ravel()], axis=1)], axis=0)
-    weights = np.concatenate([cost_v.ravel(), cost_h.ravel()])
-    return cut_general_graph(edges, weights, unary_cost.reshape(height * width, n_labels), pairwise_cost, n_iter=n_iter,
-                             algorithm=algorithm, ctx=ctx)
+    pw = np.ascontiguousarray(pairwise_cost, dtype=np.float64)
+    if pw.shape != (n_labels, n_labels):
+        raise ValueError('shape mismatch between unary %r and pairwise %r' % (unary_cost.shape, pw.shape))
+    ctx = ctx or default_context()
+    if not isinstance(ctx, Context):
+        # NOT a device path: `ctx` is a stand-in for the context, as the CPU dry runs of the drivers install one together with
+        # their own cut in the place of cut_general_graph -- the general graph pygco builds goes through that function
+        index = np.arange(height * width, dtype=np.int32).reshape(height, width)
+        edges = np.concatenate([np.stack([index[:-1].ravel(), index[1:].ravel()], axis=1),
+                                np.stack([index[:, :-1].ravel(), index[:, 1:].ravel()], axis=1)], axis=0)
+        weights = np.concatenate([cost_v.ravel(), cost_h.ravel()])
+        more = {'return_energy': True} if return_energy else {}
+        return cut_general_graph(edges, weights, unary_cost.reshape(height * width, n_labels), pw, n_iter=n_iter, ctx=ctx, **more)
+    labels = np.empty(height * width, dtype=np.int32)
+    energy = C.c_int64(0)
+    _check(load_library().imsegm_cut_grid_graph(ctx._h, _ptr(unary_cost), height, width, n_labels, _ptr(pw), _ptr(cost_v), _ptr(cost_h),
+                                                int(n_iter), _ptr(labels), C.byref(energy)))
+    return (labels, energy.value) if return_energy else labels
+
+
+def grid_arcs(height, width, ctx=None):
+    """(edges, arc_start, arc_to, arc_rev, edge_arc) of the ``height`` x ``width`` grid as the device builds them for
+    :func:`cut_grid_graph` and :func:`object_cut_pixels` (``imsegm_debug_grid_arcs``; tests)"""
+    ctx = ctx or default_context()
+    n_sites, n_edges = height * width, (height - 1) * width + height * (width - 1)
+    edges, edge_arc = np.zeros((n_edges, 2), dtype=np.int32), np.zeros((n_edges, 2), dtype=np.int32)
+    arc_start, arc_to, arc_rev = np.zeros(n_sites + 1, np.int32), np.zeros(2 * n_edges, np.int32), np.zeros(2 * n_edges, np.int32)
+    _check(load_library().imsegm_debug_grid_arcs(ctx._h, int(height), int(width), _ptr(edges), _ptr(arc_start), _ptr(arc_to),
+                                                 _ptr(arc_rev), _ptr(edge_arc)))
+    return edges, arc_start, arc_to, arc_rev, edge_arc
+
+
+def object_cut_pixels(segm, centres, a_bg, a_fg, s_bg, b, coef_shape, gc_regul, seed_size, n_iter=999, debug=False, ctx=None):
+    """``imsegm_object_cut_pixels``: the unary costs of ``object_segmentation_graphcut_pixels`` from the class map ``segm`` (int32
+    H x W), ``centres`` (int32 n x 4: row, column of the distance; row, column of the seed) and the four tables, pyGCO's integers,
+    the grid and the cut, all on the device.  Returns (labels H x W int32, energy); with ``debug`` also pyGCO's integer unary costs
+    (H x W x (n + 1)) and its down-weight factor."""
+    ctx = ctx or default_context()
+    segm = np.ascontiguousarray(segm, dtype=np.int32)
+    centres = np.ascontiguousarray(centres, dtype=np.int32).reshape(-1, 4)
+    a_bg, a_fg, s_bg, b = (np.ascontiguousarray(t, dtype=np.float64).ravel() for t in (a_bg, a_fg, s_bg, b))
+    if segm.ndim != 2 or not (len(a_bg) == len(a_fg) == len(s_bg)):
+        raise ValueError('segm is height x width; a_bg, a_fg and s_bg have one entry per class')
+    height, width = segm.shape
+    labels = np.empty((height, width), dtype=np.int32)
+    energy, dwf = C.c_int64(0), C.c_double(0.)
+    unary_int = np.empty((height, width, len(centres) + 1), dtype=np.int32) if debug else None
+    _check(load_library().imsegm_object_cut_pixels(ctx._h, _ptr(segm), height, width, _ptr(centres), len(centres), _ptr(a_bg), _ptr(a_fg),
+                                                   _ptr(s_bg), len(a_bg), _ptr(b), len(b), float(coef_shape), float(gc_regul),
+                                                   int(seed_size), int(n_iter), _ptr(labels), C.byref(energy), _ptr(unary_int),
+                                                   C.byref(dwf) if debug else None))
+    return (labels, energy.value, unary_int, dwf.value) if debug else (labels, energy.value)
 
 
 def assume_bg_on_boundary(work, strips, bg_label, ctx=None):

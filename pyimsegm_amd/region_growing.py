@@ -21,7 +21,7 @@ import numpy as np
 
 from pyimsegm_amd import _hip
 from pyimsegm_amd.descriptors import _ray_directions, interpolate_ray_dist, shift_ray_features
-from pyimsegm_amd.graph_cuts import MAX_PAIRWISE_COST, compute_spatial_dist, cut_general_graph
+from pyimsegm_amd.graph_cuts import MAX_PAIRWISE_COST, compute_spatial_dist, cut_general_graph, cut_grid_graph, get_vertexes_edges
 from pyimsegm_amd.labeling import histogram_regions_labels_norm
 
 #: stands in for an infinite cost wherever a cost table or a graph-cut term would hold one
@@ -39,11 +39,11 @@ RG2SP_THRESHOLDS = {
 }
 
 
-def _place(on):
-    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_RG_ON, unset: 'device' when a device is
-    present"""
+def _place(on, variable='IMSEGM_RG_ON'):
+    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_RG_ON (``variable``), unset: 'device' when
+    a device is present"""
     if on is None:
-        on = os.environ.get('IMSEGM_RG_ON') or None
+        on = os.environ.get(variable) or None
     if on is None:
         try:
             on = 'device' if _hip.device_count() > 0 else 'host'
@@ -807,3 +807,270 @@ def region_growing_shape_slic_graphcut(slic, slic_prob_fg, centres, shape_model,
         return labels
     finally:
         growth.state.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# object segmentation by one graph cut, on pixels and on superpixels (reference :42-256)
+# ------------------------------------------------------------------------------------------------
+
+
+#: bytes of tables and centres ``imsegm_object_cut_pixels`` takes (OBJECT_UNARY_LDS_MAX of csrc/object_cut.h)
+OBJECT_TABLES_DEVICE_MAX = 60 * 1024
+
+
+def pygco_integers(unary, weights, pairwise, weight_max=None):
+    """the integer energies pyGCO hands to GCO (gco/pygco.py ``cut_general_graph``): (unary, weights, pairwise, down-weight factor).
+    ``weight_max``: enters the maximum of ``|weights|`` (weights of edges the caller has dropped)."""
+    unary, weights, pairwise = (np.asarray(a, dtype=np.float64) for a in (unary, weights, pairwise))
+    mu = np.max(np.abs(unary)) if unary.size else 0.
+    have_edges = len(weights) > 0 or weight_max is not None
+    mw = np.max(np.abs(weights)) if len(weights) else 0.
+    if weight_max is not None and not weight_max <= mw:
+        mw = weight_max
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        scaled = mw * np.max(pairwise)
+        dwf = (scaled if have_edges and scaled > mu else mu) + 1e-10
+        return (((unary / dwf) * 100000).astype(np.int32), ((weights / dwf) * 1000).astype(np.int32),
+                (pairwise * 100).astype(np.int32), dwf)
+
+
+def _isqrt(values):
+    """floor(sqrt(v)) of non-negative integers, as integers"""
+    root = np.floor(np.sqrt(values)).astype(np.int64)
+    root -= root * root > values
+    root += (root + 1) * (root + 1) <= values
+    return root
+
+
+def _object_tables(labels_fg_prob, coef_shape, shape_mean_std, max_dist):
+    """the few values the unary costs of an object cut take: A_bg[l] = -log(1 - p[l]), A_fg[l] = -log(p[l]), S_bg[l] = log(1 - p[l])
+    and B[d] = log(1 - norm.cdf(d) + 1e-9) for d = 0 .. int(max_dist) (one zero without a shape prior)"""
+    prob_fg = np.array(labels_fg_prob, dtype=np.float64)
+    prob_bg = 1. - prob_fg
+    with np.errstate(divide='ignore', invalid='ignore'):
+        a_bg, a_fg, s_bg = -np.log(prob_bg), -np.log(prob_fg), np.log(prob_bg)
+    if coef_shape > 0:
+        from scipy import stats
+        shape_mean, shape_std = shape_mean_std
+        cdf = stats.norm.cdf(range(int(max_dist + 1)), shape_mean, shape_std)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            table = np.log(1. - cdf + 1e-9)
+    else:
+        table = np.zeros(1)
+    return a_bg, a_fg, s_bg, table
+
+
+def _max_centre_distance(shape, centres):
+    """the largest distance between a centre and a pixel (a corner of the image)"""
+    corners = np.array([(r, c) for r in (0, shape[0] - 1) for c in (0, shape[1] - 1)], dtype=np.int64)
+    diff = corners[None, :, :] - np.array(centres, dtype=np.int64)[:, None, :]
+    return float(np.sqrt(np.max(np.sum(diff * diff, axis=2))))
+
+
+def _seed_window(pos, seed_size):
+    """the square of side 2 * seed_size + 1 around a seed as (rows, columns); where it leaves the image the slices come out short
+    or empty and numpy refuses to put the disc there"""
+    row, col = int(pos[0]), int(pos[1])
+    return slice(row - seed_size, row + seed_size + 1), slice(col - seed_size, col + seed_size + 1)
+
+
+def _seed_disc(seed_size):
+    span = np.arange(-seed_size, seed_size + 1)
+    return (span[:, None]**2 + span[None, :]**2 <= seed_size**2).astype(np.uint8)
+
+
+def _object_pixels_unary(segm, centres, tables, coef_shape, seed_size):
+    """the float unary costs of :func:`object_segmentation_graphcut_pixels` (reference :214-242) from the tables: per pixel
+    u = A - coef_shape * S, the reference's order of operations; the seeds are 0"""
+    a_bg, a_fg, s_bg, table = tables
+    height, width = segm.shape
+    unary = np.empty((height, width, len(centres) + 1))
+    use_shape = coef_shape > 0
+    unary[:, :, 0] = a_bg[segm] - coef_shape * (s_bg[segm] if use_shape else 0.)
+    # (centre[0] is a row and centre[1] a column: the reference names the row index grid_x and the column index grid_y)
+    rows, cols = np.indices(segm.shape)
+    for i, centre in enumerate(centres):
+        if use_shape:
+            dist = _isqrt((rows - int(centre[0]))**2 + (cols - int(centre[1]))**2)
+            unary[:, :, i + 1] = a_fg[segm] - coef_shape * table[dist]
+        else:
+            unary[:, :, i + 1] = a_fg[segm] - coef_shape * 0.
+    for i, pos in enumerate(centres):
+        if seed_size > 0:
+            disc = np.zeros(segm.shape, dtype=bool)
+            disc[_seed_window(pos, seed_size)] = _seed_disc(seed_size)
+            unary[disc & (segm > 0), i + 1] = 0
+        else:
+            unary[pos[0], pos[1], i + 1] = 0
+    return unary
+
+
+def _object_pixels_refusals(segm, centres, tables, coef_shape, seed_size):
+    """what is refused before anything is launched; returns the seeds as rows and columns inside the image"""
+    a_bg, a_fg, s_bg, table = tables
+    probe = np.empty(segm.shape, dtype=bool)
+    seeds = []
+    for pos in centres:
+        if seed_size > 0:                       # a disc that leaves the image: the reference's slice assignment raises ValueError
+            probe[_seed_window(pos, seed_size)] = _seed_disc(seed_size)
+        else:
+            probe[pos[0], pos[1]] = False       # (IndexError as in the reference; a negative index counts from the end)
+        seeds.append((int(pos[0]) % segm.shape[0], int(pos[1]) % segm.shape[1]))
+    a_bg[[segm.min(), segm.max()]]              # (IndexError as in the reference)
+    present = np.unique(segm)
+    costs = [a_bg, a_fg] + ([s_bg] if coef_shape > 0 else [])
+    for label in present:
+        if not all(np.isfinite(cost[label]) for cost in costs):
+            raise ValueError('label %d has a foreground probability of 0 or 1: its unary cost is not finite' % label)
+    if not (np.isfinite(coef_shape) and np.all(np.isfinite(table))):
+        raise ValueError('the shape prior gives a unary cost that is not finite')
+    return seeds
+
+
+def object_segmentation_graphcut_pixels(segm, centres, labels_fg_prob=(0.1, 0.9), gc_regul=1, seed_size=0, coef_shape=0.,
+                                        shape_mean_std=(50., 10.), debug_visual=None, on=None):
+    """Label every pixel with 0 (background) or i + 1 (the object grown from centre i) by one alpha-expansion on the 4-connected
+    pixel grid (reference :159-256; the answers its docstring prints are in tests/object_cut_cases.py).  The data cost of a pixel
+    follows from its class in ``segm`` and, with a shape prior, from its integer distance to the centre (DESIGN.md section 4,
+    "Object cuts").
+
+    ``on='device'`` (the default when a device is present; ``IMSEGM_OBJECT_CUT_ON``): the class map, the centres and four small
+    tables go up; unary costs, pyGCO's integers, the grid and the cut are computed there (``imsegm_object_cut_pixels``).
+    ``on='host'``: the same costs in numpy, cut by ``cut_grid_graph``.  Without an explicit ``on``, an image whose tables exceed
+    what the device kernel keeps in LDS (a diagonal of several thousand pixels) takes the numpy costs as well.
+
+    :param ndarray segm: class map, height x width, integer classes that index ``labels_fg_prob``
+    :param list(tuple(int,int)) centres: (row, column) per object; rounded to integers
+    :param list(float) labels_fg_prob: per class, the probability that a pixel of it is part of an object
+    :param float gc_regul: cost of two neighbouring pixels with different labels
+    :param int seed_size: radius of the disc around a centre that is bound to its object where the class is not 0; 0: the
+        centre pixel alone
+    :param float coef_shape: weight of the shape prior, a normal distribution of the distance to the centre; <= 0: none
+    :param tuple(float,float) shape_mean_std: mean and standard deviation of that distribution
+    :param dict debug_visual: when given, receives ``'unary_imgs'``, the float cost image of every label
+    :param str on: ``'device'``, ``'host'`` or None
+    :return ndarray: int32 labels, height x width
+    """
+    if np.min(labels_fg_prob) >= 1:
+        raise ValueError('non label can ce strictly 1')
+    segm = np.asarray(segm)
+    if segm.max() > len(labels_fg_prob):
+        raise ValueError('table of label proba is shorter then the nb of labels in segmentation')
+    if not list(centres):
+        raise ValueError('at least one center has to be given')
+    centres = [np.round(c).astype(int) for c in centres]
+    place = _place(on, 'IMSEGM_OBJECT_CUT_ON')
+    tables = _object_tables(labels_fg_prob, coef_shape, shape_mean_std, _max_centre_distance(segm.shape, centres))
+    seeds = _object_pixels_refusals(segm, centres, tables, coef_shape, seed_size)
+    if on is None and place == 'device' and sum(t.nbytes for t in tables) + 16 * len(centres) > OBJECT_TABLES_DEVICE_MAX:
+        place = 'host'                          # (asked for explicitly, the device entry refuses such tables)
+    unary = None
+    if place == 'host' or debug_visual is not None:
+        unary = _object_pixels_unary(segm, centres, tables, coef_shape, seed_size)
+    if place == 'host':
+        height, width = segm.shape
+        pairwise = (1 - np.eye(len(centres) + 1)) * gc_regul
+        labels = cut_grid_graph(unary, pairwise, np.ones((height - 1, width)), np.ones((height, width - 1)), n_iter=999)
+        segm_obj = np.asarray(labels).reshape(segm.shape)
+    else:
+        rows = np.array([[c[0], c[1], s[0], s[1]] for c, s in zip(centres, seeds)], dtype=np.int32)
+        segm_obj, _ = _hip.object_cut_pixels(segm, rows, *tables, coef_shape=coef_shape, gc_regul=gc_regul, seed_size=max(seed_size, 0),
+                                             n_iter=999)
+    if debug_visual is not None:
+        debug_visual['unary_imgs'] = [unary[:, :, i] for i in range(unary.shape[-1])]
+    return segm_obj
+
+
+def _object_slic_terms(slic, labels, slic_points, edges, centres, labels_fg_prob, gc_regul, edge_coef, edge_type, coef_shape,
+                       shape_mean_std, add_neighbours):
+    """The graph :func:`object_segmentation_graphcut_slic` cuts, from the class of every superpixel (``labels``), the superpixel
+    centres and the adjacency: (edges, edge weights, unary, pairwise, weight maximum).
+
+    The unary costs come from the tables of the pixel variant (:func:`_object_tables`), read at the class of a superpixel and at
+    the truncated distance between its centre and the object's; the superpixel under a centre costs 0 for its object, and no
+    cost is below ``-log(MAX_UNARY_PROB)``.  With ``add_neighbours`` the neighbours of that superpixel cost 0 as well, and the
+    reference turns every edge at it into (0, 0), centre after centre: such self-edges still count where the 'model' weights take
+    their standard deviation, then they are dropped, and the largest of their weights is returned for pyGCO's scaling (None where
+    nothing was dropped)."""
+    points = np.asarray(slic_points, dtype=np.float64)
+    ends = np.array(edges)
+    n_columns = len(centres) + 1
+    use_shape = coef_shape > 0
+    dists = [np.sqrt(np.sum((points - centre)**2, axis=1)) for centre in centres] if use_shape else []
+    a_bg, a_fg, s_bg, table = _object_tables(labels_fg_prob, coef_shape, shape_mean_std, max([d.max() for d in dists] + [0.]))
+    unary_cost = np.empty((len(labels), n_columns))
+    unary_cost[:, 0] = a_bg[labels] - coef_shape * (s_bg[labels] if use_shape else 0.)
+    for column in range(1, n_columns):
+        unary_cost[:, column] = a_fg[labels] - coef_shape * (table[dists[column - 1].astype(int)] if use_shape else 0.)
+    for column, centre in enumerate(centres, 1):
+        seed = int(slic[centre[0], centre[1]])
+        unary_cost[seed, column] = 0.
+        if add_neighbours:
+            touching = (ends == seed).any(axis=1)
+            unary_cost[np.unique(ends[touching]), column] = 0.
+            ends[touching] = 0
+    np.maximum(unary_cost, -np.log(MAX_UNARY_PROB), out=unary_cost)
+    if edge_type == 'model':
+        class_fg = np.asarray(labels_fg_prob, dtype=np.float64)[labels]
+        gap = np.abs(class_fg[ends[:, 0]] - class_fg[ends[:, 1]])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            edge_weights = np.exp(-gap / (2 * np.std(gap)**2)) / compute_spatial_dist(points, ends, relative=True)
+    else:
+        edge_weights = np.ones(len(ends))
+    edge_weights = edge_weights * edge_coef
+    pairwise_cost = (1 - np.eye(n_columns)) * gc_regul
+    keep = ends[:, 0] != ends[:, 1]
+    weight_max = None
+    if not keep.all():
+        dropped = np.abs(edge_weights[~keep])
+        weight_max = float('nan') if np.isnan(dropped).any() else float(dropped.max())
+    return ends[keep], edge_weights[keep], unary_cost, pairwise_cost, weight_max
+
+
+def object_segmentation_graphcut_slic(slic, segm, centres, labels_fg_prob=(0.1, 0.9), gc_regul=1, edge_coef=0.5, edge_type='model',
+                                      coef_shape=0., shape_mean_std=(50., 10.), add_neighbours=False, debug_visual=None):
+    """Label every superpixel with 0 (background) or i + 1 (the object of centre i) by one alpha-expansion on the superpixel
+    adjacency graph (reference :42-156; the answers its docstring prints are in tests/object_cut_cases.py).  A composition of
+    ``histogram_regions_labels_norm``, ``superpixel_centers``, ``get_vertexes_edges``, ``compute_spatial_dist`` and the general
+    cut, all of which run on the device; the terms between them are numpy (:func:`_object_slic_terms`).
+
+    :param ndarray slic: superpixel map, height x width
+    :param ndarray segm: class map of the same shape; a superpixel takes the class most of its pixels have
+    :param list(tuple(int,int)) centres: (row, column) per object; rounded to integers
+    :param list(float) labels_fg_prob: per class, the probability that a superpixel of it is part of an object
+    :param float gc_regul: cost of two neighbouring superpixels with different labels
+    :param float edge_coef: factor on every edge weight
+    :param str edge_type: ``'model'``: weights from the difference of the two class probabilities and the distance of the two
+        centres; anything else: all edges weigh the same
+    :param float coef_shape: weight of the shape prior, a normal distribution of the distance to the centre; <= 0: none
+    :param tuple(float,float) shape_mean_std: mean and standard deviation of that distribution
+    :param bool add_neighbours: bind the neighbours of the superpixel under a centre to its object too
+    :param dict debug_visual: when given, receives ``'unary_imgs'``, the cost of every label as an image
+    :return ndarray: int32 label per superpixel
+    """
+    from pyimsegm_amd.superpixels import superpixel_centers
+    if np.min(labels_fg_prob) >= 1:
+        raise ValueError('non label can ce strictly 1')
+    slic, segm = np.asarray(slic), np.asarray(segm)
+    labels = np.argmax(histogram_regions_labels_norm(slic, segm), axis=1)
+    if segm.max() > len(labels_fg_prob):
+        raise ValueError('table of label prob is shorter then the nb of labels in segmentation')
+    if not list(centres):
+        raise ValueError('at least one center has to be given')
+    centres = [np.round(c).astype(int) for c in centres]
+    edges, edge_weights, unary_cost, pairwise_cost, weight_max = _object_slic_terms(
+        slic, labels, superpixel_centers(slic), get_vertexes_edges(slic)[1], centres, labels_fg_prob, gc_regul, edge_coef, edge_type,
+        coef_shape, shape_mean_std, add_neighbours)
+    graph_labels = _cut_scaled(edges, edge_weights, unary_cost, pairwise_cost, weight_max, n_iter=999)
+    if debug_visual is not None:
+        debug_visual['unary_imgs'] = [unary_cost[:, i][slic] for i in range(unary_cost.shape[-1])]
+    return graph_labels
+
+
+def _cut_scaled(edges, edge_weights, unary_cost, pairwise_cost, weight_max, n_iter):
+    """the general cut; with dropped self-edges the entry that takes their weight maximum ("Object cuts")"""
+    if weight_max is None:
+        return cut_general_graph(edges, edge_weights, unary_cost, pairwise_cost, n_iter=n_iter)
+    if np.isnan(weight_max):
+        raise ValueError('an edge at a seed has a weight that is not a number')
+    return _hip.cut_general_graph_scaled(edges, edge_weights, unary_cost, pairwise_cost, weight_max, n_iter=n_iter)
