@@ -642,6 +642,37 @@ IMSEGM_API int imsegm_ellipse_ransac(imsegm_ctx *ctx, int n_eggs, const int32_t 
                                      double *residuals_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fitted ellipses into a label map with the overlap test (imsegm/ellipse_fitting.py add_overlap_ellipse :282-349, the last call of
+ * segment_fit_ellipse / _ransac / _ransac_segm in experiments_ovary_detect/run_ovary_egg-segmentation.py and the inner loop of
+ * run_ellipse_annot_match.py and run_ellipse_cut_scale.py); csrc/ellipse_place.hip.  The mask of an ellipse is scikit-image
+ * 0.18.3's draw.ellipse(r, c, r_radius, c_radius, shape, rotation) (behind imsegm/utilities/drawing.py ellipse :116-151): the pixels
+ * of its clipped bounding box with ((a cos + b sin) / r_radius)^2 + ((a sin - b cos) / c_radius)^2 < 1 for their integer offsets
+ * (a, b) from the centre, in fp64 with one rounding per operation.  Integers and that one expression: same call, same bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_ELLIPSE_PLACE_LABELS 4096   /* labels 0 .. 4095 own a slot of the two int32 label tables the fold keeps in LDS (32 KiB) */
+/* An ellipse is 8 int32 of geom -- centre row, centre column, row radius, column radius (radii >= 1; all four at most 2^30 in
+ * absolute value), then first row, first column, last row, last column of its bounding box clipped to the map (inclusive; a last
+ * below its first: the ellipse has no pixel) -- and 2 doubles of sincos, the sine and the cosine of its angle taken modulo pi.  The
+ * caller computes the boxes and the pair (pyimsegm_amd/ellipse_fitting.py ellipse_geometry): no kernel evaluates a
+ * transcendental or a ceil.
+ *
+ * imsegm_ellipse_place replaces the fold `for e: segm = add_overlap_ellipse(segm, params[e], labels[e], thr_overlap)`: ellipse e is
+ * painted with labels[e] (placed[e] = 1) unless its mask is empty or one label lb >= 1 under it has
+ * (double)overlap / (double)min(pixels of lb in the map as it stands, pixels of the mask) > thr_overlap -- one IEEE division, a
+ * strict comparison.  segm: host int32 height x width, read and written in place (only rows that were painted are written);
+ * every value must be below IMSEGM_ELLIPSE_PLACE_LABELS (values <= 0 are never tested, as in the reference), every label too (a
+ * label <= 0 may be painted).  Returns -1 with segm untouched for a map of 2^31 pixels or more, a box that is not clipped, a radius
+ * below 1, thr_overlap negative or NaN, or a value or label without a slot.  n = 0 is a no-op. */
+IMSEGM_API int imsegm_ellipse_place(imsegm_ctx *ctx, int32_t *segm, int height, int width, int n, const int32_t *geom,
+                                    const double *sincos, const int32_t *labels, double thr_overlap, uint8_t *placed);
+/* For every ellipse on its own: areas[e] = pixels of its mask, counts[e * nb_labels + l] = those of them with segm == l for
+ * 0 <= l < nb_labels <= IMSEGM_ELLIPSE_PLACE_LABELS (other values count in the area only) -- what the Jaccard indices of
+ * run_ellipse_annot_match.py select_optimal_ellipse need besides one bincount.  One launch, int64 atomics.  Both outputs are host
+ * arrays; errors as above. */
+IMSEGM_API int imsegm_ellipse_overlaps(imsegm_ctx *ctx, const int32_t *segm, int height, int width, int n, const int32_t *geom,
+                                       const double *sincos, int nb_labels, int64_t *counts, int64_t *areas);
+
+/* ---------------------------------------------------------------------------------------------
  * From an egg class map with centre candidates to the rays the boundary points of the RANSAC are made of (imsegm/ellipse_fitting.py
  * split_segm_background_foreground :400-443 and the ray casting of prepare_boundary_points_ray_join / _edge / _mean / _dist
  * :352-597); csrc/morphology.hip.  Integers only up to the ray walk: same call, same bytes.

@@ -187,6 +187,8 @@ _SIGNATURES = {
     'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
     'imsegm_ellipse_ransac': (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                         _vp]),
+    'imsegm_ellipse_place': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp]),
+    'imsegm_ellipse_overlaps': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp]),
     'imsegm_split_background_foreground': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'imsegm_boundary_rays': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
     'imsegm_rg_open': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
@@ -1714,6 +1716,52 @@ def ellipse_ransac(point_offsets, points, params, success, trial_egg, points_all
                                                 float(residual_threshold), _ptr(best), _ptr(kept), _ptr(mask), _ptr(criterion),
                                                 _ptr(residuals)))
     return best, kept, mask, criterion, residuals
+
+
+#: ``IMSEGM_ELLIPSE_PLACE_LABELS``: labels 0 .. 4095 own a slot of the label tables of csrc/ellipse_place.hip
+ELLIPSE_PLACE_LABELS = 4096
+#: what a centre coordinate or a radius of ``imsegm_ellipse_place`` / ``imsegm_ellipse_overlaps`` may be in absolute value
+ELLIPSE_PLACE_MAX_COORD = 1 << 30
+
+
+def _ellipse_arguments(segm, geom, sincos):
+    if segm.ndim != 2 or segm.dtype != np.int32 or not segm.flags.c_contiguous:
+        raise ValueError('the label map must be a C-contiguous 2-D int32 array')
+    geom = np.ascontiguousarray(geom, dtype=np.int32).reshape(-1, 8)
+    sincos = np.ascontiguousarray(sincos, dtype=np.float64).reshape(-1, 2)
+    if len(geom) != len(sincos):
+        raise ValueError('one (sin, cos) pair per ellipse')
+    return geom, sincos
+
+
+def ellipse_place(segm, geom, sincos, labels, thr_overlap, ctx=None):
+    """``imsegm_ellipse_place``: paints the ellipses ``geom`` int32 [n, 8] (centre, radii, clipped box) / ``sincos`` float64 [n, 2]
+    with ``labels`` int32 [n] into the C-contiguous int32 map ``segm`` IN PLACE, one after the other, each unless it overlaps a label
+    of the map as it stands by more than ``thr_overlap``; returns placed uint8 [n]: see include/imsegm_hip.h"""
+    geom, sincos = _ellipse_arguments(segm, geom, sincos)
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    if len(labels) != len(geom):
+        raise ValueError('one label per ellipse')
+    placed = np.zeros(len(geom), dtype=np.uint8)
+    if len(geom) == 0:
+        return placed
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_ellipse_place(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], len(geom), _ptr(geom), _ptr(sincos),
+                                               _ptr(labels), float(thr_overlap), _ptr(placed)))
+    return placed
+
+
+def ellipse_overlaps(segm, geom, sincos, nb_labels, ctx=None):
+    """``imsegm_ellipse_overlaps``: per ellipse the histogram of the labels 0 .. nb_labels - 1 of the C-contiguous int32 map
+    ``segm`` under its mask and the size of the mask: (counts int64 [n, nb_labels], areas int64 [n])"""
+    geom, sincos = _ellipse_arguments(segm, geom, sincos)
+    counts, areas = np.zeros((len(geom), int(nb_labels)), dtype=np.int64), np.zeros(len(geom), dtype=np.int64)
+    if len(geom) == 0:
+        return counts, areas
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_ellipse_overlaps(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], len(geom), _ptr(geom), _ptr(sincos),
+                                                  int(nb_labels), _ptr(counts), _ptr(areas)))
+    return counts, areas
 
 
 #: ``IMSEGM_MORPH_MAX_RADIUS``: the largest disc radius of the opening kernels

@@ -1,10 +1,52 @@
 // api_ellipse.hip -- C ABI of the RANSAC scoring of ellipse trials (imsegm/ellipse_fitting.py ransac_segm): a stateless call on a
 // context and host arrays.  Arguments are checked before the device is touched -- every index the kernels form comes from the
-// offsets checked here; the kernels are in ellipse.hip.
+// offsets checked here; the kernels are in ellipse.hip.  Behind it the last step of the ellipse methods, add_overlap_ellipse: fitted
+// ellipses into a label map, and the label histogram under every ellipse (kernels in ellipse_place.hip); every box the kernels walk
+// is checked against the map here.
 #include "ellipse.h"
+#include "ellipse_place.h"
 #include "session.h"
 
+#include <cmath>
 #include <vector>
+
+static_assert(ELLIPSE_PLACE_LABELS == IMSEGM_ELLIPSE_PLACE_LABELS, "LDS budget of ellipse_place.hip");
+
+namespace imsegm {
+
+// the arguments both ellipse_place calls share; *max_box_rows: the tallest clipped box (0: no ellipse has a pixel)
+static int check_ellipses(const char *who, const int32_t *segm, int H, int W, int n, const int32_t *geom, const double *sincos,
+                          int *max_box_rows)
+{
+    const std::string name(who);
+    if (H < 1 || W < 1 || H > ELLIPSE_PLACE_MAX_COORD || W > ELLIPSE_PLACE_MAX_COORD || (long long)H * W >= (1ll << 31)) {
+        set_error(name + ": height and width must be positive and the map smaller than 2^31 pixels");
+        return -1;
+    }
+    if (!segm || n < 0 || (n > 0 && (!geom || !sincos))) {
+        set_error(name + ": null array or a negative number of ellipses");
+        return -1;
+    }
+    *max_box_rows = 0;
+    for (int e = 0; e < n; ++e) {
+        const int32_t *g = geom + (size_t)e * ELLIPSE_GEOM_INTS;
+        if (g[2] < 1 || g[3] < 1 || g[2] > ELLIPSE_PLACE_MAX_COORD || g[3] > ELLIPSE_PLACE_MAX_COORD ||
+            g[0] < -ELLIPSE_PLACE_MAX_COORD || g[0] > ELLIPSE_PLACE_MAX_COORD || g[1] < -ELLIPSE_PLACE_MAX_COORD ||
+            g[1] > ELLIPSE_PLACE_MAX_COORD) {
+            set_error(name + ": ellipse " + std::to_string(e) + " has a radius below 1 or a centre or radius beyond 2^30");
+            return -1;
+        }
+        if (g[6] < g[4] || g[7] < g[5]) continue;                     // no pixel: the kernels' loops do not run
+        if (g[4] < 0 || g[5] < 0 || g[6] >= H || g[7] >= W) {
+            set_error(name + ": the box of ellipse " + std::to_string(e) + " is not clipped to the map");
+            return -1;
+        }
+        if (g[6] - g[4] + 1 > *max_box_rows) *max_box_rows = g[6] - g[4] + 1;
+    }
+    return 0;
+}
+
+}  // namespace imsegm
 
 extern "C" {
 
@@ -117,6 +159,116 @@ int imsegm_ellipse_ransac(imsegm_ctx *ctx, int n_eggs, const int32_t *point_offs
     HIP_TRY(hipMemcpyAsync(mask_out, job.mask, n_points, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(criterion_out, job.criterion, (size_t)n_trials * 8, hipMemcpyDeviceToHost, st));
     if (residuals_out) HIP_TRY(hipMemcpyAsync(residuals_out, job.residuals, n_pairs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int imsegm_ellipse_place(imsegm_ctx *ctx, int32_t *segm, int height, int width, int n, const int32_t *geom, const double *sincos,
+                         const int32_t *labels, double thr_overlap, uint8_t *placed)
+{
+    int max_box_rows = 0;
+    if (check_ellipses("ellipse_place", segm, height, width, n, geom, sincos, &max_box_rows)) return -1;
+    if (n > 0 && (!labels || !placed)) {
+        set_error("ellipse_place: null array");
+        return -1;
+    }
+    if (!(thr_overlap >= 0.0)) {
+        set_error("ellipse_place: thr_overlap must not be negative or NaN");
+        return -1;
+    }
+    for (int e = 0; e < n; ++e)
+        if (labels[e] >= IMSEGM_ELLIPSE_PLACE_LABELS) {
+            set_error("ellipse_place: label " + std::to_string(labels[e]) + " has no slot in the label table");
+            return -1;
+        }
+    if (n == 0) return 0;
+    if (bind(ctx)) return -1;
+    hipStream_t st = ctx->stream;
+    const size_t pixels = (size_t)height * width;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return here;
+    };
+    const size_t o_segm = take(pixels * 4), o_counts = take((size_t)IMSEGM_ELLIPSE_PLACE_LABELS * 4 + 4);
+    const size_t o_geom = take((size_t)n * ELLIPSE_GEOM_INTS * 4), o_sincos = take((size_t)n * 16), o_labels = take((size_t)n * 4);
+    const size_t o_placed = take((size_t)n);
+    if (ctx->gc_buf.ensure(at)) return -1;
+    unsigned char *dev = ctx->gc_buf.as<unsigned char>();
+    int32_t *d_segm = reinterpret_cast<int32_t *>(dev + o_segm), *d_counts = reinterpret_cast<int32_t *>(dev + o_counts);
+    int32_t *d_beyond = d_counts + IMSEGM_ELLIPSE_PLACE_LABELS;
+    HIP_TRY(hipMemcpyAsync(d_segm, segm, pixels * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + o_geom, geom, (size_t)n * ELLIPSE_GEOM_INTS * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + o_sincos, sincos, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + o_labels, labels, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)IMSEGM_ELLIPSE_PLACE_LABELS * 4 + 4, st));
+    if (launch_ellipse_label_counts(d_segm, pixels, d_counts, d_beyond, st)) return -1;
+    if (launch_ellipse_place(d_segm, width, n, reinterpret_cast<const int32_t *>(dev + o_geom),
+                             reinterpret_cast<const double *>(dev + o_sincos), reinterpret_cast<const int32_t *>(dev + o_labels),
+                             thr_overlap, d_counts, d_beyond, dev + o_placed, st))
+        return -1;
+    int32_t beyond = 0;
+    HIP_TRY(hipMemcpyAsync(&beyond, d_beyond, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(placed, dev + o_placed, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (beyond) {
+        set_error("ellipse_place: the map holds a value that has no slot in the label table (IMSEGM_ELLIPSE_PLACE_LABELS)");
+        return -1;
+    }
+    // only the rows an ellipse was painted into come back
+    int first = height, last = -1;
+    for (int e = 0; e < n; ++e) {
+        const int32_t *g = geom + (size_t)e * ELLIPSE_GEOM_INTS;
+        if (!placed[e]) continue;
+        if (g[4] < first) first = g[4];
+        if (g[6] > last) last = g[6];
+    }
+    if (last >= first) {
+        const size_t from = (size_t)first * width;
+        HIP_TRY(hipMemcpyAsync(segm + from, d_segm + from, (size_t)(last - first + 1) * width * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+int imsegm_ellipse_overlaps(imsegm_ctx *ctx, const int32_t *segm, int height, int width, int n, const int32_t *geom,
+                            const double *sincos, int nb_labels, int64_t *counts, int64_t *areas)
+{
+    int max_box_rows = 0;
+    if (check_ellipses("ellipse_overlaps", segm, height, width, n, geom, sincos, &max_box_rows)) return -1;
+    if (nb_labels < 1 || nb_labels > IMSEGM_ELLIPSE_PLACE_LABELS) {
+        set_error("ellipse_overlaps: between 1 and IMSEGM_ELLIPSE_PLACE_LABELS labels");
+        return -1;
+    }
+    if (n > 0 && (!counts || !areas)) {
+        set_error("ellipse_overlaps: null array");
+        return -1;
+    }
+    if (n == 0) return 0;
+    if (bind(ctx)) return -1;
+    hipStream_t st = ctx->stream;
+    const size_t pixels = (size_t)height * width, table = (size_t)n * nb_labels;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return here;
+    };
+    const size_t o_segm = take(pixels * 4), o_geom = take((size_t)n * ELLIPSE_GEOM_INTS * 4), o_sincos = take((size_t)n * 16);
+    const size_t o_counts = take(table * 8), o_areas = take((size_t)n * 8);
+    if (ctx->gc_buf.ensure(at)) return -1;
+    unsigned char *dev = ctx->gc_buf.as<unsigned char>();
+    HIP_TRY(hipMemcpyAsync(dev + o_segm, segm, pixels * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + o_geom, geom, (size_t)n * ELLIPSE_GEOM_INTS * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dev + o_sincos, sincos, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dev + o_counts, 0, at - o_counts, st));             // the counts and, behind them, the areas
+    if (launch_ellipse_overlaps(reinterpret_cast<const int32_t *>(dev + o_segm), width, n, reinterpret_cast<const int32_t *>(dev + o_geom),
+                                reinterpret_cast<const double *>(dev + o_sincos), nb_labels, max_box_rows,
+                                reinterpret_cast<long long *>(dev + o_counts), reinterpret_cast<long long *>(dev + o_areas), st))
+        return -1;
+    HIP_TRY(hipMemcpyAsync(counts, dev + o_counts, table * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(areas, dev + o_areas, (size_t)n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

@@ -1,0 +1,31 @@
+// ellipse_place.h -- launchers of csrc/ellipse_place.hip (rasterising fitted ellipses into a label map with the reference's overlap
+// test, and the label histogram under every ellipse; the C ABI is in api_ellipse.hip)
+#pragma once
+#include "common.h"
+
+namespace imsegm {
+
+// Labels 0 .. ELLIPSE_PLACE_LABELS - 1 own a slot of the label tables (IMSEGM_ELLIPSE_PLACE_LABELS of include/imsegm_hip.h).  The fold
+// keeps two int32 tables of that length in LDS -- the running pixel count of every label and the histogram under the current
+// ellipse: 2 x 16 KiB of the 64 KiB a workgroup may take.
+constexpr int ELLIPSE_PLACE_LABELS = 4096;
+// what a centre coordinate or a radius may be in absolute value: row - centre stays inside int32 for every row of a map
+constexpr int ELLIPSE_PLACE_MAX_COORD = 1 << 30;
+
+// One ellipse is 8 int32 of `geom` -- centre row, centre column, row radius, column radius, first row, first column, last row, last
+// column of its bounding box clipped to the map (inclusive; last < first: no pixel) -- and 2 doubles of `sincos`: sin and cos of
+// its angle.  Both come from the host, so that no kernel evaluates a transcendental or a ceil.
+constexpr int ELLIPSE_GEOM_INTS = 8;
+
+// counts[v] += number of pixels with value v for 1 <= v < ELLIPSE_PLACE_LABELS (counts zeroed by the caller); *beyond = 1 when a
+// value >= ELLIPSE_PLACE_LABELS is met
+int launch_ellipse_label_counts(const int32_t *segm, size_t n_pixels, int32_t *counts, int32_t *beyond, hipStream_t st);
+// the fold over the n ellipses in order; does nothing (placed = 0) when *beyond is set
+int launch_ellipse_place(int32_t *segm, int width, int n, const int32_t *geom, const double *sincos, const int32_t *labels,
+                         double thr_overlap, const int32_t *counts, const int32_t *beyond, uint8_t *placed, hipStream_t st);
+// counts[e][l] (zeroed by the caller) = pixels of value l under ellipse e for 0 <= l < nb_labels <= ELLIPSE_PLACE_LABELS,
+// areas[e] (zeroed too) = pixels under ellipse e; max_box_rows: the tallest clipped box
+int launch_ellipse_overlaps(const int32_t *segm, int width, int n, const int32_t *geom, const double *sincos, int nb_labels,
+                            int max_box_rows, long long *counts, long long *areas, hipStream_t st);
+
+}  // namespace imsegm

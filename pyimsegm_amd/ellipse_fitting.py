@@ -14,6 +14,11 @@
   ``_mean`` / ``_dist`` -- smooths the class map and casts the rays of all centres on the device (``imsegm_boundary_rays``,
   csrc/morphology.hip); what follows the rays (at most 72 values per centre) is the reference's numpy in float64.  ``on='host'`` is
   the scipy / numpy statement of the same definitions (:func:`split_host`, :func:`ray_walk_host`).
+* The step behind the fits -- ``add_overlap_ellipse`` / ``add_overlap_ellipses`` and ``ellipse_label_overlaps`` -- rasterises the
+  ellipses (scikit-image's ``draw.ellipse``, restated as :func:`ellipse_pixels_host`) and applies the reference's overlap test on the
+  device (``imsegm_ellipse_place`` / ``imsegm_ellipse_overlaps``, csrc/ellipse_place.hip); ``on='host'`` is the numpy statement
+  (:func:`place_host`, :func:`overlaps_host`).  ``filter_boundary_points`` and ``prepare_boundary_points_close`` compose device calls
+  of ``pyimsegm_amd.superpixels``.
 
 Definitions ("Ellipse RANSAC"): the criterion keeps the reference's ``weights[labels_in]`` -- the weight is
 looked up by the CLASS LABEL of a centre inside the ellipse, not by the centre; the residual is the distance to the closest
@@ -717,3 +722,325 @@ def prepare_boundary_points_ray_dist(seg, centers, close_points=1, sel_bg=STRUC_
     points[(points < 0) & (points > -1e-3)] = 0.
     close_center = np.argmin(cdist(points, centers, metric='euclidean'), axis=1)
     return [points[close_center == i] for i in range(close_center.max() + 1)]
+
+
+# ------------------------------------------------------------------------------------------------
+# fitted ellipses into a label map with the overlap test (reference ellipse_fitting.py:282-349), and what stands around it
+# ------------------------------------------------------------------------------------------------
+
+#: a single ``add_overlap_ellipse`` goes to the device by default only from this ``max(segm)`` on: below it the host statement's
+#: ``max(segm)`` passes over the map cost less than carrying the map to the device and back (tools/time_ellipse_place.py)
+SINGLE_CALL_DEVICE_FROM_LABELS = 2
+
+
+def _place_place(on):
+    """'host', 'device' or None (the default: the device when one is present, the host for a single ellipse on a map with few
+    labels) from the ``on`` keyword and the environment variable IMSEGM_ELLIPSE_PLACE_ON"""
+    if on is None:
+        on = os.environ.get('IMSEGM_ELLIPSE_PLACE_ON') or None
+    if on not in (None, 'host', 'device'):
+        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
+    if on != 'host':
+        try:
+            present = _hip.device_count() > 0
+        except _hip.HipUnavailableError:
+            present = False
+        if not present:
+            if on == 'device':
+                raise _hip.HipUnavailableError('no HIP device is visible')
+            return 'host'
+    return on
+
+
+def _ellipse_box(r, c, r_radius, c_radius, orientation, shape):
+    """sine and cosine of the angle modulo pi and the bounding box of the rotated ellipse, clipped to ``shape`` when given:
+    (sin, cos, upper_left int [2], lower_right int [2]), the operations of scikit-image 0.18.3's ``draw.ellipse`` in its order"""
+    center = np.array([r, c])
+    orientation = orientation % np.pi
+    sin_alpha, cos_alpha = np.sin(orientation), np.cos(orientation)
+    r_radius_rot = abs(r_radius * cos_alpha) + c_radius * abs(sin_alpha)
+    c_radius_rot = r_radius * abs(sin_alpha) + abs(c_radius * cos_alpha)
+    radii_rot = np.array([r_radius_rot, c_radius_rot])
+    upper_left = np.ceil(center - radii_rot).astype(int)
+    lower_right = np.floor(center + radii_rot).astype(int)
+    if shape is not None:
+        upper_left = np.maximum(upper_left, np.array([0, 0]))
+        lower_right = np.minimum(lower_right, np.array(shape[:2]) - 1)
+    return sin_alpha, cos_alpha, upper_left, lower_right
+
+
+def ellipse_pixels_host(r, c, r_radius, c_radius, orientation=0., shape=None):
+    """ the pixels of an ellipse: scikit-image 0.18.3's ``draw.ellipse(r, c, r_radius, c_radius, shape, rotation=orientation)``, which
+    the reference's ``utilities.drawing.ellipse`` hands its arguments to, restated in numpy.  The angle is taken modulo pi; the
+    bounding box runs from ``ceil(centre - radii_rot)`` to ``floor(centre + radii_rot)`` with the rotated radii
+    ``|r_radius cos| + c_radius |sin|`` and ``r_radius |sin| + |c_radius cos|`` and is clipped to ``shape``; a pixel with the offsets
+    (a, b) from the centre is inside when ``((a cos + b sin) / r_radius)**2 + ((a sin - b cos) / c_radius)**2 < 1`` in float64,
+    every operation rounded on its own.  Row-major order.
+
+    >>> rr, cc = ellipse_pixels_host(7, 10, 5, 8, np.deg2rad(30), (15, 20))
+    >>> len(rr), int(rr.min()), int(rr.max()), int(cc.min()), int(cc.max())
+    (127, 2, 12, 3, 17)
+
+    :param int r: centre row
+    :param int c: centre column
+    :param int r_radius: radius along the rows
+    :param int c_radius: radius along the columns
+    :param float orientation: angle in radians
+    :param tuple(int,int) shape: size of the image the pixels are clipped to
+    :return tuple(ndarray,ndarray): rows, columns
+    """
+    sin_alpha, cos_alpha, upper_left, lower_right = _ellipse_box(r, c, r_radius, c_radius, orientation, shape)
+    r_org, c_org = np.array([r, c]) - upper_left
+    bounding_shape = lower_right - upper_left + 1
+    r_lim, c_lim = np.ogrid[0:float(bounding_shape[0]), 0:float(bounding_shape[1])]
+    rows, cols = (r_lim - r_org), (c_lim - c_org)
+    with np.errstate(all='ignore'):
+        distances = ((rows * cos_alpha + cols * sin_alpha) / r_radius) ** 2 + ((rows * sin_alpha - cols * cos_alpha) / c_radius) ** 2
+    rr, cc = np.nonzero(distances < 1)
+    return rr + upper_left[0], cc + upper_left[1]
+
+
+def _int_params(ellipse_params):
+    """the reference's reading of (c1, c2, h, w, phi): the first four truncated with ``int()``"""
+    c1, c2, h, w, phi = ellipse_params
+    return int(c1), int(c2), int(h), int(w), phi
+
+
+def place_host(segm, list_params, labels, thr_overlap):
+    """the numpy statement of ``imsegm_ellipse_place``: the reference's ``add_overlap_ellipse`` ellipse by ellipse, ``segm`` changed
+    in place; placed bool [E] -- painted, with at least one pixel"""
+    placed = np.zeros(len(list_params), dtype=bool)
+    for e, (params, label) in enumerate(zip(list_params, labels)):
+        if not params:
+            continue
+        c1, c2, h, w, phi = _int_params(params)
+        rr, cc = ellipse_pixels_host(c1, c2, h, w, orientation=phi, shape=segm.shape)
+        under, area, accepted = segm[rr, cc], len(rr), True
+        for lb in range(1, int(np.max(segm) + 1)):
+            overlap = np.sum(under == lb)
+            sizes = [s for s in [np.sum(segm == lb), area] if s > 0]
+            if not sizes or float(overlap) / float(min(sizes)) > thr_overlap:
+                accepted = False
+                break
+        if accepted:
+            segm[rr, cc] = label
+            placed[e] = area > 0
+    return placed
+
+
+def overlaps_host(segm, list_params, nb_labels):
+    """the numpy statement of ``imsegm_ellipse_overlaps``: (counts int64 [E, nb_labels], areas int64 [E])"""
+    nb_labels = max(int(nb_labels), 0)
+    counts, areas = np.zeros((len(list_params), nb_labels), dtype=np.int64), np.zeros(len(list_params), dtype=np.int64)
+    for e, params in enumerate(list_params):
+        if not params:
+            continue
+        c1, c2, h, w, phi = _int_params(params)
+        rr, cc = ellipse_pixels_host(c1, c2, h, w, orientation=phi, shape=segm.shape)
+        under = segm[rr, cc]
+        areas[e] = len(rr)
+        under = under[(under >= 0) & (under < nb_labels)]
+        whole = under.astype(np.int64)
+        counts[e] = np.bincount(whole[whole == under], minlength=nb_labels)[:nb_labels]
+    return counts, areas
+
+
+def ellipse_geometry(list_params, shape):
+    """what the device takes of ellipses that were read with :func:`_int_params`: (geom int32 [E, 8] -- centre, radii, clipped
+    bounding box --, sincos float64 [E, 2]), or None when one of them is not the device's: a radius below 1, a centre or radius beyond
+    2^30, an angle that is not finite"""
+    geom, sincos = np.zeros((len(list_params), 8), dtype=np.int32), np.zeros((len(list_params), 2), dtype=np.float64)
+    for e, (c1, c2, h, w, phi) in enumerate(list_params):
+        try:
+            phi = float(phi)
+        except (TypeError, ValueError):
+            return None
+        if not (np.isfinite(phi) and 1 <= h <= _hip.ELLIPSE_PLACE_MAX_COORD and 1 <= w <= _hip.ELLIPSE_PLACE_MAX_COORD
+                and abs(c1) <= _hip.ELLIPSE_PLACE_MAX_COORD and abs(c2) <= _hip.ELLIPSE_PLACE_MAX_COORD):
+            return None
+        sin_alpha, cos_alpha, upper_left, lower_right = _ellipse_box(c1, c2, h, w, phi, shape)
+        if np.any(lower_right < upper_left):
+            upper_left, lower_right = np.array([0, 0]), np.array([-1, -1])
+        geom[e] = (c1, c2, h, w, upper_left[0], upper_left[1], lower_right[0], lower_right[1])
+        sincos[e] = (sin_alpha, cos_alpha)
+    return geom, sincos
+
+
+def _device_map(segm, upper):
+    """``segm`` as the C-contiguous int32 map the device reads (``segm`` itself when it is one), or None when the device does not take
+    it: not a non-empty 2-D array below 2^31 pixels, values that are no integers, below int32 or above ``upper``"""
+    if not isinstance(segm, np.ndarray) or segm.ndim != 2 or segm.size == 0 or segm.size >= 2 ** 31 or segm.dtype.kind not in 'biuf':
+        return None
+    low, high = segm.min(), segm.max()
+    if not (low >= np.iinfo(np.int32).min and high <= upper):                  # (NaN fails both)
+        return None
+    if segm.dtype.kind == 'f' and not np.array_equal(segm, np.trunc(segm)):
+        return None
+    if segm.dtype == np.int32 and segm.flags.c_contiguous:
+        return segm
+    return np.ascontiguousarray(segm, dtype=np.int32)
+
+
+def _device_labels(labels, dtype):
+    """the labels as int32, or None when one is no integer below the label table, or is not itself once stored in a map of
+    ``dtype`` (the fold then reads back another value than it painted)"""
+    try:
+        values = np.asarray(labels, dtype=np.float64).ravel()
+    except (TypeError, ValueError):
+        return None
+    if len(values) and not (np.all(values == np.trunc(values)) and values.min() >= np.iinfo(np.int32).min
+                            and values.max() < _hip.ELLIPSE_PLACE_LABELS):
+        return None
+    whole = values.astype(np.int64)
+    with np.errstate(all='ignore'):
+        if not np.array_equal(whole.astype(dtype).astype(np.float64), values):
+            return None
+    return whole.astype(np.int32)
+
+
+def add_overlap_ellipses(segm, list_params, labels=None, thr_overlap=1., on=None):
+    """ the fold of :func:`add_overlap_ellipse` over a list of ellipses -- what the loops of ``segment_fit_ellipse``,
+    ``segment_fit_ellipse_ransac`` and ``segment_fit_ellipse_ransac_segm`` do with their fits: ellipse e is painted into ``segm`` with
+    ``labels[e]`` unless it overlaps a label of the map as it stands by more than ``thr_overlap``.  One upload of the map, one
+    histogram launch, one launch that walks the ellipses, one download (``imsegm_ellipse_place``, csrc/ellipse_place.hip);
+    ``on='host'`` (or the environment variable ``IMSEGM_ELLIPSE_PLACE_ON=host``, or no device) runs the numpy statement
+    :func:`place_host`, and so does every call the device does not take: a radius below 1 after truncation, ``thr_overlap`` negative
+    or NaN, a map that is not 2-D, not integer-valued or beyond int32, a value or label beyond ``IMSEGM_ELLIPSE_PLACE_LABELS``.
+
+    :param ndarray segm: label map, changed in place
+    :param list(tuple) list_params: (row, column, row radius, column radius, angle) per ellipse; a falsy entry is skipped
+    :param list(int) labels: label per ellipse, default 1 .. E
+    :param float thr_overlap: largest accepted overlap relative to the smaller of the two objects
+    :return tuple(ndarray,ndarray): ``segm`` itself and placed bool [E]: the ellipse was painted (with at least one pixel)
+    """
+    list_params = list(list_params)
+    labels = list(range(1, len(list_params) + 1)) if labels is None else list(labels)
+    if len(labels) != len(list_params):
+        raise ValueError('%i labels for %i ellipses' % (len(labels), len(list_params)))
+    place = _place_place(on)
+    kept = [e for e, params in enumerate(list_params) if params]
+    ints = [_int_params(list_params[e]) for e in kept]
+    placed = np.zeros(len(list_params), dtype=bool)
+    if not kept:
+        return segm, placed
+    work = geometry = device_labels = None
+    if place != 'host':
+        try:
+            threshold_ok = float(thr_overlap) >= 0
+        except (TypeError, ValueError):
+            threshold_ok = False
+        if threshold_ok:
+            work = _device_map(segm, _hip.ELLIPSE_PLACE_LABELS - 1)
+        if work is not None:
+            geometry = ellipse_geometry(ints, segm.shape)
+            device_labels = _device_labels([labels[e] for e in kept], segm.dtype)
+        if place is None and work is not None and len(kept) == 1 and segm.max() < SINGLE_CALL_DEVICE_FROM_LABELS:
+            work = None
+    if work is None or geometry is None or device_labels is None:
+        placed[kept] = place_host(segm, [list_params[e] for e in kept], [labels[e] for e in kept], thr_overlap)
+        return segm, placed
+    placed[kept] = _hip.ellipse_place(work, geometry[0], geometry[1], device_labels, float(thr_overlap)).astype(bool)
+    if work is not segm:
+        segm[...] = work
+    return segm, placed
+
+
+def add_overlap_ellipse(segm, ellipse_params, label, thr_overlap=1., on=None):
+    """ add to existing image ellipse with specific label
+    if the new ellipse does not ouvelap with already existing object / ellipse (reference ``ellipse_fitting.py:282-349``): for every
+    label ``1 .. max(segm)`` the overlap with the ellipse relative to the smaller of the two must not exceed ``thr_overlap``.  The
+    ellipse is that of :func:`ellipse_pixels_host` after ``int()`` of centre and radii; ``segm`` is changed in place and returned.
+    Places and the calls the device does not take as :func:`add_overlap_ellipses`, of which this is the list of one; by default a
+    single ellipse goes to the device only when ``max(segm) >= SINGLE_CALL_DEVICE_FROM_LABELS``.
+
+    >>> seg = np.zeros((15, 20), dtype=int)
+    >>> ell = add_overlap_ellipse(seg, (7, 10, 5, 8, np.deg2rad(30)), 1, on='host')
+    >>> ell is seg, int(ell.sum())
+    (True, 127)
+    >>> int((add_overlap_ellipse(ell, (4, 5, 2, 3, np.deg2rad(-30)), 2, on='host') == 2).sum())
+    19
+
+    :param ndarray segm: segmentation
+    :param tuple ellipse_params: parameters
+    :param int label: selected label
+    :param float thr_overlap: relative overlap with existing objects
+    :return ndarray:
+    """
+    if not ellipse_params:
+        return segm
+    return add_overlap_ellipses(segm, [ellipse_params], [label], thr_overlap, on)[0]
+
+
+def ellipse_label_overlaps(segm, list_params, nb_labels=None, on=None):
+    """ for every ellipse on its own the number of its pixels inside ``segm`` and the histogram of the labels
+    ``0 .. nb_labels - 1`` under it: with ``np.bincount(segm.ravel())`` the Jaccard index of every candidate ellipse against every
+    annotated egg, which ``select_optimal_ellipse`` of ``run_ellipse_annot_match.py`` gets from one rasterised mask per pair.  One
+    launch over ellipses and bands of their boxes (``imsegm_ellipse_overlaps``); ``on='host'`` and every call the device does not
+    take (see :func:`add_overlap_ellipses`; ``nb_labels`` beyond ``IMSEGM_ELLIPSE_PLACE_LABELS`` too) run :func:`overlaps_host`.
+
+    :param ndarray segm: label map
+    :param list(tuple) list_params: (row, column, row radius, column radius, angle) per ellipse; a falsy entry counts nothing
+    :param int nb_labels: default ``max(segm) + 1``
+    :return tuple(ndarray,ndarray): counts int64 [E, nb_labels], areas int64 [E]
+    """
+    segm = np.asarray(segm)
+    list_params = list(list_params)
+    nb_labels = int(np.max(segm) + 1) if nb_labels is None else int(nb_labels)
+    place = _place_place(on)
+    kept = [e for e, params in enumerate(list_params) if params]
+    ints = [_int_params(list_params[e]) for e in kept]
+    work = geometry = None
+    if place != 'host' and kept and 1 <= nb_labels <= _hip.ELLIPSE_PLACE_LABELS:
+        work = _device_map(segm, np.iinfo(np.int32).max)
+        if work is not None:
+            geometry = ellipse_geometry(ints, segm.shape)
+    if work is None or geometry is None:
+        return overlaps_host(segm, list_params, nb_labels)
+    counts, areas = np.zeros((len(list_params), nb_labels), dtype=np.int64), np.zeros(len(list_params), dtype=np.int64)
+    counts[kept], areas[kept] = _hip.ellipse_overlaps(work, geometry[0], geometry[1], nb_labels)
+    return counts, areas
+
+
+def filter_boundary_points(segm, slic):
+    """ the centres of the superpixels on the border between background and objects (reference ``ellipse_fitting.py:600-622``):
+    background superpixels (class 0 at their centre) with a neighbour of another class, and superpixels of class 1 with a background
+    neighbour.  Centres and the edge list come from the device (``superpixel_centers``, ``make_graph_segm_connect_grid2d_conn4``);
+    the share of every class among a superpixel's neighbours is two scatter-adds over the edge list.
+
+    :param ndarray segm: class map H x W
+    :param ndarray slic: superpixels H x W
+    :return ndarray: points N x 2 (int)
+    """
+    from pyimsegm_amd.superpixels import make_graph_segm_connect_grid2d_conn4, superpixel_centers
+    slic_centers = np.array(superpixel_centers(slic)).astype(int)
+    labels = segm[slic_centers[:, 0], slic_centers[:, 1]]
+    vertices, edges = make_graph_segm_connect_grid2d_conn4(slic)
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    neighbour_labels = np.zeros((int(np.max(vertices)) + 1, int(labels.max()) + 1))
+    np.add.at(neighbour_labels, (edges[:, 0], labels[edges[:, 1]]), 1)
+    np.add.at(neighbour_labels, (edges[:, 1], labels[edges[:, 0]]), 1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        neighbour_labels = neighbour_labels / neighbour_labels.sum(axis=1)[:, None]
+        filter_bg = np.logical_and(labels == 0, neighbour_labels[:, 0] < 1)
+        filter_fc = np.logical_and(labels == 1, neighbour_labels[:, 0] > 0)
+    return slic_centers[np.logical_or(filter_bg, filter_fc)]
+
+
+def prepare_boundary_points_close(seg, centers, sp_size=25, relative_compact=0.3):
+    """ extract some point around foreground boundaries (reference ``ellipse_fitting.py:625-653``): SLIC superpixels of the class map
+    scaled to [0, 1] on the device, :func:`filter_boundary_points`, every point given to the centre nearest to it; the list ends at
+    the last centre that got a point
+
+    :param ndarray seg: input segmentation
+    :param list(tuple(int,int)) centers: list of centers
+    :param int sp_size: superpixel size
+    :param float relative_compact: SLIC regularisation
+    :return list(ndarray):
+    """
+    from pyimsegm_amd.superpixels import segment_slic_img2d
+    slic = segment_slic_img2d(seg / float(seg.max()), sp_size=sp_size, relative_compact=relative_compact)
+    points_all = filter_boundary_points(seg, slic)
+    centers = np.asarray(centers, dtype=np.float64).reshape(-1, 2)
+    diff = points_all[:, None, :].astype(np.float64) - centers[None, :, :]
+    close_center = np.argmin(np.sqrt((diff * diff).sum(axis=2)), axis=1)
+    return [points_all[close_center == i] for i in range(int(close_center.max() + 1))]
