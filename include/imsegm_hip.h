@@ -39,6 +39,11 @@ extern "C" {
  * fits on the host */
 #define IMSEGM_E_FIT_CAPS (-4)
 
+/* status of imsegm_object_shapes for a map it does not take -- more objects than the caller's capacity, or more than two label
+ * values that span IMSEGM_OBJECT_SHAPES_MAX_SPAN or more: nothing is wrong with the context and no error message is set -- the
+ * caller evaluates the map on the host */
+#define IMSEGM_E_OBJECT_CAPS (-5)
+
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
 typedef struct imsegm_image2d imsegm_image2d;   /* device-resident state of one H x W image */
 
@@ -740,6 +745,35 @@ IMSEGM_API int imsegm_rg_greedy_step(imsegm_rg *rg, const int32_t *labels, int a
                                      int32_t *objects_out, int32_t *superpixels_out, double *changes_out);
 /* Replaces compute_rg_crit (:1114-1133) on the resident tables: a fixed summation tree, the same labels give the same bytes */
 IMSEGM_API int imsegm_rg_criterion(imsegm_rg *rg, const int32_t *labels, const double *coefs, double *criterion_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * From annotated egg maps to the rays a shape model is estimated from (imsegm/region_growing.py compute_object_shapes :289-331 with
+ * the first half of compute_segm_object_shape :259-280); csrc/object_shapes.hip.  Integers up to the centre of mass, then the ray
+ * walk: same map, same bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_OBJECT_SHAPES_MAX_SPAN 65536     /* entries of the presence table: max - min of a map of more than two values stays below it */
+#define IMSEGM_OBJECT_SHAPES_MAX_OBJECTS 65536  /* the largest capacity a caller may ask for */
+/* Replaces, for all objects of one map at once, the loop of :319-329 -- np.unique, scipy.ndimage.label, one `img == label` mask,
+ * ndimage.center_of_mass and compute_ray_features_segm_2d(mask, centre, ray_step, 0, edge='down') per object -- by one labelling, one
+ * reduction and one ray launch.  segm: host int32, height x width.
+ *   * At most two distinct values (np.unique(img) <= 2, :321): the objects are the 4-connected components of the pixels != 0,
+ *     numbered from 1 in raster order of their first pixel (scipy.ndimage.label with its default cross), labels_out[k] = k + 1.  As
+ *     np.unique(labelled)[1:] drops the first value whatever it is, a map without a 0 has no objects, and neither has a constant map.
+ *   * More than two values: the objects are the distinct values in ascending order WITHOUT the smallest (0 or not); an object is not
+ *     split into components; labels_out[k] is the value.  max - min must stay below IMSEGM_OBJECT_SHAPES_MAX_SPAN.
+ * Per object k < *n_objects_out, in that order: moments_out[3 k ..] = pixel count, sum of rows, sum of columns (int64, exact);
+ * centres_out[2 k ..] = int(round(sum / count)) per coordinate, one IEEE fp64 division and round-half-to-even (ndimage.center_of_mass of
+ * a boolean mask forms this quotient); rays_out[k * n_angles ..] = the float32 distances from the centre to where the object ends
+ * along directions (n_angles x 2 float32, the table of imsegm_ray_features_binary2d), -1 where no such edge is met.  The centre of
+ * an object of several pieces may lie outside it; the walk then starts outside, as the reference's does.
+ * Returns 0; IMSEGM_E_OBJECT_CAPS with *n_objects_out = the number of objects when that exceeds max_objects, or = -1 when the values
+ * span too much -- no per-object output is written and no error message set; -1 with a message for n_angles outside
+ * [1, IMSEGM_RAY_MAX_ANGLES], a non-positive height or width, 2^31 pixels or more, or max_objects outside
+ * [0, IMSEGM_OBJECT_SHAPES_MAX_OBJECTS] (with 0 the per-object outputs may be NULL: the call counts).  One upload, one chain of
+ * launches on the context's stream without a host round trip, one download. */
+IMSEGM_API int imsegm_object_shapes(imsegm_ctx *ctx, const int32_t *segm, int height, int width, const float *directions,
+                                    int n_angles, int max_objects, int *n_objects_out, int32_t *labels_out, int64_t *moments_out,
+                                    int32_t *centres_out, float *rays_out);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ class HipFitCapsError(HipError):
 
 IMSEGM_E_FUSED_PATH = -3
 IMSEGM_E_FIT_CAPS = -4
+IMSEGM_E_OBJECT_CAPS = -5
 
 
 _lib = None
@@ -199,6 +200,7 @@ _SIGNATURES = {
     'imsegm_rg_object_shapes': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     'imsegm_rg_greedy_step': (C.c_int, [_vp, _vp, C.c_int, _vp, _ip, _vp, _vp, _vp]),
     'imsegm_rg_criterion': (C.c_int, [_vp, _vp, _vp, _vp]),
+    'imsegm_object_shapes': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _ip, _vp, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -1791,6 +1793,33 @@ def boundary_rays(segm, sel_bg, sel_fg, positions, directions, with_fg=True, ctx
     _check(load_library().imsegm_boundary_rays(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], int(sel_bg), int(sel_fg), _ptr(positions),
                                                len(positions), _ptr(directions), len(directions), _ptr(rays_bg), _ptr(rays_fg)))
     return rays_bg, rays_fg
+
+
+#: ``IMSEGM_OBJECT_SHAPES_MAX_SPAN`` / ``IMSEGM_OBJECT_SHAPES_MAX_OBJECTS``
+OBJECT_SHAPES_MAX_SPAN, OBJECT_SHAPES_MAX_OBJECTS = 65536, 65536
+
+
+def object_shapes(segm, directions, max_objects=1024, ctx=None):
+    """``imsegm_object_shapes``: the objects of a C-contiguous 2-D int32 label map in the order of ``compute_object_shapes`` with
+    their moments, rounded centres of mass and raw 'down' rays, from one chain of launches: (n_objects, labels int32 [n], moments
+    int64 [n, 3], centres int32 [n, 2], rays float32 [n, A]).  A map the call does not take (``IMSEGM_E_OBJECT_CAPS``) gives
+    (n_objects, None, None, None, None): n_objects above ``max_objects``, or -1 for label values that span
+    ``OBJECT_SHAPES_MAX_SPAN`` or more -- no error."""
+    if segm.ndim != 2 or segm.dtype != np.int32 or not segm.flags.c_contiguous:
+        raise ValueError('the label map must be a C-contiguous 2-D int32 array')
+    directions = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 2)
+    capacity = int(max_objects)
+    labels, moments = np.empty(capacity, dtype=np.int32), np.empty((capacity, 3), dtype=np.int64)
+    centres, rays = np.empty((capacity, 2), dtype=np.int32), np.empty((capacity, len(directions)), dtype=np.float32)
+    count = C.c_int(0)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_object_shapes(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], _ptr(directions), len(directions),
+                                                 capacity, C.byref(count), _ptr(labels), _ptr(moments), _ptr(centres), _ptr(rays))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return count.value, None, None, None, None
+    _check(status)
+    n = count.value
+    return n, labels[:n], moments[:n], centres[:n], rays[:n]
 
 
 def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):

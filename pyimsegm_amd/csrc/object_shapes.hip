@@ -1,0 +1,346 @@
+// object_shapes.hip -- the objects of an annotated label map with the rays of their shape, on the device: what
+// compute_object_shapes (imsegm/region_growing.py:289-331) computes in front of the fill / smooth / rotate of
+// compute_segm_object_shape (:259-286) -- np.unique, scipy.ndimage.label with its default cross, ndimage.center_of_mass of every
+// `img == label` mask and computeRayFeaturesBinary2d(mask, centre, edge='down') -- for ALL objects of a map in one chain of launches:
+// label once, reduce once, cast the rays of every object together.  Integers up to the centre (one fp64 division, rint) and the walk
+// of k_rg_object_rays (region_growing.hip): same map, same bytes.  The numpy statement of the same definitions is
+// pyimsegm_amd/region_growing.py (_object_shape_rays_host).
+//
+// Nothing comes back to the host between the launches: the case decision, the number of objects and the capacity test live in a
+// header on the device (OS_* of object_shapes.h); a kernel whose case was not taken returns at once.
+#include "object_shapes.h"
+#include "scan.h"
+#include "slic.h"
+#include "unionfind.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace imsegm {
+
+// ---- case decision: smallest value, largest value, and whether a value lies strictly between them ------------------------------
+// (np.unique(img) has at most two entries exactly when nothing does.)  The triple of two pixel sets joins to the triple of their
+// union; the empty set is (INT_MAX, INT_MIN, 0), which no comparison below takes for a value in between.
+struct OsRange {
+    int lo, hi, mid;
+};
+__device__ __forceinline__ OsRange os_join(const OsRange &a, const OsRange &b)
+{
+    OsRange r;
+    r.lo = min(a.lo, b.lo);
+    r.hi = max(a.hi, b.hi);
+    auto between = [&](int x) { return x > r.lo && x < r.hi; };
+    r.mid = a.mid | b.mid | between(a.lo) | between(a.hi) | between(b.lo) | between(b.hi);
+    return r;
+}
+// join over a workgroup of 256; the result is valid in thread 0
+__device__ __forceinline__ OsRange os_join_block(OsRange r)
+{
+    __shared__ OsRange per_wave[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        OsRange o;
+        o.lo = __shfl_xor(r.lo, off, 64);
+        o.hi = __shfl_xor(r.hi, off, 64);
+        o.mid = __shfl_xor(r.mid, off, 64);
+        r = os_join(r, o);
+    }
+    if ((threadIdx.x & 63) == 0) per_wave[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) r = os_join(os_join(per_wave[0], per_wave[1]), os_join(per_wave[2], per_wave[3]));
+    return r;
+}
+
+__global__ void __launch_bounds__(256) k_os_range(const int32_t *__restrict__ segm, int n, int32_t *__restrict__ partial)
+{
+    OsRange r = { INT_MAX, INT_MIN, 0 };
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long)gridDim.x * 256) {
+        const int v = segm[p];
+        r = os_join(r, OsRange{ v, v, 0 });
+    }
+    r = os_join_block(r);
+    if (threadIdx.x == 0) {
+        partial[3 * blockIdx.x] = r.lo;
+        partial[3 * blockIdx.x + 1] = r.hi;
+        partial[3 * blockIdx.x + 2] = r.mid;
+    }
+}
+
+// one workgroup: the triples of all workgroups -> the header
+__global__ void __launch_bounds__(256) k_os_decide(const int32_t *__restrict__ partial, int n_partial, int32_t *__restrict__ hdr)
+{
+    OsRange r = { INT_MAX, INT_MIN, 0 };
+    for (int i = threadIdx.x; i < n_partial; i += 256) r = os_join(r, OsRange{ partial[3 * i], partial[3 * i + 1], partial[3 * i + 2] });
+    r = os_join_block(r);
+    if (threadIdx.x != 0) return;
+    int mode;
+    if (!r.mid) {
+        // ndimage.label: every non-zero pixel is foreground; np.unique(labelled)[1:] drops the 0 -- or, in a map without a 0, the
+        // one component there is
+        const bool has_zero = r.lo == 0 || r.hi == 0, has_object = r.lo != 0 || r.hi != 0;
+        mode = has_zero && has_object ? OS_RELABEL : OS_NONE;
+    } else {
+        mode = (long long)r.hi - (long long)r.lo < OS_MAX_SPAN ? OS_VALUES : OS_SPAN;
+    }
+    hdr[OS_MIN] = r.lo;
+    hdr[OS_MAX] = r.hi;
+    hdr[OS_MODE] = mode;
+    hdr[OS_COUNT] = 0;
+}
+
+// ---- relabelled case: scipy.ndimage.label, 4-connected, on the pixels != 0 -----------------------------------------------------
+// The run rule of k_holes_init / k_holes_merge (morphology.hip) on another predicate: a wave covers 64 consecutive pixels of a row,
+// every object pixel starts out pointing at the first pixel of its run inside that segment, and the unions that are left lie where a
+// run crosses a segment and where a run meets the row above for the first time.  Workgroup b covers pixels 256 c .. 256 c + 255 of
+// row y, b = y * chunks + c.
+__global__ void __launch_bounds__(256)
+k_os_cc_init(const int32_t *__restrict__ segm, const int32_t *__restrict__ hdr, int32_t *__restrict__ parent, int W, int chunks)
+{
+    if (hdr[OS_MODE] != OS_RELABEL) return;
+    const int lane = threadIdx.x & 63;
+    const int y = blockIdx.x / chunks, x = (blockIdx.x - y * chunks) * 256 + threadIdx.x;
+    const size_t row = (size_t)y * W;
+    const bool inx = x < W;
+    const bool obj = inx && segm[row + x] != 0;
+    const unsigned long long z = __ballot(obj);
+    if (!inx) return;
+    int start = lane;
+    if (obj) {
+        const unsigned long long starts = z & ~(z << 1);
+        const unsigned long long below = starts & ((2ULL << lane) - 1ULL);
+        start = 63 - __clzll((long long)below);
+    }
+    parent[row + x] = (int)(row + x) - (lane - start);
+}
+
+__global__ void __launch_bounds__(256)
+k_os_cc_merge(const int32_t *__restrict__ segm, const int32_t *__restrict__ hdr, int32_t *parent, int W, int chunks)
+{
+    if (hdr[OS_MODE] != OS_RELABEL) return;
+    const int lane = threadIdx.x & 63;
+    const int y = blockIdx.x / chunks, x = (blockIdx.x - y * chunks) * 256 + threadIdx.x;
+    const size_t row = (size_t)y * W;
+    const bool inx = x < W;
+    const bool obj = inx && segm[row + x] != 0;
+    const bool up_any = inx && y > 0 && segm[row - W + x] != 0;
+    const bool up = obj && up_any;
+    const unsigned long long z = __ballot(obj), zu = __ballot(up_any);
+    if (!obj) return;
+    const int p = (int)(row + x);
+    const bool first = lane == 0 || !((z >> (lane - 1)) & 1ULL);
+    if (lane == 0 && x > 0 && segm[p - 1] != 0) uf_union_pair(parent, p, p - 1);
+    if (up && (first || !((zu >> (lane - 1)) & 1ULL))) uf_union_pair(parent, p, p - W);
+}
+
+// ---- keys and their presence ---------------------------------------------------------------------------------------------------
+// key of a pixel: the root of its component (relabelled case; roots are the smallest index of a set, so their order is the raster
+// order of the first pixels, scipy's numbering) or value - min (multi-label case; the smallest value is no object), -1 for a pixel
+// of no object.  table[key] = 1 for every key there is: by the root itself, or by the first pixel of every run of a value.
+__global__ void __launch_bounds__(256)
+k_os_keys(const int32_t *__restrict__ segm, const int32_t *__restrict__ hdr, const int32_t *__restrict__ parent, int n,
+          int32_t *__restrict__ key, int32_t *__restrict__ table)
+{
+    const int mode = hdr[OS_MODE];
+    if (mode != OS_RELABEL && mode != OS_VALUES) return;
+    const unsigned int p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= (unsigned int)n) return;
+    const int v = segm[p];
+    int k = -1;
+    if (mode == OS_RELABEL) {
+        if (v != 0) {
+            k = uf_find(parent, (int)p);
+            if (k == (int)p) table[k] = 1;
+        }
+    } else {
+        const int lo = hdr[OS_MIN];
+        if (v != lo) {
+            k = (int)((long long)v - (long long)lo);                  // below OS_MAX_SPAN <= table_len in this mode
+            if (p == 0 || segm[p - 1] != v) table[k] = 1;
+        }
+    }
+    key[p] = k;
+}
+
+// ---- ranks: the objects in ascending order of their key ------------------------------------------------------------------------
+// A workgroup owns 1024 consecutive entries of the table: k_os_block_count counts the present ones, launch_exclusive_scan (scan.hip)
+// turns the counts into the rank of every workgroup's first object and the number of objects, k_os_assign ranks inside.
+__global__ void __launch_bounds__(256) k_os_block_count(const int32_t *__restrict__ table, int len, int32_t *__restrict__ blocksum)
+{
+    __shared__ int per_wave[4];
+    const int i = blockIdx.x * 1024 + threadIdx.x * 4;
+    int v[4];
+    load4_i32(table, i, len, 0, v);
+    const int t = wave_sum_i32(i < len ? v[0] + v[1] + v[2] + v[3] : 0);
+    if ((threadIdx.x & 63) == 0) per_wave[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = (per_wave[0] + per_wave[1]) + (per_wave[2] + per_wave[3]);
+}
+
+__global__ void __launch_bounds__(256)
+k_os_assign(int32_t *table, int len, const int32_t *__restrict__ blocksum, const int32_t *__restrict__ hdr, int max_objects,
+            int32_t *__restrict__ obj_key, int32_t *__restrict__ labels)
+{
+    const int i = blockIdx.x * 1024 + threadIdx.x * 4;
+    int v[4];
+    if (i < len) {
+        load4_i32(table, i, len, 0, v);
+    } else {
+        v[0] = v[1] = v[2] = v[3] = 0;
+    }
+    int total;
+    int rank = blocksum[blockIdx.x] + block_exclusive_scan<4>(v[0] + v[1] + v[2] + v[3], &total);
+    const bool by_value = hdr[OS_MODE] == OS_VALUES;
+    const int lo = hdr[OS_MIN];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (i + c >= len) break;
+        if (v[c]) {
+            table[i + c] = rank;
+            if (rank < max_objects) {
+                obj_key[rank] = i + c;
+                labels[rank] = by_value ? (int)((long long)lo + (i + c)) : rank + 1;
+            }
+            ++rank;
+        } else {
+            table[i + c] = -1;
+        }
+    }
+}
+
+// ---- moments: pixel count, row sum and column sum of every object, int64 -------------------------------------------------------
+// A workgroup takes a tile of 256 columns x OS_TILE_ROWS rows.  In a row, the lanes of a wave that hold one key side by side are a
+// run: its first lane knows the length from a ballot and adds the run in closed form (count n, rows y n, columns n x + n (n - 1) / 2)
+// to the slot of the object's rank in LDS -- 256 slots, claimed by compare-and-swap on a tag; an object whose slot another object of
+// the tile holds goes to global memory directly.  At the end every claimed slot is added to the global sums once: three global
+// atomics per (object, tile) instead of three per pixel.  Integer atomics only: the sums do not depend on the order.
+constexpr int OS_TILE_ROWS = 16;
+
+__global__ void __launch_bounds__(256)
+k_os_moments(const int32_t *__restrict__ key, const int32_t *__restrict__ table, const int32_t *__restrict__ hdr, int H, int W,
+             int chunks, int max_objects, long long *moments)
+{
+    const int count = hdr[OS_COUNT];
+    if (count == 0 || count > max_objects) return;
+    __shared__ int tag[256];
+    __shared__ unsigned long long acc[256 * 3];
+    tag[threadIdx.x] = -1;
+    acc[3 * threadIdx.x] = acc[3 * threadIdx.x + 1] = acc[3 * threadIdx.x + 2] = 0ULL;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int band = blockIdx.x / chunks, x = (blockIdx.x - band * chunks) * 256 + threadIdx.x;
+    const bool inx = x < W;
+    const int y_end = min(H, (band + 1) * OS_TILE_ROWS);
+    for (int y = band * OS_TILE_ROWS; y < y_end; ++y) {
+        const int k = inx ? key[(size_t)y * W + x] : -1;
+        const bool brk = lane == 0 || lane_prev(k, -2) != k;                     // a run (of a key or of -1) begins here
+        const unsigned long long breaks = __ballot(brk);
+        const int rank = brk && k >= 0 ? table[k] : max_objects;
+        if (rank >= max_objects) continue;                                        // no first lane of an object's run
+        const unsigned long long later = breaks & ~((2ULL << lane) - 1ULL);
+        const unsigned long long len = (unsigned long long)((later ? __ffsll((long long)later) - 1 : 64) - lane);
+        const unsigned long long rows = (unsigned long long)y * len, cols = len * (unsigned long long)x + len * (len - 1) / 2;
+        const int slot = rank & 255;
+        const int seen = atomicCAS(&tag[slot], -1, rank);
+        if (seen == -1 || seen == rank) {
+            atomicAdd(&acc[3 * slot], len);
+            atomicAdd(&acc[3 * slot + 1], rows);
+            atomicAdd(&acc[3 * slot + 2], cols);
+        } else {
+            atomic_add_i64(&moments[3 * (size_t)rank], (long long)len);
+            atomic_add_i64(&moments[3 * (size_t)rank + 1], (long long)rows);
+            atomic_add_i64(&moments[3 * (size_t)rank + 2], (long long)cols);
+        }
+    }
+    __syncthreads();
+    const int rank = tag[threadIdx.x];
+    if (rank >= 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) atomic_add_i64(&moments[3 * (size_t)rank + j], (long long)acc[3 * threadIdx.x + j]);
+    }
+}
+
+// int(round(c)) for c of ndimage.center_of_mass(mask): the quotient of two exactly representable sums, one IEEE division, and
+// Python's round (half to even)
+__global__ void __launch_bounds__(256)
+k_os_centres(const long long *__restrict__ moments, const int32_t *__restrict__ hdr, int max_objects, int32_t *__restrict__ centres)
+{
+    const int count = hdr[OS_COUNT];
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (count > max_objects || o >= count) return;
+    const double pixels = (double)moments[3 * o];
+    centres[2 * o] = (int32_t)rint((double)moments[3 * o + 1] / pixels);
+    centres[2 * o + 1] = (int32_t)rint((double)moments[3 * o + 2] / pixels);
+}
+
+// ---- rays ------------------------------------------------------------------------------------------------------------------------
+// computeRayFeaturesBinary2d (features_cython.pyx:244-282) with edge 'down' on the mask key == key of the object, which is never
+// materialised: the walk of k_rg_object_rays (region_growing.hip) / k_ray_features_binary2d (natives.hip), the same float32 / float64
+// operations in the same order.  One wave per object, the lanes stride over the angles.  The centre of an object of several pieces
+// may lie outside it: the walk then starts with last = false, as the reference's does.
+__global__ void __launch_bounds__(64)
+k_os_rays(const int32_t *__restrict__ key, int H, int W, const int32_t *__restrict__ hdr, int max_objects,
+          const int32_t *__restrict__ obj_key, const int32_t *__restrict__ centres, const float *__restrict__ grad, int A,
+          float *__restrict__ out)
+{
+    const int count = hdr[OS_COUNT];
+    const int o = blockIdx.x;
+    if (count > max_objects || o >= count) return;
+    const int own = obj_key[o];
+    const int py = centres[2 * o], px = centres[2 * o + 1];
+    const bool inside = py >= 0 && py < H && px >= 0 && px < W;
+    const bool start = inside ? key[(size_t)py * W + px] == own : false;
+    const int diag = (int)sqrt((double)W * W + (double)H * H);
+    for (int a = threadIdx.x; a < A; a += 64) {
+        float res = -1.f;
+        if (inside) {
+            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
+            float pos0 = (float)py, pos1 = (float)px;
+            bool last = start;
+            for (int it = 0; it < diag; ++it) {
+                pos0 += g0;
+                pos1 += g1;
+                const double r0 = round((double)pos0), r1 = round((double)pos1);
+                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
+                const bool actual = key[(size_t)(int)r0 * W + (int)r1] == own;
+                if (last && !actual) {
+                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
+                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
+                    break;
+                }
+                last = actual;
+            }
+        }
+        out[(size_t)o * A + a] = res;
+    }
+}
+
+int launch_object_shapes(const OsView &v, hipStream_t st)
+{
+    const int n = v.H * v.W;
+    const int chunks = cdiv(v.W, 256);
+    const int row_groups = v.H * chunks;
+    const int range_blocks = min(OS_RANGE_BLOCKS, cdiv(n, 256 * 8));
+    const int table_blocks = cdiv(v.table_len, 1024);
+    HIP_TRY(hipMemsetAsync(v.table, 0, (size_t)v.table_len * 4, st));
+    if (v.max_objects > 0) HIP_TRY(hipMemsetAsync(v.moments, 0, (size_t)v.max_objects * 24, st));
+    hipLaunchKernelGGL(k_os_range, range_blocks, 256, 0, st, v.segm, n, v.partial);
+    hipLaunchKernelGGL(k_os_decide, 1, 256, 0, st, v.partial, range_blocks, v.hdr);
+    hipLaunchKernelGGL(k_os_cc_init, row_groups, 256, 0, st, v.segm, v.hdr, v.parent, v.W, chunks);
+    hipLaunchKernelGGL(k_os_cc_merge, row_groups, 256, 0, st, v.segm, v.hdr, v.parent, v.W, chunks);
+    hipLaunchKernelGGL(k_os_keys, cdiv(n, 256), 256, 0, st, v.segm, v.hdr, v.parent, n, v.key, v.table);
+    hipLaunchKernelGGL(k_os_block_count, table_blocks, 256, 0, st, v.table, v.table_len, v.blocksum);
+    launch_exclusive_scan(v.blocksum, table_blocks, v.hdr + OS_COUNT, st);
+    hipLaunchKernelGGL(k_os_assign, table_blocks, 256, 0, st, v.table, v.table_len, v.blocksum, v.hdr, v.max_objects, v.obj_key,
+                       v.labels);
+    if (v.max_objects > 0) {
+        hipLaunchKernelGGL(k_os_moments, cdiv(v.H, OS_TILE_ROWS) * chunks, 256, 0, st, v.key, v.table, v.hdr, v.H, v.W, chunks,
+                           v.max_objects, v.moments);
+        hipLaunchKernelGGL(k_os_centres, cdiv(v.max_objects, 256), 256, 0, st, v.moments, v.hdr, v.max_objects, v.centres);
+        hipLaunchKernelGGL(k_os_rays, v.max_objects, 64, 0, st, v.key, v.H, v.W, v.hdr, v.max_objects, v.obj_key, v.centres,
+                           v.directions, v.A, v.rays);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace imsegm

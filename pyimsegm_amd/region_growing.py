@@ -18,6 +18,8 @@ Definitions ("Region growing"): the shape prior is bilinear
 import os
 
 import numpy as np
+from scipy import ndimage, stats
+from sklearn import cluster, mixture
 
 from pyimsegm_amd import _hip
 from pyimsegm_amd.descriptors import _ray_directions, interpolate_ray_dist, shift_ray_features
@@ -339,22 +341,301 @@ def compute_segm_object_shape(img_object, ray_step=5, interp_order=3, smooth_coe
 
     :return tuple(list(float),float): rays, rotation
     """
-    from scipy import ndimage
     from pyimsegm_amd.descriptors import compute_ray_features_segm_2d
     start = [int(round(c)) for c in ndimage.center_of_mass(img_object)]
     return _finish_rays(compute_ray_features_segm_2d(img_object, start, ray_step, 0, edge='down'), interp_order, smooth_coef,
                         shift_method)
 
 
-def _finish_rays(rays, interp_order=3, smooth_coef=0, shift_method='phase'):
-    """what follows the ray walk of :func:`compute_segm_object_shape`: fill, smooth, rotate"""
+def _finish_rays(rays, interp_order=3, smooth_coef=0, shift_method='phase', shift_rays=shift_ray_features):
+    """what follows the ray walk of :func:`compute_segm_object_shape`: fill, smooth, rotate (by ``shift_rays``)"""
     if interp_order is not None and np.any(np.asarray(rays) == -1):
         rays = interpolate_ray_dist(rays, interp_order)
     if smooth_coef > 0:
         from scipy.ndimage import gaussian_filter1d
         rays = gaussian_filter1d(rays, smooth_coef)
-    rays, rotation = shift_ray_features(rays, shift_method)
+    rays, rotation = shift_rays(rays, shift_method)
     return rays.tolist(), rotation
+
+
+def _shift_rays_double(ray_dist, method='phase'):
+    """``shift_ray_features`` for the float32 rays of the walk with the spectrum in float64: numpy before 2.0 transformed a float32
+    vector in double -- the answers recorded from the reference, and the ``45.`` of its doctest -- where numpy 2 keeps single
+    precision, which moves the phase by some 1e-6 degrees.  The mean is taken off in float32 first, as both do."""
+    ray_dist = np.asarray(ray_dist)
+    if method != 'phase' or ray_dist.dtype != np.float32:
+        return shift_ray_features(ray_dist, method)
+    periods = np.hstack([ray_dist] * 5)
+    half = len(periods) // 2
+    spectrum = np.fft.fft((periods - np.mean(periods)).astype(np.float64)) / float(len(periods))
+    strongest = np.argmax(np.abs(spectrum)[:half])
+    shift = np.rad2deg(-np.angle(spectrum)[:half][strongest])
+    shift = (360 + shift) if shift < 0 else shift
+    steps = int(round(shift / (360 / len(ray_dist))))
+    return np.array(ray_dist[steps:].tolist() + ray_dist[:steps].tolist()), shift
+
+
+# ------------------------------------------------------------------------------------------------
+# ray shape models from annotated label maps (reference :289-588)
+# ------------------------------------------------------------------------------------------------
+
+
+#: objects of one map ``imsegm_object_shapes`` is given room for; a map with more is evaluated on the host
+OBJECT_SHAPES_CAPACITY = 1024
+
+
+def _int32_map(img):
+    """the map as a C-contiguous int32 array where that holds every value exactly (integers, booleans, floats with integral
+    values), else None"""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.size == 0 or img.dtype.kind not in 'iubf':
+        return None
+    if img.dtype.kind == 'f' and not (np.all(np.isfinite(img)) and np.all(img == np.rint(img))):
+        return None
+    info = np.iinfo(np.int32)
+    if img.dtype.kind == 'b' or (info.min <= img.min() and img.max() <= info.max):
+        return np.ascontiguousarray(img, dtype=np.int32)
+    return None
+
+
+def _object_shape_rays_host(img, directions):
+    """the numpy / scipy statement of ``imsegm_object_shapes`` (csrc/object_shapes.hip): the objects of a map as the reference's
+    ``compute_object_shapes`` takes them (:320-326) -- the components of ``ndimage.label`` for a map of at most two values, else the
+    values -- without the first, each with its exact pixel count, row sum and column sum, the rounded centre of mass of
+    ``compute_segm_object_shape`` (:278-279) and the raw 'down' rays from there"""
+    values = np.unique(img)
+    if len(values) <= 2:
+        img, _ = ndimage.label(img)
+        values = np.unique(img)
+    labels = values[1:]
+    rows, cols = np.indices(img.shape)
+    moments = np.zeros((len(labels), 3), dtype=np.int64)
+    centres = np.zeros((len(labels), 2), dtype=np.int32)
+    rays = np.zeros((len(labels), len(directions)), dtype=np.float32)
+    for k, label in enumerate(labels):
+        mask = img == label
+        count, row_sum, col_sum = int(np.count_nonzero(mask)), int(rows[mask].sum()), int(cols[mask].sum())
+        moments[k] = count, row_sum, col_sum
+        # ndimage.center_of_mass of a boolean mask: this quotient of two exactly representable sums
+        centres[k] = int(round(row_sum / float(count))), int(round(col_sum / float(count)))
+        rays[k] = ray_distances_down(mask, centres[k], directions)
+    return labels, moments, centres, rays
+
+
+def object_shape_rays(img_objects, ray_step=5, on=None):
+    """the stage of :func:`compute_object_shapes` in front of :func:`_finish_rays`, for one map: its objects in the reference's
+    order with their labels, moments int64 [n, 3] (pixel count, row sum, column sum), rounded centres of mass int32 [n, 2] and raw
+    'down' rays float32 [n, angles], -1 where a ray meets no edge.
+
+    ``on='device'`` (the default when a device is present; ``IMSEGM_OBJECT_SHAPES_ON``): one ``imsegm_object_shapes`` call -- the
+    map goes up, labelling, moments, centres and the rays of all objects are one chain of launches, the four tables come down.
+    ``on='host'``: the numpy / scipy statement of the same definitions.  A map that is not integer-valued or leaves int32, label
+    values that span ``_hip.OBJECT_SHAPES_MAX_SPAN`` or more, and more than ``OBJECT_SHAPES_CAPACITY`` objects take the host
+    statement as well ("Object shapes").
+
+    :param ndarray img_objects: annotated map: at most two values (objects are the 4-connected components of the non-zero pixels)
+        or one value per object above the smallest one
+    :param int ray_step: angular step of the rays in degrees
+    :param str on: ``'device'``, ``'host'`` or None
+    :return tuple(ndarray,ndarray,ndarray,ndarray): labels, moments, centres, raw_rays
+    """
+    place = _place(on, 'IMSEGM_OBJECT_SHAPES_ON')
+    directions = _ray_directions(float(ray_step))
+    segm = _int32_map(img_objects)
+    if segm is not None and place == 'device':
+        count, labels, moments, centres, rays = _hip.object_shapes(segm, directions, OBJECT_SHAPES_CAPACITY)
+        if labels is not None:
+            return labels, moments, centres, rays
+    return _object_shape_rays_host(np.asarray(img_objects) if segm is None else segm, directions)
+
+
+def compute_object_shapes(list_img_objects, ray_step=5, interp_order=3, smooth_coef=0, shift_method='phase', on=None):
+    """ray distances and rotation of every object of every annotated map, objects of all maps one after the other (reference
+    :289-331; its example is in tests/test_object_shapes_reference_host.py): :func:`object_shape_rays` per map -- one device call -- then the
+    fill, smoothing and rotation of :func:`compute_segm_object_shape` per object on the host
+
+    :param list(ndarray) list_img_objects: annotated maps
+    :param int ray_step: angular step of the rays in degrees
+    :param int interp_order: how rays that left the image are filled in; None: not at all
+    :param float smooth_coef: sigma of the smoothing along the angle
+    :param str shift_method: 'phase' or 'max'
+    :param str on: ``'device'``, ``'host'`` or None (``IMSEGM_OBJECT_SHAPES_ON``)
+    :return tuple(list(list(float)),list(float)): rays, rotations
+    """
+    list_rays, list_shifts = [], []
+    for img_objects in list_img_objects:
+        for raw in object_shape_rays(img_objects, ray_step, on)[3]:
+            rays, shift = _finish_rays(raw, interp_order, smooth_coef, shift_method, _shift_rays_double)
+            list_rays.append(rays)
+            list_shifts.append(shift)
+    return list_rays, list_shifts
+
+
+def compute_cumulative_distrib(means, stds, weights, max_dist):
+    """inverse cumulative distribution of the ray length per direction: the weighted normal cdfs of the components at the
+    distances 0 .. int(max_dist), stretched to [0, 1] and turned over, plus 1e-9 (reference :334-361), all directions and samples at
+    once; the components are added in their order
+
+    :param ndarray means: [components, directions]
+    :param ndarray stds: [components, directions]
+    :param ndarray weights: [components]
+    :param float max_dist: the largest distance of the table
+    :return ndarray: [directions, int(max_dist) + 1]
+    """
+    means, stds = np.asarray(means), np.asarray(stds)
+    samples = np.arange(int(max_dist) + 1)
+    cdf = np.zeros((means.shape[1], int(max_dist + 1)))
+    for j, weight in enumerate(weights):
+        cdf += stats.norm.cdf(samples[None, :], means[j][:, None], stds[j][:, None]) * weight
+    low, high = cdf.min(axis=1, keepdims=True), cdf.max(axis=1, keepdims=True)
+    cdf = (cdf - low) / (high - low)
+    return 1. - cdf + 1e-9
+
+
+def _cdf_of_full_mixture(means, covariances, weights):
+    """the table of :func:`transform_rays_model_cdf_mixture` from the fitted attributes (:393-400)"""
+    means, covariances = np.asarray(means), np.asarray(covariances)
+    max_dist = np.max([[m[i] + np.sqrt(c[i, i]) for i in range(len(m))] for m, c in zip(means, covariances)])
+    stds = np.sqrt(abs(covariances))[:, np.eye(means.shape[1], dtype=bool)]
+    return compute_cumulative_distrib(means, stds, weights, max_dist)
+
+
+def _mean_cdfs_of_diag_mixture(means, covariances, slic_size):
+    """(mean rays, table) per component of a mixture with diagonal covariances (:426-436)"""
+    list_mean_cdf = []
+    for mean, covar in zip(means, covariances):
+        std = np.sqrt(covar + 1) * 2 + slic_size
+        mean = ndimage.gaussian_filter1d(mean, 1)
+        std = ndimage.gaussian_filter1d(std, 1)
+        max_dist = np.max(mean + 2 * std)
+        cdist = compute_cumulative_distrib(np.array([mean]), np.array([std]), np.array([1]), max_dist)
+        list_mean_cdf.append((mean.tolist(), cdist))
+    return list_mean_cdf
+
+
+def _mean_cdfs_of_clusters(list_rays, centres, labels):
+    """(mean rays, table) per cluster of a k-means fit (:459-468)"""
+    list_mean_cdf = []
+    for lb, mean in enumerate(centres):
+        std = np.std(np.asarray(list_rays)[labels == lb], axis=0)
+        mean = ndimage.gaussian_filter1d(mean, 1)
+        std = ndimage.gaussian_filter1d(std, 1)
+        std = (std + 1) * 5.
+        max_dist = np.max(mean + 2 * std)
+        cdist = compute_cumulative_distrib(np.array([mean]), np.array([std]), np.array([1]), max_dist)
+        list_mean_cdf.append((mean.tolist(), cdist))
+    return list_mean_cdf
+
+
+def _cdf_of_clusters(list_rays, labels, centres=None):
+    """one table from a clustering of the rays (:496-509, :542-553): per cluster the mean -- the smoothed mean of its members, or
+    the given centre -- and the standard deviation of its members plus 1, weighted by the share of the cluster"""
+    rays, labels = np.asarray(list_rays), np.asarray(labels)
+    present = np.unique(labels)
+    means = np.zeros((len(present), rays.shape[1])) if centres is None else np.asarray(centres)
+    stds = np.zeros((len(means), rays.shape[1]))
+    for i, lb in enumerate(present):
+        if centres is None:
+            means[i, :] = np.mean(rays[labels == lb], axis=0)
+            means[i, :] = ndimage.gaussian_filter1d(means[i, :], 1)
+        stds[i, :] = np.std(rays[labels == lb], axis=0)
+    stds += 1
+    weights = np.bincount(labels) / float(len(labels))
+    max_dist = np.max([[m[i] + c[i] for i in range(len(m))] for m, c in zip(means, stds)])
+    return compute_cumulative_distrib(means, stds, weights, max_dist)
+
+
+def transform_rays_model_cdf_mixture(list_rays, coef_components=1):
+    """a Bayesian Gaussian mixture of the ray vectors, with as many components as mean shift finds clusters times
+    ``coef_components``, and its cumulative table (reference :364-401).  The fits are scikit-learn's on the host.
+
+    :return tuple(BayesianGaussianMixture,list(list(float))): mixture, table [directions, distances]
+    """
+    rays = np.array(list_rays)
+    ms = cluster.MeanShift()
+    ms.fit(rays)
+    nb_components = int(len(np.unique(ms.labels_)) * coef_components)
+    mm = mixture.BayesianGaussianMixture(n_components=nb_components)
+    mm.fit(rays, ms.labels_)
+    covs = mm.covariances if hasattr(mm, 'covariances') else mm.covariances_
+    return mm, _cdf_of_full_mixture(mm.means_, covs, mm.weights_).tolist()
+
+
+def transform_rays_model_sets_mean_cdf_mixture(list_rays, nb_components=5, slic_size=15):
+    """a Bayesian Gaussian mixture with diagonal covariances and, per component, its smoothed mean rays with a table of their own
+    (reference :404-438)
+
+    :return tuple(BayesianGaussianMixture,list(tuple(list(float),ndarray))): mixture, [(mean rays, table)]
+    """
+    rays = np.array(list_rays)
+    mm = mixture.BayesianGaussianMixture(n_components=nb_components, covariance_type='diag')
+    mm.fit(rays)
+    return mm, _mean_cdfs_of_diag_mixture(mm.means_, mm.covariances_, slic_size)
+
+
+def transform_rays_model_sets_mean_cdf_kmeans(list_rays, nb_components=5):
+    """k-means of the ray vectors and, per cluster, its smoothed centre with a table of its own (reference :441-470)
+
+    :return tuple(KMeans,list(tuple(list(float),ndarray))): k-means, [(mean rays, table)]
+    """
+    rays = np.array(list_rays)
+    kmeans = cluster.KMeans(nb_components)
+    kmeans.fit(rays)
+    return kmeans, _mean_cdfs_of_clusters(list_rays, kmeans.cluster_centers_, kmeans.labels_)
+
+
+def transform_rays_model_cdf_spectral(list_rays, nb_components=5):
+    """spectral clustering of the ray vectors and one table of the clusters (reference :473-510)
+
+    :return tuple(SpectralClustering,list(list(float))): clustering, table
+    """
+    rays = np.array(list_rays)
+    sc = cluster.SpectralClustering(nb_components)
+    sc.fit(rays)
+    return sc, _cdf_of_clusters(list_rays, sc.labels_).tolist()
+
+
+def transform_rays_model_cdf_kmeans(list_rays, nb_components=None):
+    """k-means of the ray vectors -- with as many clusters as mean shift finds when ``nb_components`` is not given -- and one table
+    of the clusters (reference :513-554)
+
+    :return tuple(KMeans,list(list(float))): k-means, table
+    """
+    rays = np.array(list_rays)
+    if not nb_components:
+        ms = cluster.MeanShift()
+        ms.fit(rays)
+        nb_components = len(np.unique(ms.labels_))
+        kmeans = cluster.KMeans(nb_components)
+        kmeans.fit(rays, ms.labels_)
+    else:
+        kmeans = cluster.KMeans(nb_components)
+        kmeans.fit(rays)
+    return kmeans, _cdf_of_clusters(list_rays, kmeans.labels_, kmeans.cluster_centers_).tolist()
+
+
+def transform_rays_model_cdf_histograms(list_rays, nb_bins=10):
+    """one cumulative histogram per direction from all measured rays, read at integer bin centres (reference :557-588; its example
+    is in tests/test_object_shapes_reference_host.py)
+
+    :param list(list(int)) list_rays: integer ray lengths, one list per object
+    :param int nb_bins: bins of the histogram of a direction
+    :return list(list(float)): table [directions, max + 1]
+    """
+    rays = np.array(list_rays)
+    max_dist = np.max(rays)
+    list_chist = []
+    for i in range(rays.shape[1]):
+        cum = np.zeros(max_dist + 1)
+        hist, bin_edges = np.histogram(rays[:, i], nb_bins)
+        hist = hist.astype(float) / np.sum(hist)
+        bin_edges = bin_edges.astype(int)
+        bins = ((bin_edges[1:] + bin_edges[:-1]) / 2).astype(int)
+        cum[:bins[0]] = 1
+        for j, edge in enumerate(bins):
+            cum[edge:] = cum[edge - 1] - hist[j]
+        list_chist.append(cum.tolist())
+    return list_chist
 
 
 def compute_data_costs_points(slic, slic_prob_fg, centres, labels):
