@@ -742,7 +742,9 @@ class Image2D(object):
 
         :return dict: 'segm' (H x W int32), 'soft' (H x W x C), 'graph_labels' (K), 'proba' (K x C) as requested, plus
             with ``debug`` the graph-cut terms ('edges', 'edge_weights', 'edge_weights_int', 'unary', 'unary_int',
-            'centres', 'energy')"""
+            'centres', 'energy').  With ``debug`` the whole call runs a second time when the label map has more edges than
+            the debug arrays were sized for (3 K + 64, volumes 16 K + 64: a map that is no planar partition), with arrays of
+            the size the first run reported; without ``debug`` it is always one call"""
         code = EDGE_TYPES.get(edge_type)
         if code is None:
             raise ValueError('edge type %r is not evaluated on the device' % (edge_type, ))
@@ -794,18 +796,26 @@ class Image2D(object):
             dbg.keep_soft_on_device = int(bool(keep_soft_on_device))
             dbg.segm_u8, dbg.soft_f32 = int(segm_u8), int(soft_f32)
         if debug:
-            cap = (16 if len(self.shape) == 3 else 3) * k + 64
             ndim = len(self.shape)
-            out.update(edges=np.empty((cap, 2), np.int32), edge_weights=np.empty(cap), edge_weights_int=np.empty(cap, np.int32),
-                       unary=np.empty((k, nc)), unary_int=np.empty((k, nc), np.int32), centres=np.empty((k, ndim)),
+            out.update(unary=np.empty((k, nc)), unary_int=np.empty((k, nc), np.int32), centres=np.empty((k, ndim)),
                        energy=np.zeros(1, np.int64))
-            dbg.edge_capacity = cap
-            for name in ('edges', 'edge_weights', 'edge_weights_int', 'unary', 'unary_int', 'centres', 'energy'):
+            for name in ('unary', 'unary_int', 'centres', 'energy'):
                 setattr(dbg, name, _ptr(out[name]))
-        _check(load_library().imsegm_image2d_segment(
-            self._h, C.byref(gmm.params) if gmm is not None else None, _ptr(pr), nc, _ptr(pairwise), code, float(edge_cost),
-            int(bool(use_graphcut)), _ptr(cl), _ptr(out.get('segm')), _ptr(out.get('soft')), _ptr(out.get('graph_labels')),
-            _ptr(out.get('proba')), C.byref(dbg) if dbg is not None else None))
+        cap = (16 if len(self.shape) == 3 else 3) * k + 64
+        while True:
+            if debug:
+                out.update(edges=np.empty((cap, 2), np.int32), edge_weights=np.empty(cap), edge_weights_int=np.empty(cap, np.int32))
+                dbg.edge_capacity = cap
+                for name in ('edges', 'edge_weights', 'edge_weights_int'):
+                    setattr(dbg, name, _ptr(out[name]))
+            _check(load_library().imsegm_image2d_segment(
+                self._h, C.byref(gmm.params) if gmm is not None else None, _ptr(pr), nc, _ptr(pairwise), code, float(edge_cost),
+                int(bool(use_graphcut)), _ptr(cl), _ptr(out.get('segm')), _ptr(out.get('soft')), _ptr(out.get('graph_labels')),
+                _ptr(out.get('proba')), C.byref(dbg) if dbg is not None else None))
+            # (a label map that is no planar partition has more edges than the debug arrays were sized for: once more, as graph())
+            if not debug or dbg.n_edges <= cap:
+                break
+            cap = dbg.n_edges
         if debug:
             ne = dbg.n_edges
             for name in ('edges', 'edge_weights', 'edge_weights_int'):
