@@ -775,6 +775,46 @@ IMSEGM_API int imsegm_object_shapes(imsegm_ctx *ctx, const int32_t *segm, int he
                                     int n_angles, int max_objects, int *n_objects_out, int32_t *labels_out, int64_t *moments_out,
                                     int32_t *centres_out, float *rays_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the
+ * nearest exactly-coloured pixel (imsegm/annotation.py, the module behind handling_annotations/run_image_color_quantization.py,
+ * run_image_convert_label_color.py, run_overlap_images_segms.py and run_segm_annot_inpaint.py); csrc/annotation.hip.  Integers
+ * only: same call, same bytes.  Images are interleaved uint8 (height x width x 3), label maps int32, colour tables n_colors x 3
+ * uint8 with 1 <= n_colors <= IMSEGM_ANNOT_MAX_COLORS.  All arrays are host arrays.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_ANNOT_MAX_COLORS 256        /* entries of a colour table: it lives in LDS as one packed word per colour */
+#define IMSEGM_ANNOT_MATCH_EXACT 0         /* out: int32 per pixel, labels[k] of the colour the pixel equals, -1 for none */
+#define IMSEGM_ANNOT_MATCH_NEAREST 1       /* out: int32 per pixel, the index of the nearest colour */
+#define IMSEGM_ANNOT_MATCH_NEAREST_COLOR 2 /* out: uint8 x 3 per pixel, the nearest colour itself */
+/* One pass over n_pixels pixels against the table.  EXACT replaces the loop of convert_img_colors_to_labels_reverted
+ * (annotation.py:113-121) and the labelling loop of quantize_image_nearest_pixel (:311-316): when several entries hold the pixel's
+ * colour the LAST one's label is taken (later colours overwrite); labels (none negative) may be NULL for labels[k] = k;
+ * *unmatched_out (may be NULL) = the number of pixels without an entry (:122 compares it against the pixel count).  NEAREST replaces image_color_2_labels
+ * (:245-248) and NEAREST_COLOR quantize_image_nearest_color (:271-275): the first entry with the smallest
+ * |r - r_k| + |g - g_k| + |b - b_k| (np.argmin over the colours in table order).  Returns -1 (no launch) for n_pixels < 1, a table
+ * size outside [1, IMSEGM_ANNOT_MAX_COLORS] or an unknown mode. */
+IMSEGM_API int imsegm_annot_match(imsegm_ctx *ctx, const uint8_t *image, size_t n_pixels, const uint8_t *colors, const int32_t *labels,
+                                  int n_colors, int mode, void *out, int64_t *unmatched_out);
+/* Replaces convert_img_labels_to_colors (:146-160): image_out[i] = table[labels[i] - min_label] for a table of n_table colours with
+ * one `present` byte per entry (0: the label has no colour).  A pixel whose label lies outside the table or has no colour makes the
+ * call return -1 with image_out untouched (:146-147 raises). */
+IMSEGM_API int imsegm_annot_paint(imsegm_ctx *ctx, const int32_t *labels, size_t n_pixels, int min_label, int n_table,
+                                  const uint8_t *table, const uint8_t *present, uint8_t *image_out);
+/* Replaces PIL's Image.getcolors behind unique_image_colors (:61-67) and image_frequent_colors (:184-185): the distinct colours of
+ * the image as packed keys r << 16 | g << 8 | b in ascending order with their pixel counts.  *n_colors_out = their number; keys_out
+ * and counts_out (capacity entries each; NULL with capacity 0 to count only) are written only when that number fits. */
+IMSEGM_API int imsegm_annot_color_hist(imsegm_ctx *ctx, const uint8_t *image, size_t n_pixels, int capacity, int *n_colors_out,
+                                       uint32_t *keys_out, uint32_t *counts_out);
+/* Replaces image_inpaint_pixels (:279-286, scipy's NearestNDInterpolator over all valid pixels) on a label map: a pixel equal to -1
+ * is invalid and gets the label of the valid pixel at the smallest squared Euclidean distance (exact, uint32); among several at
+ * that distance the one with the smallest row-major index.  Every other value is a label and stays.  Returns -1 with labels_out
+ * untouched for a map without a valid pixel, height^2 + width^2 > 2^32 - 1 or more than 65535 rows.  labels_out may be labels. */
+IMSEGM_API int imsegm_annot_nearest_valid(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int32_t *labels_out);
+/* Replaces quantize_image_nearest_pixel (:308-321): EXACT match with labels[k] = k, imsegm_annot_nearest_valid and the gather of
+ * colors[label] per pixel with ONE upload of the image and ONE download.  Errors as the two calls; image_out may be image. */
+IMSEGM_API int imsegm_annot_quantize_nearest_pixel(imsegm_ctx *ctx, const uint8_t *image, int height, int width, const uint8_t *colors,
+                                                   int n_colors, uint8_t *image_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,11 @@ _SIGNATURES = {
     'imsegm_rg_greedy_step': (C.c_int, [_vp, _vp, C.c_int, _vp, _ip, _vp, _vp, _vp]),
     'imsegm_rg_criterion': (C.c_int, [_vp, _vp, _vp, _vp]),
     'imsegm_object_shapes': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _ip, _vp, _vp, _vp, _vp]),
+    'imsegm_annot_match': (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, C.POINTER(C.c_int64)]),
+    'imsegm_annot_paint': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp]),
+    'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
+    'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -1830,6 +1835,105 @@ def object_shapes(segm, directions, max_objects=1024, ctx=None):
     _check(status)
     n = count.value
     return n, labels[:n], moments[:n], centres[:n], rays[:n]
+
+
+#: ``IMSEGM_ANNOT_MAX_COLORS``: entries of a colour table of the ``imsegm_annot_*`` calls
+ANNOT_MAX_COLORS = 256
+#: modes of ``imsegm_annot_match``
+ANNOT_MATCH_EXACT, ANNOT_MATCH_NEAREST, ANNOT_MATCH_NEAREST_COLOR = 0, 1, 2
+
+
+def _annot_image(image):
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or not image.flags.c_contiguous or image.size == 0:
+        raise ValueError('the image must be a non-empty C-contiguous uint8 array [H, W, 3]')
+    return image
+
+
+def _annot_colors(colors):
+    colors = np.ascontiguousarray(colors, dtype=np.uint8).reshape(-1, 3)
+    if not 1 <= len(colors) <= ANNOT_MAX_COLORS:
+        raise ValueError('a colour table holds 1 to %i colours' % ANNOT_MAX_COLORS)
+    return colors
+
+
+def annot_match(image, colors, labels=None, mode=ANNOT_MATCH_EXACT, ctx=None):
+    """``imsegm_annot_match`` on a uint8 image [H, W, 3] and a table of colours uint8 [K, 3].  Exact: (int32 [H, W] with ``labels[k]``
+    -- none negative, default k -- of the last colour the pixel equals and -1 for none, number of such pixels); nearest: the index of
+    the first colour at the smallest L1 distance, int32 [H, W]; nearest colour: that colour, uint8 [H, W, 3]"""
+    image, colors = _annot_image(image), _annot_colors(colors)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+        if len(labels) != len(colors):
+            raise ValueError('one label per colour')
+    out = np.empty(image.shape if mode == ANNOT_MATCH_NEAREST_COLOR else image.shape[:2], dtype=np.uint8 if mode == ANNOT_MATCH_NEAREST_COLOR else np.int32)
+    unmatched = C.c_int64(0)
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_annot_match(ctx._h, _ptr(image), image.shape[0] * image.shape[1], _ptr(colors), _ptr(labels), len(colors),
+                                             int(mode), _ptr(out), C.byref(unmatched)))
+    return (out, int(unmatched.value)) if mode == ANNOT_MATCH_EXACT else out
+
+
+def annot_paint(labels, min_label, table, present=None, out=None, ctx=None):
+    """``imsegm_annot_paint``: the C-contiguous int32 map ``labels`` through the colours ``table`` uint8 [T, 3] of the labels
+    ``min_label .. min_label + T - 1`` (``present`` uint8 [T]: 0 marks a label without a colour): uint8 labels.shape + (3,).  A label of
+    the map without a colour raises ``HipError`` and leaves ``out`` as it came."""
+    if labels.dtype != np.int32 or not labels.flags.c_contiguous or labels.size == 0:
+        raise ValueError('the label map must be a non-empty C-contiguous int32 array')
+    table = _annot_colors(table)
+    present = np.ones(len(table), dtype=np.uint8) if present is None else np.ascontiguousarray(present, dtype=np.uint8).ravel()
+    if len(present) != len(table):
+        raise ValueError('one present flag per colour')
+    if out is None:
+        out = np.empty(labels.shape + (3, ), dtype=np.uint8)
+    elif out.dtype != np.uint8 or out.shape != labels.shape + (3, ) or not out.flags.c_contiguous:
+        raise ValueError('out must be a C-contiguous uint8 array of the shape of the map + (3,)')
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_annot_paint(ctx._h, _ptr(labels), labels.size, int(min_label), len(table), _ptr(table), _ptr(present),
+                                             _ptr(out)))
+    return out
+
+
+def annot_color_hist(image, capacity=None, ctx=None):
+    """``imsegm_annot_color_hist``: (keys uint32 [n] ascending, ``r << 16 | g << 8 | b``; counts uint32 [n]) of the distinct colours of
+    a uint8 image [H, W, 3] in one call: the result arrays have room for ``capacity`` colours, by default for as many as the image
+    can hold (one per pixel, 2^24 at the most; pages nothing is written to cost nothing).  An image with more colours than an
+    explicit ``capacity`` raises ``ValueError``."""
+    image = _annot_image(image)
+    ctx = ctx or default_context()
+    n_pixels, n = image.shape[0] * image.shape[1], C.c_int(0)
+    if capacity is None:
+        capacity = min(n_pixels, 1 << 24)
+    keys, counts = np.empty(capacity, dtype=np.uint32), np.empty(capacity, dtype=np.uint32)
+    _check(load_library().imsegm_annot_color_hist(ctx._h, _ptr(image), n_pixels, int(capacity), C.byref(n), _ptr(keys), _ptr(counts)))
+    if n.value > capacity:
+        raise ValueError('the image holds %i colours, more than the %i asked for' % (n.value, capacity))
+    return keys[:n.value].copy(), counts[:n.value].copy()
+
+
+def annot_nearest_valid(labels, out=None, ctx=None):
+    """``imsegm_annot_nearest_valid``: the C-contiguous 2-D int32 map with every pixel equal to -1 given the label of the nearest
+    other pixel (squared Euclidean distance, the smallest row-major index among equals).  A map without such a pixel raises
+    ``HipError`` and leaves ``out`` as it came."""
+    if labels.ndim != 2 or labels.dtype != np.int32 or not labels.flags.c_contiguous or labels.size == 0:
+        raise ValueError('the label map must be a non-empty C-contiguous 2-D int32 array')
+    if out is None:
+        out = np.empty_like(labels)
+    elif out.dtype != np.int32 or out.shape != labels.shape or not out.flags.c_contiguous:
+        raise ValueError('out must be a C-contiguous int32 array of the shape of the map')
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_annot_nearest_valid(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], _ptr(out)))
+    return out
+
+
+def annot_quantize_nearest_pixel(image, colors, ctx=None):
+    """``imsegm_annot_quantize_nearest_pixel``: every pixel of the uint8 image [H, W, 3] replaced by the colour of the nearest pixel
+    that has exactly one of ``colors`` uint8 [K, 3] (itself when it has one): uint8 [H, W, 3]"""
+    image, colors = _annot_image(image), _annot_colors(colors)
+    out = np.empty_like(image)
+    ctx = ctx or default_context()
+    _check(load_library().imsegm_annot_quantize_nearest_pixel(ctx._h, _ptr(image), image.shape[0], image.shape[1], _ptr(colors), len(colors),
+                                                              _ptr(out)))
+    return out
 
 
 def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):
