@@ -140,6 +140,13 @@ IMSEGM_API long imsegm_debug_gc_grid_fallbacks(void);
 /* Diagnostic (no reference counterpart): the one-workgroup exclusive prefix sum that the labelling, graph and compaction stages share
  * (csrc/scan.hip), on n host values: host_out[i] = host_in[0] + ... + host_in[i - 1], *total = the sum of all n (tests). */
 IMSEGM_API int imsegm_debug_exclusive_scan(const int32_t *host_in, int n, int32_t *host_out, int32_t *total);
+/* Diagnostics (no reference counterpart) for the tests of reused scratch: fill every device allocation the context / the session
+ * owns with the 32-bit `word`, over its whole capacity, and put the host-side bookkeeping of the object back to that of a new one
+ * (no table of a mixture fit; no image, label map, converted image, filter bank, feature table or prepared graph).  After the call
+ * the object differs from a new one only in that its buffers keep their capacity and hold `word`.  *bytes_out = bytes filled.
+ * The page-locked staging memory is left alone; batch and region-growing handles own their device memory themselves. */
+IMSEGM_API int imsegm_debug_poison_context(imsegm_ctx *ctx, uint32_t word, size_t *bytes_out);
+IMSEGM_API int imsegm_debug_image2d_poison(imsegm_image2d *img, uint32_t word, size_t *bytes_out);
 /* Replaces skimage.segmentation._slic._enforce_label_connectivity_cython(segments, min_size, max_size, start_label)
  * (scikit-image 0.18; the connectivity pass of skimage.segmentation.slic, reached from imsegm/superpixels.py:61-63 and
  * :104-106 with enforce_connectivity=True) on a label map given by the caller: labels = host int32, one value per

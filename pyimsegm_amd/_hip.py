@@ -121,6 +121,8 @@ _SIGNATURES = {
     'imsegm_debug_slic_sweep_runs': (C.c_int, [_vp, _vp]),
     'imsegm_debug_gc_grid_fallbacks': (C.c_long, []),
     'imsegm_debug_exclusive_scan': (C.c_int, [_vp, C.c_int, _vp, _ip]),
+    'imsegm_debug_poison_context': (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_size_t)]),
+    'imsegm_debug_image2d_poison': (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_size_t)]),
     'imsegm_assume_bg_on_boundary': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _ip]),
     'imsegm_image2d_all_finite': (C.c_int, [_vp, _ip]),
     'imsegm_image2d_lm_features': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _vp]),
@@ -332,6 +334,13 @@ class Context(object):
         ms, n = C.c_double(0), C.c_int(0)
         _check(load_library().imsegm_ctx_profile_get(self._h, PROFILE_GROUPS[group], C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def poison(self, word):
+        """diagnostic (``imsegm_debug_poison_context``): fill the context's device scratch with the 32-bit ``word`` over its whole
+        capacity and forget the resident table of a mixture fit -- a new context whose buffers hold ``word``; returns the bytes filled"""
+        nbytes = C.c_size_t(0)
+        _check(load_library().imsegm_debug_poison_context(self._h, int(word) & 0xffffffff, C.byref(nbytes)))
+        return int(nbytes.value)
 
     def close_idle_sessions(self):
         """give the device memory of the sessions kept for reuse back (a volume session owns ~70 bytes per voxel)"""
@@ -658,6 +667,16 @@ class Image2D(object):
         _check(load_library().imsegm_image2d_upload(self._h, _ptr(image), _DTYPES[image.dtype]))
         self._uploaded = image          # a page-locked source is read asynchronously: keep it alive until the next sync
         return self
+
+    def poison(self, word):
+        """diagnostic (``imsegm_debug_image2d_poison``): fill every device buffer of the session with the 32-bit ``word`` over its
+        whole capacity and forget the image, the label map and everything derived from them -- a new session whose buffers hold
+        ``word``; returns the bytes filled"""
+        nbytes = C.c_size_t(0)
+        _check(load_library().imsegm_debug_image2d_poison(self._h, int(word) & 0xffffffff, C.byref(nbytes)))
+        self.n_labels = 0
+        self._uploaded = None
+        return int(nbytes.value)
 
     def run_color(self, image, n_segments, compactness, gmm, pairwise, edge_type='model', feature_flags=(True, True, True),
                   sigma=1., normalize=2, max_iter=10, start_label=0, slic_zero=False, edge_cost=1., use_graphcut=True,

@@ -276,6 +276,7 @@ int imsegm_image2d_slic(imsegm_image2d *im, int minmax_normalize, int n_segments
         used_persistent = false;
     }
     ctx->end(sp_all);
+    im->slic_ran = true;
     im->n_labels = n_labels;
     im->have_labels = true;
     im->labels_connected = false;
@@ -378,7 +379,7 @@ int imsegm_image2d_get_lab(imsegm_image2d *im, double *lab_out)
 {
     if (!im || bind(im->ctx)) return -1;
     if (wrong_kind(im, false)) return -1;
-    if (im->labA.cap < 3 * im->n * 8) {
+    if (!im->slic_ran || im->labA.cap < 3 * im->n * 8) {
         set_error("slic has not been run");
         return -1;
     }
@@ -392,7 +393,7 @@ int imsegm_image2d_get_pre_scalars(imsegm_image2d *im, double out[3])
 {
     if (!im || bind(im->ctx)) return -1;
     if (wrong_kind(im, false)) return -1;
-    if (!out || im->labA.cap < 3 * im->n * 8 || im->small.cap < 4096) {
+    if (!out || !im->slic_ran || im->labA.cap < 3 * im->n * 8 || im->small.cap < 4096) {
         set_error("slic has not been run");
         return -1;
     }
@@ -405,7 +406,7 @@ int imsegm_image2d_get_pre_scalars(imsegm_image2d *im, double out[3])
 int imsegm_image2d_get_nearest(imsegm_image2d *im, int32_t *nearest_out)
 {
     if (!im || bind(im->ctx)) return -1;
-    if (im->nearest.cap < im->n * 4) {
+    if (!im->slic_ran || im->nearest.cap < im->n * 4) {
         set_error("slic has not been run");
         return -1;
     }

@@ -170,6 +170,7 @@ int imsegm_volume_slic(imsegm_image2d *im, int n_segments, double compactness, c
     ctx->end(sp_all);
     im->vol_pre_dtype = f32 ? IMSEGM_F32 : IMSEGM_F64;
     im->vol_K = K;
+    im->slic_ran = true;
     im->n_labels = n_labels;
     im->have_labels = true;
     im->labels_connected = enforce_connectivity != 0;

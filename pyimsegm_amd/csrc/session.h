@@ -173,6 +173,8 @@ struct imsegm_image2d {
     bool have_labels = false;
     bool labels_connected = false;              // the label map is what the connectivity pass wrote: every label > 0 is ONE 6-connected set
     bool tex_ready = false;
+    bool small_zeroed = false;                  // `small` has been cleared since it was allocated (ensure_small)
+    bool slic_ran = false;                      // a SLIC of this session has left its planes, assignment and scalars (the get_* of them)
     bool is_volume = false;
     double vol_off = 0.0, vol_scale = 1.0;      // intensity seen by the volume SLIC = (v + off) * scale
     int vol_pre_dtype = -1, vol_K = 0;          // the last imsegm_volume_slic: type of its plane in labB (IMSEGM_F32 / IMSEGM_F64), centroids
@@ -227,12 +229,14 @@ inline int bind(imsegm_ctx *ctx)
     return 0;
 }
 
-// the session's page of reduction words: zeroed once where it is allocated (launch_minmax leaves its words at zero, slic.hip)
+// the session's page of reduction words: zeroed once, by the first call that needs it (launch_minmax leaves its words at zero,
+// slic.hip).  `small_zeroed` and not the capacity says whether that has happened: what hipMalloc returns is not zero by contract
 inline int ensure_small(imsegm_image2d *im)
 {
-    if (im->small.cap >= 4096) return 0;
+    if (im->small_zeroed && im->small.cap >= 4096) return 0;
     if (im->small.ensure(4096)) return -1;
     HIP_TRY(hipMemsetAsync(im->small.p, 0, 4096, im->ctx->stream));
+    im->small_zeroed = true;
     return 0;
 }
 
