@@ -289,6 +289,27 @@ def device_count():
     return _device_count[pid]
 
 
+def resolve_place(on, variable, raise_without_device):
+    """Where a call with the keyword ``on=None | 'host' | 'device'`` runs: ``(place, explicit)``.  ``on=None`` reads the environment
+    variable ``variable`` (unset or empty: nothing asked); any other value raises ValueError.  With nothing asked the place is
+    'device' when a device is present and 'host' otherwise, and ``explicit`` is False: the caller may still have a default of its
+    own.  'device' asked for without a device raises HipUnavailableError here when ``raise_without_device``; otherwise 'device' is
+    handed back without a look at the devices, and the call fails where it needs one."""
+    if on is None:
+        on = os.environ.get(variable) or None
+    if on not in (None, 'host', 'device'):
+        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
+    if on == 'host' or (on == 'device' and not raise_without_device):
+        return on, True
+    try:
+        present = device_count() > 0
+    except HipUnavailableError:
+        present = False
+    if not present and on == 'device':
+        raise HipUnavailableError('no HIP device is visible')
+    return ('device' if present else 'host'), on is not None
+
+
 def _ptr(arr):
     return None if arr is None else arr.ctypes.data_as(_vp)
 

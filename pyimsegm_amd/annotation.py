@@ -11,8 +11,8 @@ defaults, result dtypes and errors, the per-pixel work on the device (csrc/annot
 * ``image_inpaint_pixels`` -- ``imsegm_annot_nearest_valid``, an exact nearest-feature transform; ``quantize_image_nearest_pixel`` --
   exact match, transform and colour gather in one call (``imsegm_annot_quantize_nearest_pixel``).
 
-Every pixel function takes ``on=None | 'host' | 'device'`` (environment: ``IMSEGM_ANNOTATION_ON``).  ``'host'`` runs the numpy / scipy
-statement of the same definition, and so does -- whatever ``on`` says -- every call the device does not take: an image that is not
+Every pixel function takes ``on=None | 'host' | 'device'`` (environment: ``IMSEGM_ANNOTATION_ON``; the rules of the switch are
+``_hip.resolve_place``, and ``'device'`` without a device raises).  ``'host'`` runs the numpy / scipy statement of the same definition, and so does -- whatever ``on`` says -- every call the device does not take: an image that is not
 ``[H, W, 3]`` or whose values are not integers in 0 .. 255, colours with a component outside 0 .. 255 or more than
 ``IMSEGM_ANNOT_MAX_COLORS`` = 256 of them, labels that are not non-negative int32 integers, a map beyond the uint32 limit of the
 squared distances (``H^2 + W^2 > 2^32 - 1``) or with more than 65535 rows.  With ``on=None`` the functions named in
@@ -58,25 +58,10 @@ HOST_BY_DEFAULT = frozenset()
 
 
 def _place(on, name):
-    """'host' or 'device' for the public function ``name`` from the ``on`` keyword, the environment variable IMSEGM_ANNOTATION_ON,
-    the presence of a device and -- when neither says anything -- ``HOST_BY_DEFAULT``"""
-    if on is None:
-        on = os.environ.get('IMSEGM_ANNOTATION_ON') or None
-    if on not in (None, 'host', 'device'):
-        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
-    if on == 'host':
-        return 'host'
-    try:
-        present = _hip.device_count() > 0
-    except _hip.HipUnavailableError:
-        present = False
-    if not present:
-        if on == 'device':
-            raise _hip.HipUnavailableError('no HIP device is visible')
-        return 'host'
-    if on is None and name in HOST_BY_DEFAULT:
-        return 'host'
-    return 'device'
+    """'host' or 'device' for the public function ``name``: ``_hip.resolve_place`` on IMSEGM_ANNOTATION_ON ('device' without a
+    device raises) and -- when neither the keyword nor the variable says anything -- ``HOST_BY_DEFAULT``"""
+    place, explicit = _hip.resolve_place(on, 'IMSEGM_ANNOTATION_ON', True)
+    return place if explicit or name not in HOST_BY_DEFAULT else 'host'
 
 
 # ------------------------------------------------------------------------------------------------

@@ -233,26 +233,17 @@ __global__ void __launch_bounds__(256)
 k_annot_hist_gather(const uint32_t *__restrict__ bins, const uint32_t *__restrict__ offsets, uint32_t *__restrict__ keys_out,
                     uint32_t *__restrict__ counts_out)
 {
-    __shared__ uint32_t s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t start = (size_t)blockIdx.x * ANNOT_HIST_CHUNK;
     uint32_t base = offsets[blockIdx.x];
     if (offsets[blockIdx.x + 1] == base) return;       // (uniform over the workgroup: no bin of this chunk is in use)
     for (int it = 0; it < ANNOT_HIST_CHUNK / 256; ++it) {
         const size_t i = start + (size_t)it * 256 + threadIdx.x;
         const uint32_t count = bins[i];
-        const unsigned long long votes = __ballot(count != 0u);
-        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(votes);
-        __syncthreads();
-        uint32_t before = base;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
+        const uint32_t at = block_stable_slot(count != 0u, &base);
         if (count != 0u) {
-            const uint32_t at = before + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
             keys_out[at] = (uint32_t)i;
             counts_out[at] = count;
         }
-        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
     }
 }
 

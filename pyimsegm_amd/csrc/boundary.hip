@@ -14,6 +14,7 @@
 // the brute-force integer minimum, and scipy's distance_transform_edt (the same square root of the same integer), bit for bit.
 //
 // Squared distances are uint32: the caller refuses maps with H^2 + W^2 > 2^32 - 1 (launch_edt_* return an error, nothing wraps).
+#include "scan.h"
 #include "slic.h"
 
 namespace imsegm {
@@ -161,26 +162,17 @@ __global__ void __launch_bounds__(256)
 k_compact_gather(const uint8_t *__restrict__ mask, const uint32_t *__restrict__ d2, size_t n, int W, const uint32_t *__restrict__ offsets,
                  int32_t *__restrict__ points, double *__restrict__ dist)
 {
-    __shared__ uint32_t s_wave[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t start = (size_t)blockIdx.x * CP_CHUNK;
     uint32_t base = offsets[blockIdx.x];
     for (int it = 0; it < CP_ITEMS; ++it) {
         const size_t i = start + (size_t)it * 256 + threadIdx.x;
         const bool set = i < n && mask[i];
-        const unsigned long long votes = __ballot(set);
-        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(votes);
-        __syncthreads();
-        uint32_t before = base;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
+        const uint32_t at = block_stable_slot(set, &base);
         if (set) {
-            const uint32_t at = before + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
             points[2 * (size_t)at] = (int32_t)(i / (size_t)W);
             points[2 * (size_t)at + 1] = (int32_t)(i % (size_t)W);
             dist[at] = sqrt((double)d2[i]);
         }
-        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
     }
 }
 

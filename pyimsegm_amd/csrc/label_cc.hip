@@ -65,8 +65,7 @@ k_cc_init_rows(const int32_t *__restrict__ labels, int32_t *__restrict__ parent,
     const bool cont = lane_prev(l, -1) == l && lane > 1 && l != 0;          // continues a run that began inside this segment
     const unsigned long long starts = __ballot(mine && !cont);
     if (!mine) return;
-    const unsigned long long below = starts & ((2ULL << lane) - 1ULL);     // (lane <= 62)
-    const int start_lane = 63 - __clzll((long long)below);
+    const int start_lane = run_start_lane(starts, lane);                   // (lane <= 62)
     parent[row + x] = (int)(row + x) - (lane - start_lane);
 }
 

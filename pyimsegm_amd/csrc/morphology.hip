@@ -2,53 +2,27 @@
 //   split_segm_background_foreground     imsegm/ellipse_fitting.py:400-443 (scipy.ndimage binary_fill_holes, skimage.morphology
 //                                        opening with disk(r) for integer r)
 //   compute_ray_features_segm_2d         per centre on seg_bg ('up') and seg_fg ('down'), ellipse_fitting.py:385-390, :480-482,
-//                                        :531-533, :581 (the walk of k_ray_features_binary2d, natives.hip)
+//                                        :531-533, :581 (the walk of raywalk.h)
 // Integers only up to the ray walk: a pixel survives the erosion when no 0 of the image lies within dy^2 + dx^2 <= r^2 of it, and is
 // set by the dilation when a surviving pixel does; pixels outside the image never count ("Boundary points").
 #include "morphology.h"
+#include "raywalk.h"
 #include "unionfind.h"
 
 namespace imsegm {
 
 // ---- hole filling: one labelling of the zero pixels (segm <= 0), 4-connected -------------------------------------------------
-// A wave covers 64 consecutive pixels of a row (the segments start at multiples of 64 in every row).  Every zero pixel starts out
-// pointing at the first pixel of its run INSIDE its segment, so the unions that are left lie where a run crosses a segment and
-// where a run meets the row above for the first time.
+// The run rule of unionfind.h (run_label_init / run_label_merge); workgroup (c, y) covers pixels 256 c .. 256 c + 255 of row y.
+__device__ __forceinline__ bool holes_zero(int32_t l) { return l <= 0; }
+
 __global__ void __launch_bounds__(256) k_holes_init(const int32_t *__restrict__ segm, int32_t *__restrict__ parent, int W)
 {
-    const int lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const size_t row = (size_t)blockIdx.y * W;
-    const bool inx = x < W;
-    const bool zero = inx && segm[row + x] <= 0;
-    const unsigned long long z = __ballot(zero);
-    if (!inx) return;
-    int start = lane;
-    if (zero) {
-        const unsigned long long starts = z & ~(z << 1);
-        const unsigned long long below = starts & ((2ULL << lane) - 1ULL);
-        start = 63 - __clzll((long long)below);
-    }
-    parent[row + x] = (int)(row + x) - (lane - start);
+    run_label_init(segm, parent, blockIdx.y, blockIdx.x * 256 + threadIdx.x, W, holes_zero);
 }
 
-// p and the pixel above it are tied when p starts a run of its segment or the pixel above p - 1 is no zero: otherwise p - 1 is tied
-// to the pixel above it, which shares a run (and a segment) with the pixel above p
 __global__ void __launch_bounds__(256) k_holes_merge(const int32_t *__restrict__ segm, int32_t *parent, int W)
 {
-    const int lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    const size_t row = (size_t)y * W;
-    const bool inx = x < W;
-    const bool zero = inx && segm[row + x] <= 0;
-    const bool up = zero && y > 0 && segm[row - W + x] <= 0;
-    const bool up_any = inx && y > 0 && segm[row - W + x] <= 0;
-    const unsigned long long z = __ballot(zero), zu = __ballot(up_any);
-    if (!zero) return;
-    const int p = (int)(row + x);
-    const bool first = lane == 0 || !((z >> (lane - 1)) & 1ULL);
-    if (lane == 0 && x > 0 && segm[p - 1] <= 0) uf_union_pair(parent, p, p - 1);
-    if (up && (first || !((zu >> (lane - 1)) & 1ULL))) uf_union_pair(parent, p, p - W);
+    run_label_merge(segm, parent, blockIdx.y, blockIdx.x * 256 + threadIdx.x, W, holes_zero);
 }
 
 // the border pixels, one lane each: top row, bottom row, left column, right column
@@ -145,8 +119,8 @@ __global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ 
 }
 
 // ---- rays of all centres on both masks ----------------------------------------------------------------------------------------
-// blockIdx.y = 0: seg_bg with edge 'up', 1: seg_fg with edge 'down'; the walk is k_ray_features_binary2d's (natives.hip), the same
-// float32 / float64 operations in the same order.  One wave per (position, mask), one lane per angle.
+// blockIdx.y = 0: seg_bg with edge 'up', 1: seg_fg with edge 'down'; the walk is ray_walk (raywalk.h).  One wave per
+// (position, mask), one lane per angle.
 __global__ void __launch_bounds__(64)
 k_boundary_rays(const uint8_t *__restrict__ seg_bg, const uint8_t *__restrict__ seg_fg, int H, int W,
                 const int32_t *__restrict__ positions, int P, const float *__restrict__ grad, int A, float *__restrict__ rays_bg,
@@ -159,32 +133,11 @@ k_boundary_rays(const uint8_t *__restrict__ seg_bg, const uint8_t *__restrict__ 
     if (p >= P || !out) return;
     const int py = positions[2 * p], px = positions[2 * p + 1];
     const bool inside = py >= 0 && py < H && px >= 0 && px < W;
-    const uint8_t start = inside ? seg[(size_t)py * W + px] : 0;
-    const int diag = (int)sqrt((double)W * W + (double)H * H);
-    for (int a = threadIdx.x; a < A; a += blockDim.x) {
-        float res = -1.f;
-        if (start && edge == 1) {
-            res = 0.f;                                       // the position lies on the mask
-        } else if (inside) {
-            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
-            float pos0 = (float)py, pos1 = (float)px;
-            uint8_t last = start;
-            for (int it = 0; it < diag; ++it) {
-                pos0 += g0;
-                pos1 += g1;
-                const double r0 = round((double)pos0), r1 = round((double)pos1);
-                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
-                const uint8_t actual = seg[(size_t)(int)r0 * W + (int)r1];
-                if ((edge == 1 && actual) || (edge == -1 && last && !actual)) {
-                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
-                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
-                    break;
-                }
-                last = actual;
-            }
-        }
-        out[(size_t)p * A + a] = res;
-    }
+    auto on_mask = [&](int y, int x) -> bool { return seg[(size_t)y * W + x] != 0; };
+    const bool start = inside ? on_mask(py, px) : false;
+    const int diag = ray_walk_limit(H, W);
+    for (int a = threadIdx.x; a < A; a += blockDim.x)
+        out[(size_t)p * A + a] = ray_walk(py, px, inside, start, grad[2 * a], grad[2 * a + 1], H, W, diag, edge, on_mask);
 }
 
 int morph_size_ok(int H, int W)

@@ -3,6 +3,7 @@
 //   computeRayFeaturesBinary2d   features_cython.pyx:244-282                          (descriptors.py:1630-1660)
 // The reference calls them once per position from Python loops (compute_label_hist_proba, compute_ray_features_positions,
 // the region-growing and centre-detection tools); here one wave serves one position.
+#include "raywalk.h"
 #include "slic.h"
 
 namespace imsegm {
@@ -27,11 +28,9 @@ k_label_hist2d(const int16_t *__restrict__ segm, int H, int W, const int32_t *__
     }
 }
 
-// Ray features: from every position a ray per angle walks the binary segmentation in unit steps of the larger
-// direction component until it meets the searched edge ('up' = 1: first foreground pixel, 'down' = -1: first
-// background pixel after foreground); float32 arithmetic in the operation order of the .pyx (the per-angle direction
-// table -- sin / cos of the float32 angle divided by its larger component -- comes from the host, formed with the
-// same numpy calls the reference makes).  One wave per position, one lane per angle.
+// Ray features: from every position a ray per angle walks the binary segmentation until it meets the searched edge ('up' = 1:
+// first foreground pixel, 'down' = -1: first background pixel after foreground); the walk and its precision are ray_walk's
+// (raywalk.h), the per-angle direction table comes from the host.  One wave per position, one lane per angle.
 __global__ void __launch_bounds__(64)
 k_ray_features_binary2d(const int8_t *__restrict__ seg, int H, int W, const int32_t *__restrict__ positions, int P,
                         const float *__restrict__ grad, int A, int edge, float *__restrict__ out)
@@ -40,32 +39,11 @@ k_ray_features_binary2d(const int8_t *__restrict__ seg, int H, int W, const int3
     if (p >= P) return;
     const int py = positions[2 * p], px = positions[2 * p + 1];
     const bool inside = py >= 0 && py < H && px >= 0 && px < W;
-    const int8_t start = inside ? seg[(size_t)py * W + px] : 0;
-    const int diag = (int)sqrt((double)W * W + (double)H * H);
-    for (int a = threadIdx.x; a < A; a += blockDim.x) {
-        float res = -1.f;
-        if (start && edge == 1) {
-            res = 0.f;                                       // the position lies inside the border label
-        } else if (inside) {
-            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
-            float pos0 = (float)py, pos1 = (float)px;
-            int8_t last = start;
-            for (int it = 0; it < diag; ++it) {
-                pos0 += g0;
-                pos1 += g1;
-                const double r0 = round((double)pos0), r1 = round((double)pos1);
-                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
-                const int8_t actual = seg[(size_t)(int)r0 * W + (int)r1];
-                if ((edge == 1 && actual) || (edge == -1 && last && !actual)) {
-                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
-                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
-                    break;
-                }
-                last = actual;
-            }
-        }
-        out[(size_t)p * A + a] = res;
-    }
+    auto on_mask = [&](int y, int x) -> bool { return seg[(size_t)y * W + x] != 0; };
+    const bool start = inside ? on_mask(py, px) : false;
+    const int diag = ray_walk_limit(H, W);
+    for (int a = threadIdx.x; a < A; a += blockDim.x)
+        out[(size_t)p * A + a] = ray_walk(py, px, inside, start, grad[2 * a], grad[2 * a + 1], H, W, diag, edge, on_mask);
 }
 
 int launch_label_hist2d(const int16_t *segm, int H, int W, const int32_t *windows, int P, const int16_t *selem, int SH, int SW,

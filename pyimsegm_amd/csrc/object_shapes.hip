@@ -3,12 +3,13 @@
 // compute_segm_object_shape (:259-286) -- np.unique, scipy.ndimage.label with its default cross, ndimage.center_of_mass of every
 // `img == label` mask and computeRayFeaturesBinary2d(mask, centre, edge='down') -- for ALL objects of a map in one chain of launches:
 // label once, reduce once, cast the rays of every object together.  Integers up to the centre (one fp64 division, rint) and the walk
-// of k_rg_object_rays (region_growing.hip): same map, same bytes.  The numpy statement of the same definitions is
+// of raywalk.h: same map, same bytes.  The numpy statement of the same definitions is
 // pyimsegm_amd/region_growing.py (_object_shape_rays_host).
 //
 // Nothing comes back to the host between the launches: the case decision, the number of objects and the capacity test live in a
 // header on the device (OS_* of object_shapes.h); a kernel whose case was not taken returns at once.
 #include "object_shapes.h"
+#include "raywalk.h"
 #include "scan.h"
 #include "slic.h"
 #include "unionfind.h"
@@ -89,47 +90,24 @@ __global__ void __launch_bounds__(256) k_os_decide(const int32_t *__restrict__ p
 }
 
 // ---- relabelled case: scipy.ndimage.label, 4-connected, on the pixels != 0 -----------------------------------------------------
-// The run rule of k_holes_init / k_holes_merge (morphology.hip) on another predicate: a wave covers 64 consecutive pixels of a row,
-// every object pixel starts out pointing at the first pixel of its run inside that segment, and the unions that are left lie where a
-// run crosses a segment and where a run meets the row above for the first time.  Workgroup b covers pixels 256 c .. 256 c + 255 of
-// row y, b = y * chunks + c.
+// The run rule of unionfind.h (run_label_init / run_label_merge); workgroup b covers pixels 256 c .. 256 c + 255 of row y,
+// b = y * chunks + c.
+__device__ __forceinline__ bool os_object(int32_t l) { return l != 0; }
+
 __global__ void __launch_bounds__(256)
 k_os_cc_init(const int32_t *__restrict__ segm, const int32_t *__restrict__ hdr, int32_t *__restrict__ parent, int W, int chunks)
 {
     if (hdr[OS_MODE] != OS_RELABEL) return;
-    const int lane = threadIdx.x & 63;
-    const int y = blockIdx.x / chunks, x = (blockIdx.x - y * chunks) * 256 + threadIdx.x;
-    const size_t row = (size_t)y * W;
-    const bool inx = x < W;
-    const bool obj = inx && segm[row + x] != 0;
-    const unsigned long long z = __ballot(obj);
-    if (!inx) return;
-    int start = lane;
-    if (obj) {
-        const unsigned long long starts = z & ~(z << 1);
-        const unsigned long long below = starts & ((2ULL << lane) - 1ULL);
-        start = 63 - __clzll((long long)below);
-    }
-    parent[row + x] = (int)(row + x) - (lane - start);
+    const int y = blockIdx.x / chunks;
+    run_label_init(segm, parent, y, (blockIdx.x - y * chunks) * 256 + threadIdx.x, W, os_object);
 }
 
 __global__ void __launch_bounds__(256)
 k_os_cc_merge(const int32_t *__restrict__ segm, const int32_t *__restrict__ hdr, int32_t *parent, int W, int chunks)
 {
     if (hdr[OS_MODE] != OS_RELABEL) return;
-    const int lane = threadIdx.x & 63;
-    const int y = blockIdx.x / chunks, x = (blockIdx.x - y * chunks) * 256 + threadIdx.x;
-    const size_t row = (size_t)y * W;
-    const bool inx = x < W;
-    const bool obj = inx && segm[row + x] != 0;
-    const bool up_any = inx && y > 0 && segm[row - W + x] != 0;
-    const bool up = obj && up_any;
-    const unsigned long long z = __ballot(obj), zu = __ballot(up_any);
-    if (!obj) return;
-    const int p = (int)(row + x);
-    const bool first = lane == 0 || !((z >> (lane - 1)) & 1ULL);
-    if (lane == 0 && x > 0 && segm[p - 1] != 0) uf_union_pair(parent, p, p - 1);
-    if (up && (first || !((zu >> (lane - 1)) & 1ULL))) uf_union_pair(parent, p, p - W);
+    const int y = blockIdx.x / chunks;
+    run_label_merge(segm, parent, y, (blockIdx.x - y * chunks) * 256 + threadIdx.x, W, os_object);
 }
 
 // ---- keys and their presence ---------------------------------------------------------------------------------------------------
@@ -274,9 +252,8 @@ k_os_centres(const long long *__restrict__ moments, const int32_t *__restrict__ 
 
 // ---- rays ------------------------------------------------------------------------------------------------------------------------
 // computeRayFeaturesBinary2d (features_cython.pyx:244-282) with edge 'down' on the mask key == key of the object, which is never
-// materialised: the walk of k_rg_object_rays (region_growing.hip) / k_ray_features_binary2d (natives.hip), the same float32 / float64
-// operations in the same order.  One wave per object, the lanes stride over the angles.  The centre of an object of several pieces
-// may lie outside it: the walk then starts with last = false, as the reference's does.
+// materialised: the walk of raywalk.h.  One wave per object, the lanes stride over the angles.  The centre of an object of several
+// pieces may lie outside it: the walk then starts off the mask, as the reference's does.
 __global__ void __launch_bounds__(64)
 k_os_rays(const int32_t *__restrict__ key, int H, int W, const int32_t *__restrict__ hdr, int max_objects,
           const int32_t *__restrict__ obj_key, const int32_t *__restrict__ centres, const float *__restrict__ grad, int A,
@@ -288,30 +265,11 @@ k_os_rays(const int32_t *__restrict__ key, int H, int W, const int32_t *__restri
     const int own = obj_key[o];
     const int py = centres[2 * o], px = centres[2 * o + 1];
     const bool inside = py >= 0 && py < H && px >= 0 && px < W;
-    const bool start = inside ? key[(size_t)py * W + px] == own : false;
-    const int diag = (int)sqrt((double)W * W + (double)H * H);
-    for (int a = threadIdx.x; a < A; a += 64) {
-        float res = -1.f;
-        if (inside) {
-            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
-            float pos0 = (float)py, pos1 = (float)px;
-            bool last = start;
-            for (int it = 0; it < diag; ++it) {
-                pos0 += g0;
-                pos1 += g1;
-                const double r0 = round((double)pos0), r1 = round((double)pos1);
-                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
-                const bool actual = key[(size_t)(int)r0 * W + (int)r1] == own;
-                if (last && !actual) {
-                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
-                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
-                    break;
-                }
-                last = actual;
-            }
-        }
-        out[(size_t)o * A + a] = res;
-    }
+    auto on_mask = [&](int y, int x) -> bool { return key[(size_t)y * W + x] == own; };
+    const bool start = inside ? on_mask(py, px) : false;
+    const int diag = ray_walk_limit(H, W);
+    for (int a = threadIdx.x; a < A; a += 64)
+        out[(size_t)o * A + a] = ray_walk(py, px, inside, start, grad[2 * a], grad[2 * a + 1], H, W, diag, -1, on_mask);
 }
 
 int launch_object_shapes(const OsView &v, hipStream_t st)

@@ -3,6 +3,7 @@
 //   compute_ray_features_positions       descriptors.py:1805-1895 (the mask `segm in border_labels`, the walk of
 //                                        features_cython.pyx:244-282 and scipy.ndimage.gaussian_filter1d along the angle)
 // The reference loops over the positions in Python, with one Cython call per position and per disc.
+#include "raywalk.h"
 #include "slic.h"
 
 namespace imsegm {
@@ -147,10 +148,9 @@ __device__ __forceinline__ int reflect_index(int i, int A)
 }
 
 // Ray features against the mask `segm in border` (descriptors.py:1869-1871), formed here from the label table: no binary image is
-// built or uploaded.  The walk is k_ray_features_binary2d's (natives.hip), the same float32 / float64 operations in the same order.
-// One wave per position; its A distances stay in LDS for the optional smoothing along the angle, which is
-// scipy.ndimage.gaussian_filter1d(ray, sigma) on the float32 row: taps[j] = the normalised weight at distance j (from the host),
-// boundary 'reflect', float64 sums in scipy's symmetric order (ni_filters.c NI_Correlate1D: the centre tap, then the pairs from the
+// built or uploaded.  The walk is ray_walk (raywalk.h).  One wave per position; its A distances stay in LDS for the optional
+// smoothing along the angle, which is scipy.ndimage.gaussian_filter1d(ray, sigma) on the float32 row: taps[j] = the normalised
+// weight at distance j (from the host), boundary 'reflect', float64 sums in scipy's symmetric order (ni_filters.c NI_Correlate1D: the centre tap, then the pairs from the
 // farthest to the nearest, (x[i - j] + x[i + j]) * taps[j]), stored as float32.
 __global__ void __launch_bounds__(64)
 k_ray_features_labels2d(const int32_t *__restrict__ segm, int H, int W, const int32_t *__restrict__ border, int n_border,
@@ -160,38 +160,18 @@ k_ray_features_labels2d(const int32_t *__restrict__ segm, int H, int W, const in
     extern __shared__ float ray[];                          // [A]
     const int p = blockIdx.x;
     if (p >= P) return;
-    auto masked = [&](int y, int x) -> int8_t {
+    auto masked = [&](int y, int x) -> bool {
         const int32_t l = segm[(size_t)y * W + x];
-        int8_t hit = 0;
-        for (int b = 0; b < n_border; ++b) hit |= (int8_t)(l == border[b]);
+        bool hit = false;
+        for (int b = 0; b < n_border; ++b) hit |= l == border[b];
         return hit;
     };
     const int py = positions[2 * p], px = positions[2 * p + 1];
     const bool inside = py >= 0 && py < H && px >= 0 && px < W;
-    const int8_t start = inside ? masked(py, px) : 0;
-    const int diag = (int)sqrt((double)W * W + (double)H * H);
+    const bool start = inside ? masked(py, px) : false;
+    const int diag = ray_walk_limit(H, W);
     for (int a = threadIdx.x; a < A; a += blockDim.x) {
-        float res = -1.f;
-        if (start && edge == 1) {
-            res = 0.f;                                       // the position lies inside the border label
-        } else if (inside) {
-            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
-            float pos0 = (float)py, pos1 = (float)px;
-            int8_t last = start;
-            for (int it = 0; it < diag; ++it) {
-                pos0 += g0;
-                pos1 += g1;
-                const double r0 = round((double)pos0), r1 = round((double)pos1);
-                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
-                const int8_t actual = masked((int)r0, (int)r1);
-                if ((edge == 1 && actual) || (edge == -1 && last && !actual)) {
-                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
-                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
-                    break;
-                }
-                last = actual;
-            }
-        }
+        const float res = ray_walk(py, px, inside, start, grad[2 * a], grad[2 * a + 1], H, W, diag, edge, masked);
         if (taps)
             ray[a] = res;
         else

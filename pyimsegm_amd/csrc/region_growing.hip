@@ -5,6 +5,7 @@
 // criterion (compute_rg_crit :1114-1133).  All fp64 (the rays float32, as the .pyx), every operation rounds on its own
 // (-ffp-contract=off), sums in a fixed order, no floating-point atomics.  The numpy statement of the same definitions is
 // pyimsegm_amd/region_growing.py (on='host').
+#include "raywalk.h"
 #include "region_growing.h"
 #include "slic.h"
 
@@ -85,8 +86,8 @@ __global__ __launch_bounds__(RG_THREADS) void k_rg_shape_cost(const int32_t *__r
     if (proba) proba[(size_t)j * K + s] = p;
 }
 
-// computeRayFeaturesBinary2d (features_cython.pyx:244-282, the walk of k_ray_features_binary2d in natives.hip) with edge 'down'
-// on the mask labels[slic[y][x]] == object + 1, which is never materialised.  One wave per object, one lane per angle.
+// computeRayFeaturesBinary2d (the walk of raywalk.h) with edge 'down' on the mask labels[slic[y][x]] == object + 1, which is never
+// materialised.  One wave per object, one lane per angle.
 __global__ __launch_bounds__(64) void k_rg_object_rays(const int32_t *__restrict__ slic, int H, int W, const int32_t *__restrict__ labels,
                                                        int K, const int32_t *__restrict__ positions, const float *__restrict__ grad,
                                                        int A, float *__restrict__ out)
@@ -99,29 +100,9 @@ __global__ __launch_bounds__(64) void k_rg_object_rays(const int32_t *__restrict
         return (unsigned)l < (unsigned)K && labels[l] == obj;
     };
     const bool start = inside ? mask(py, px) : false;
-    const int diag = (int)sqrt((double)W * W + (double)H * H);
-    for (int a = threadIdx.x; a < A; a += 64) {
-        float res = -1.f;
-        if (inside) {
-            const float g0 = grad[2 * a], g1 = grad[2 * a + 1];
-            float pos0 = (float)py, pos1 = (float)px;
-            bool last = start;
-            for (int it = 0; it < diag; ++it) {
-                pos0 += g0;
-                pos1 += g1;
-                const double r0 = round((double)pos0), r1 = round((double)pos1);
-                if (pos0 < 0 || r0 >= H || pos1 < 0 || r1 >= W) break;
-                const bool actual = mask((int)r0, (int)r1);
-                if (last && !actual) {
-                    const float dx = pos0 - (float)py, dy = pos1 - (float)px;
-                    res = (float)sqrt((double)((dx * dx) + (dy * dy)));
-                    break;
-                }
-                last = actual;
-            }
-        }
-        out[(size_t)o * A + a] = res;
-    }
+    const int diag = ray_walk_limit(H, W);
+    for (int a = threadIdx.x; a < A; a += 64)
+        out[(size_t)o * A + a] = ray_walk(py, px, inside, start, grad[2 * a], grad[2 * a + 1], H, W, diag, -1, mask);
 }
 
 // get_neighboring_candidates for every object at once: one lane per (object, superpixel); the pair qualifies when the superpixel

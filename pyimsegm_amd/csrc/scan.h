@@ -38,4 +38,22 @@ template <int NW, typename T> __device__ __forceinline__ T block_exclusive_scan(
     return base + incl - v;
 }
 
+// One step of a stable compaction by a workgroup of 256 (k_compact_gather, k_annot_hist_gather): the output index of this lane's
+// element -- *base plus the number of lanes below it in the workgroup whose flag is set; meaningful where the lane's own flag is
+// set -- and *base moved on by the number of set flags.  Two barriers: every thread of the workgroup has to call it, and a caller
+// may call it again at once.
+__device__ __forceinline__ uint32_t block_stable_slot(bool flag, uint32_t *base)
+{
+    __shared__ uint32_t s_wave[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long votes = __ballot(flag);
+    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(votes);
+    __syncthreads();
+    uint32_t before = *base;
+    for (int w = 0; w < wave; ++w) before += s_wave[w];
+    *base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+    return before + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull));
+}
+
 }  // namespace imsegm

@@ -1,7 +1,8 @@
 // unionfind.h -- the union-find forest in global memory that the labelling passes share (connectivity.hip, label_cc.hip): a set's
 // root is its SMALLEST index (atomicMin on the parent of the larger root), so the result does not depend on the order of the unions.
 // (The 2-D tile path of connectivity.hip keeps a forest of its own in volatile LDS -- lds_find / lds_union -- with other memory
-// semantics; it is not this one.)  Also here: load4_i32, the 16-byte load of four consecutive words with a tail that these passes
+// semantics; it is not this one.)  Also here: the 2-D labelling by row segments that morphology.hip and object_shapes.hip share
+// (run_start_lane, run_label_init, run_label_merge), and load4_i32, the 16-byte load of four consecutive words with a tail that these passes
 // and their neighbours (k_kept_scan, k_small_bbox) read parents with.
 #pragma once
 #include "common.h"
@@ -56,6 +57,51 @@ __device__ __forceinline__ void uf_union_pair(int32_t *parent, int a, int b)
         if (old == a) return;
         a = old;
     }
+}
+
+// the lane at which the run of `lane` starts: the highest bit of `starts` (one bit per lane that begins a run) at or below it
+__device__ __forceinline__ int run_start_lane(unsigned long long starts, int lane)
+{
+    const unsigned long long below = starts & ((2ULL << lane) - 1ULL);
+    return 63 - __clzll((long long)below);
+}
+
+// ---- 4-connected labelling of the pixels of a 2-D map that a predicate on their value selects, by row segments -----------------
+// (k_holes_* of morphology.hip on the pixels <= 0, k_os_cc_* of object_shapes.hip on the pixels != 0.)  A wave covers 64
+// consecutive pixels of row y, lane = x & 63, and every lane of the wave calls.  run_label_init: every selected pixel starts out
+// pointing at the first pixel of its run INSIDE its segment, every other pixel at itself, so the unions that are left lie where a
+// run crosses a segment and where a run meets the row above for the first time.
+template <typename Selected>
+__device__ __forceinline__ void run_label_init(const int32_t *__restrict__ segm, int32_t *__restrict__ parent, int y, int x, int W,
+                                               Selected selected)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)y * W;
+    const bool inx = x < W;
+    const bool sel = inx && selected(segm[row + x]);
+    const unsigned long long z = __ballot(sel);
+    if (!inx) return;
+    const int start = sel ? run_start_lane(z & ~(z << 1), lane) : lane;
+    parent[row + x] = (int)(row + x) - (lane - start);
+}
+
+// run_label_merge: p and the pixel above it are tied when p starts a run of its segment or the pixel above p - 1 is not selected:
+// otherwise p - 1 is tied to the pixel above it, which shares a run (and a segment) with the pixel above p
+template <typename Selected>
+__device__ __forceinline__ void run_label_merge(const int32_t *__restrict__ segm, int32_t *parent, int y, int x, int W, Selected selected)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)y * W;
+    const bool inx = x < W;
+    const bool sel = inx && selected(segm[row + x]);
+    const bool up_any = inx && y > 0 && selected(segm[row - W + x]);
+    const bool up = sel && up_any;
+    const unsigned long long z = __ballot(sel), zu = __ballot(up_any);
+    if (!sel) return;
+    const int p = (int)(row + x);
+    const bool first = lane == 0 || !((z >> (lane - 1)) & 1ULL);
+    if (lane == 0 && x > 0 && selected(segm[p - 1])) uf_union_pair(parent, p, p - 1);
+    if (up && (first || !((zu >> (lane - 1)) & 1ULL))) uf_union_pair(parent, p, p - W);
 }
 
 // Union-find with the smaller index as the root (atomicMin on the parent of the larger root), TWO unions of a lane side by side:

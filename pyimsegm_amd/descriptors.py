@@ -829,6 +829,44 @@ def _ray_directions(angle_step):
     return dirs
 
 
+def ray_walk_host(mask, positions, directions, edge):
+    """``computeRayFeaturesBinary2d(mask, position, edge)`` in numpy for all positions and angles: float32 [P, A]; float32 positions
+    advanced by the float32 ``directions`` [A, 2], the walk of csrc/raywalk.h operation by operation -- the one host statement of
+    it (``ellipse_fitting.ray_walk_host`` is this function, ``region_growing.ray_distances_down`` its one-position 'down' call).
+    ``edge`` is 1 ('up': the first mask pixel) or -1 ('down': the first pixel off the mask after one on it)."""
+    mask = np.asarray(mask, dtype=bool)
+    height, width = mask.shape
+    directions = np.asarray(directions, dtype=np.float32).reshape(-1, 2)
+    positions = np.asarray(positions, dtype=np.int64).reshape(-1, 2)
+    rays = np.full((len(positions), len(directions)), -1, dtype=np.float32)
+    steps = int(np.sqrt(float(width) * width + float(height) * height))
+    for p, (py, px) in enumerate(positions):
+        if not (0 <= py < height and 0 <= px < width):
+            continue
+        if edge == 1 and mask[py, px]:
+            rays[p] = 0
+            continue
+        pos0 = np.full(len(directions), py, dtype=np.float32)
+        pos1 = np.full(len(directions), px, dtype=np.float32)
+        last = np.full(len(directions), mask[py, px], dtype=bool)
+        active = np.ones(len(directions), dtype=bool)
+        for _ in range(steps):
+            if not active.any():
+                break
+            pos0 = pos0 + directions[:, 0]
+            pos1 = pos1 + directions[:, 1]
+            r0, r1 = np.floor(pos0.astype(np.float64) + 0.5), np.floor(pos1.astype(np.float64) + 0.5)
+            active &= ~((pos0 < 0) | (r0 >= height) | (pos1 < 0) | (r1 >= width))
+            idx = np.nonzero(active)[0]
+            actual = mask[r0[idx].astype(int), r1[idx].astype(int)]
+            hit = actual if edge == 1 else last[idx] & ~actual
+            dx, dy = pos0[idx[hit]] - np.float32(py), pos1[idx[hit]] - np.float32(px)
+            rays[p, idx[hit]] = np.sqrt(((dx * dx) + (dy * dy)).astype(np.float64)).astype(np.float32)
+            last[idx] = actual
+            active[idx[hit]] = False
+    return rays
+
+
 def hip_ray_features_positions(seg_binary, positions, angle_step=5., edge='up'):
     """ ray features of many positions in ONE launch (``computeRayFeaturesBinary2d`` per position): float32 P x A """
     edge_int = {'down': -1, 'up': 1}[edge]

@@ -24,11 +24,10 @@ Definitions ("Ellipse RANSAC"): the criterion keeps the ref
 looked up by the CLASS LABEL of a centre inside the ellipse, not by the centre; the residual is the distance to the closest
 point of the ellipse in the basin of skimage's starting parameter (what its ``leastsq`` converges to, not its iteration).
 """
-import os
-
 import numpy as np
 
 from pyimsegm_amd import _hip
+from pyimsegm_amd.descriptors import ray_walk_host  # noqa: F401  (the one host walk, also under this module's name)
 
 #: what the reference's rays are clamped to from below (its spelling)
 MIN_ELLIPSE_DAIM = 25.
@@ -289,18 +288,8 @@ def score_trials_host(point_offsets, points, params, success, trial_egg, points_
 
 
 def _place(on):
-    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_RANSAC_ON, unset: 'device' when a device
-    is present"""
-    if on is None:
-        on = os.environ.get('IMSEGM_RANSAC_ON') or None
-    if on is None:
-        try:
-            on = 'device' if _hip.device_count() > 0 else 'host'
-        except _hip.HipUnavailableError:
-            on = 'host'
-    if on not in ('host', 'device'):
-        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
-    return on
+    """'host' or 'device': ``_hip.resolve_place`` on IMSEGM_RANSAC_ON"""
+    return _hip.resolve_place(on, 'IMSEGM_RANSAC_ON', False)[0]
 
 
 def _nb_samples(min_samples, nb_points):
@@ -384,9 +373,10 @@ def ransac_segm(points, model_class, points_all, weights, labels, table_prob, mi
     (``|residual| < residual_threshold``) follows it only when it has more inliers than the mask kept so far; the model is
     re-estimated from the kept inliers.  Returns ``(model, inliers)``, or ``(None, None)`` when no trial succeeded.
 
-    With ``model_class=EllipseModelSegm`` all trials are scored at once, ``on='device'`` (the default when a device is present, or
-    the environment variable ``IMSEGM_RANSAC_ON``) by ``imsegm_ellipse_ransac``, ``on='host'`` by the numpy statement of the same
-    definitions; any other model class runs the plain per-trial loop on the host."""
+    With ``model_class=EllipseModelSegm`` all trials are scored at once, ``on='device'`` by ``imsegm_ellipse_ransac``, ``on='host'``
+    by the numpy statement of the same definitions (``on=None``: the environment variable ``IMSEGM_RANSAC_ON``; the rules every
+    ``on=`` keyword of this module follows are ``_hip.resolve_place``); any other model class runs the plain per-trial loop on the
+    host."""
     if model_class is EllipseModelSegm:
         return ransac_segm_batch([points], points_all, weights, labels, table_prob, min_samples, residual_threshold, max_trials, on)[0]
     points = np.array(points)
@@ -414,18 +404,8 @@ def get_slic_points_labels(segm, img=None, slic_size=20, slic_regul=0.1):
 
 
 def _points_place(on):
-    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_BOUNDARY_POINTS_ON, unset: 'device' when a
-    device is present"""
-    if on is None:
-        on = os.environ.get('IMSEGM_BOUNDARY_POINTS_ON') or None
-    if on is None:
-        try:
-            on = 'device' if _hip.device_count() > 0 else 'host'
-        except _hip.HipUnavailableError:
-            on = 'host'
-    if on not in ('host', 'device'):
-        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
-    return on
+    """'host' or 'device': ``_hip.resolve_place`` on IMSEGM_BOUNDARY_POINTS_ON"""
+    return _hip.resolve_place(on, 'IMSEGM_BOUNDARY_POINTS_ON', False)[0]
 
 
 def _integer_radii(*radii):
@@ -471,43 +451,6 @@ def split_host(seg, sel_bg=STRUC_ELEM_BG, sel_fg=STRUC_ELEM_FG, with_fg=True):
         if sel_fg > 0:
             seg_fg = opening_host(seg_fg, sel_fg)
     return seg_bg, seg_fg
-
-
-def ray_walk_host(mask, positions, directions, edge):
-    """``computeRayFeaturesBinary2d(mask, position, edge)`` in numpy for all positions and angles: float32 [P, A]; float32 positions
-    advanced by the float32 ``directions`` [A, 2], the walk of ``k_boundary_rays`` / ``k_ray_features_binary2d`` operation by
-    operation.  ``edge`` is 1 ('up': the first mask pixel) or -1 ('down': the first pixel off the mask after one on it)."""
-    mask = np.asarray(mask, dtype=bool)
-    height, width = mask.shape
-    directions = np.asarray(directions, dtype=np.float32).reshape(-1, 2)
-    positions = np.asarray(positions, dtype=np.int64).reshape(-1, 2)
-    rays = np.full((len(positions), len(directions)), -1, dtype=np.float32)
-    steps = int(np.sqrt(float(width) * width + float(height) * height))
-    for p, (py, px) in enumerate(positions):
-        if not (0 <= py < height and 0 <= px < width):
-            continue
-        if edge == 1 and mask[py, px]:
-            rays[p] = 0
-            continue
-        pos0 = np.full(len(directions), py, dtype=np.float32)
-        pos1 = np.full(len(directions), px, dtype=np.float32)
-        last = np.full(len(directions), mask[py, px], dtype=bool)
-        active = np.ones(len(directions), dtype=bool)
-        for _ in range(steps):
-            if not active.any():
-                break
-            pos0 = pos0 + directions[:, 0]
-            pos1 = pos1 + directions[:, 1]
-            r0, r1 = np.floor(pos0.astype(np.float64) + 0.5), np.floor(pos1.astype(np.float64) + 0.5)
-            active &= ~((pos0 < 0) | (r0 >= height) | (pos1 < 0) | (r1 >= width))
-            idx = np.nonzero(active)[0]
-            actual = mask[r0[idx].astype(int), r1[idx].astype(int)]
-            hit = actual if edge == 1 else last[idx] & ~actual
-            dx, dy = pos0[idx[hit]] - np.float32(py), pos1[idx[hit]] - np.float32(px)
-            rays[p, idx[hit]] = np.sqrt(((dx * dx) + (dy * dy)).astype(np.float64)).astype(np.float32)
-            last[idx] = actual
-            active[idx[hit]] = False
-    return rays
 
 
 def boundary_rays_host(seg, sel_bg, sel_fg, positions, directions, with_fg=True):
@@ -735,21 +678,9 @@ SINGLE_CALL_DEVICE_FROM_LABELS = 2
 
 def _place_place(on):
     """'host', 'device' or None (the default: the device when one is present, the host for a single ellipse on a map with few
-    labels) from the ``on`` keyword and the environment variable IMSEGM_ELLIPSE_PLACE_ON"""
-    if on is None:
-        on = os.environ.get('IMSEGM_ELLIPSE_PLACE_ON') or None
-    if on not in (None, 'host', 'device'):
-        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
-    if on != 'host':
-        try:
-            present = _hip.device_count() > 0
-        except _hip.HipUnavailableError:
-            present = False
-        if not present:
-            if on == 'device':
-                raise _hip.HipUnavailableError('no HIP device is visible')
-            return 'host'
-    return on
+    labels): ``_hip.resolve_place`` on IMSEGM_ELLIPSE_PLACE_ON ('device' without a device raises)"""
+    place, explicit = _hip.resolve_place(on, 'IMSEGM_ELLIPSE_PLACE_ON', True)
+    return place if explicit or place == 'host' else None
 
 
 def _ellipse_box(r, c, r_radius, c_radius, orientation, shape):

@@ -15,14 +15,12 @@ the device.
 Definitions ("Region growing"): the shape prior is bilinear on the 2 x 2 cell where the reference builds an
 ``interp2d`` object; the energy change of a candidate is the delta of the criterion, not the difference of two full sums.
 """
-import os
-
 import numpy as np
 from scipy import ndimage, stats
 from sklearn import cluster, mixture
 
 from pyimsegm_amd import _hip
-from pyimsegm_amd.descriptors import _ray_directions, interpolate_ray_dist, shift_ray_features
+from pyimsegm_amd.descriptors import _ray_directions, interpolate_ray_dist, ray_walk_host, shift_ray_features
 from pyimsegm_amd.graph_cuts import MAX_PAIRWISE_COST, compute_spatial_dist, cut_general_graph, cut_grid_graph, get_vertexes_edges
 from pyimsegm_amd.labeling import histogram_regions_labels_norm
 
@@ -42,18 +40,8 @@ RG2SP_THRESHOLDS = {
 
 
 def _place(on, variable='IMSEGM_RG_ON'):
-    """'host' or 'device' from the ``on`` keyword; None: the environment variable IMSEGM_RG_ON (``variable``), unset: 'device' when
-    a device is present"""
-    if on is None:
-        on = os.environ.get(variable) or None
-    if on is None:
-        try:
-            on = 'device' if _hip.device_count() > 0 else 'host'
-        except _hip.HipUnavailableError:
-            on = 'host'
-    if on not in ('host', 'device'):
-        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
-    return on
+    """'host' or 'device': ``_hip.resolve_place`` on IMSEGM_RG_ON (``variable``)"""
+    return _hip.resolve_place(on, variable, False)[0]
 
 
 def _replace_inf(values):
@@ -125,34 +113,9 @@ def _shape_cost(prior):
 
 
 def ray_distances_down(mask, position, directions):
-    """``computeRayFeaturesBinary2d(mask, position, edge='down')`` in numpy, all angles at once: float32 positions advanced by the
-    float32 ``directions`` [A, 2], the walk of ``k_rg_object_rays`` / ``k_ray_features_binary2d`` operation by operation"""
-    mask = np.asarray(mask, dtype=bool)
-    height, width = mask.shape
-    directions = np.asarray(directions, dtype=np.float32)
-    rays = np.full(len(directions), -1, dtype=np.float32)
-    py, px = int(position[0]), int(position[1])
-    if not (0 <= py < height and 0 <= px < width):
-        return rays
-    pos0 = np.full(len(directions), py, dtype=np.float32)
-    pos1 = np.full(len(directions), px, dtype=np.float32)
-    last = np.full(len(directions), mask[py, px], dtype=bool)
-    active = np.ones(len(directions), dtype=bool)
-    for _ in range(int(np.sqrt(float(width) * width + float(height) * height))):
-        if not active.any():
-            break
-        pos0 = pos0 + directions[:, 0]
-        pos1 = pos1 + directions[:, 1]
-        r0, r1 = np.floor(pos0.astype(np.float64) + 0.5), np.floor(pos1.astype(np.float64) + 0.5)
-        active &= ~((pos0 < 0) | (r0 >= height) | (pos1 < 0) | (r1 >= width))
-        idx = np.nonzero(active)[0]
-        actual = mask[r0[idx].astype(int), r1[idx].astype(int)]
-        hit = last[idx] & ~actual
-        dx, dy = pos0[idx[hit]] - np.float32(py), pos1[idx[hit]] - np.float32(px)
-        rays[idx[hit]] = np.sqrt(((dx * dx) + (dy * dy)).astype(np.float64)).astype(np.float32)
-        last[idx] = actual
-        active[idx[hit]] = False
-    return rays
+    """``computeRayFeaturesBinary2d(mask, position, edge='down')`` in numpy, all angles at once: float32 [A], the one-position call
+    of ``descriptors.ray_walk_host``"""
+    return ray_walk_host(mask, [(int(position[0]), int(position[1]))], directions, -1)[0]
 
 
 def _delta_scores(objects, superpixels, labels, weights, lut_data, lut_shape, nb_off, nb_flat, coef_data, coef_shape, coef_pairwise,
@@ -1005,7 +968,7 @@ def region_growing_shape_slic_greedy(slic, slic_prob_fg, centres, shape_model, s
     :param dict dict_thresholds: in place of ``RG2SP_THRESHOLDS``
     :param int nb_iter: at most this many iterations
     :param dict debug_history: filled with the criteria, labels, centres, shifts and cost tables of every iteration
-    :param str on: 'device' or 'host' (default: the environment variable IMSEGM_RG_ON, else the device when one is present)
+    :param str on: 'device', 'host' or None (IMSEGM_RG_ON); the rules of the switch are ``_hip.resolve_place``
     :return ndarray: label of every superpixel
     """
     growth = _Growth(slic, slic_prob_fg, centres, shape_model, shape_type, (coef_data, coef_shape, coef_pairwise), prob_label_trans,

@@ -73,3 +73,21 @@ def cumulative_inputs(seed):
     means, stds = rng.uniform(5, 25, (3, 5)), rng.uniform(0.5, 4, (3, 5))
     weights = rng.dirichlet(np.ones(3))
     return means, stds, weights, float(np.max(means + 2 * stds))
+
+
+#: maps wider than one workgroup of 256 pixels, so that a row is more than one chunk of the run labelling
+SEAM_SHAPES = ((9, 257), (12, 300))
+
+
+def seam_map(shape, multi):
+    """three objects around the seam between the pixels 255 and 256 of a row: a run across it, a U whose two bars (columns 252 and
+    256) meet only in its bottom row -- the union across the seam closes last -- and a single pixel at column 256; one value
+    (``multi`` False) or the values 2, 3, 5"""
+    height, width = shape
+    img = np.zeros(shape, dtype=np.int32)
+    img[0, 240:min(width, 290)] = 2
+    img[2:6, 252] = 3
+    img[2:6, 256] = 3
+    img[5, 252:257] = 3
+    img[7, 256] = 5
+    return img if multi else (img != 0).astype(np.int32)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import boundary_points_cases as C
+import object_shapes_cases as S
 
 pytestmark = pytest.mark.gpu
 EDGE = C.edge_cases()
@@ -64,6 +65,19 @@ def test_masks_equal_the_host_statement(hip, host_results, name):
     assert same_bytes(seg_fg, want_fg.astype(np.uint8)), name
     again = hip.split_background_foreground(case['seg'].astype(np.int32), case['sel_bg'], case['sel_fg'])
     assert same_bytes(again[0], seg_bg) and same_bytes(again[1], seg_fg)
+
+
+@pytest.mark.parametrize('shape', S.SEAM_SHAPES)
+@pytest.mark.parametrize('multi', [False, True])
+def test_holes_in_rows_of_more_than_one_chunk(hip, ell, shape, multi):
+    """maps wider than 256 pixels, inverted so that the objects around the seam between two chunks of a row are the holes"""
+    objects = S.seam_map(shape, multi)
+    seg = np.where(objects != 0, 0, 1).astype(np.int32)
+    seg_bg, seg_fg = hip.split_background_foreground(seg, 0, 0)
+    want_bg, want_fg = ell.split_host(seg, 0, 0)
+    assert same_bytes(seg_bg, want_bg.astype(np.uint8)) and same_bytes(seg_fg, want_fg.astype(np.uint8))
+    # the run lies on the border; the U and the pixel are holes unless column 256 is the border itself
+    assert seg_bg[0, 240:257].all() and seg_bg[2:8].any() == (shape[1] == 257)
 
 
 @pytest.mark.parametrize('name', sorted(EDGE))

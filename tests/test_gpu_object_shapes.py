@@ -66,6 +66,32 @@ def test_widths_beside_and_across_a_wave(rg, hip, shape, relabel):
     assert len(labels) >= 2 and (rays == -1).any()
 
 
+@pytest.mark.parametrize('shape', C.SEAM_SHAPES)
+@pytest.mark.parametrize('multi', [False, True])
+def test_rows_of_more_than_one_chunk(rg, hip, shape, multi):
+    """wider than 256 pixels: a workgroup is one of several chunks of its row, and runs, unions and single pixels sit on the seam"""
+    labels, moments, centres, rays = check(rg, hip, C.seam_map(shape, multi), 45, objects=3, interp_order=None)
+    assert labels.tolist() == ([2, 3, 5] if multi else [1, 2, 3])
+    assert moments[:, 0].tolist() == [min(shape[1], 290) - 240, 11, 1] and centres[2].tolist() == [7, 256]
+
+
+def test_border_components_are_the_background_of_the_inverted_map(rg, hip):
+    """two labellings of one map agree: the components of ``m`` that touch the image border (object shapes, pixels != 0) are the
+    background that hole filling leaves of ``1 - m`` (pixels <= 0)"""
+    from scipy import ndimage
+    m = C.seam_map(C.SEAM_SHAPES[1], False)
+    m[3:5, 0:3] = 1                                          # one more component on the border, and the U and the pixel inside
+    moments = check(rg, hip, m, 45, objects=4, interp_order=None)[1]
+    seg_bg, _ = hip.split_background_foreground((1 - m).astype(np.int32), 0, 0)
+    numbered, count = ndimage.label(m)                       # scipy's numbering is the order of the device's objects (check)
+    on_border = np.unique(np.concatenate([numbered[0], numbered[-1], numbered[:, 0], numbered[:, -1]]))
+    on_border = on_border[on_border > 0]
+    assert count == 4 and on_border.tolist() == [1, 3]
+    assert np.array_equal(seg_bg != 0, np.isin(numbered, on_border))
+    rows, cols = np.nonzero(seg_bg)
+    assert moments[on_border - 1].sum(axis=0).tolist() == [len(rows), rows.sum(), cols.sum()]
+
+
 @pytest.mark.parametrize('shape', [(1, 97), (97, 1)])
 def test_single_row_and_column(rg, hip, shape):
     line = np.zeros(97, dtype=np.int32)
