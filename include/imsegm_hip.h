@@ -822,6 +822,34 @@ IMSEGM_API int imsegm_annot_nearest_valid(imsegm_ctx *ctx, const int32_t *labels
 IMSEGM_API int imsegm_annot_quantize_nearest_pixel(imsegm_ctx *ctx, const uint8_t *image, int height, int width, const uint8_t *colors,
                                                    int n_colors, uint8_t *image_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scoring label maps against annotations (imsegm/classification.py compute_classif_metrics :305-371,
+ * compute_classif_stat_segm_annot :374-421, compute_stat_per_image :424-471): everything those report is a function of the
+ * contingency table of the two maps over the labels present; csrc/scoring.hip counts it, the host does the rest on a U x U matrix.
+ * Integers only: same call, same bytes.  All arrays are host arrays.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_SCORE_I32 0                 /* element type of the maps: int32 */
+#define IMSEGM_SCORE_U8 1                  /* uint8, uploaded at one byte per pixel and widened on load */
+#define IMSEGM_SCORE_MAX_LABELS 64         /* distinct labels of a pair the device counts */
+#define IMSEGM_SCORE_MAX_DROP 64           /* entries of the drop list */
+#define IMSEGM_SCORE_OK 0                  /* status of a pair: counted */
+#define IMSEGM_SCORE_TOO_MANY_LABELS 1     /* more than IMSEGM_SCORE_MAX_LABELS labels: nothing else of the pair is written */
+/* geometry of the two pixel kernels (the tests take their sizes from here) */
+#define IMSEGM_SCORE_THREADS 256           /* lanes of a workgroup: four waves of 64 */
+#define IMSEGM_SCORE_RUN 8                 /* consecutive pixels a lane loads per step */
+#define IMSEGM_SCORE_CHUNK_STEPS 4         /* steps of a workgroup: it owns THREADS * RUN * CHUNK_STEPS consecutive pixels of one pair */
+#define IMSEGM_SCORE_WAVE_TABLE_LABELS 32  /* up to here every wave counts into an LDS table of its own, above into one per workgroup */
+/* Pair i is annots[i] and segms[i], sizes[i] elements each (0 is legal, 2^40 at the most) of the type `dtype`; a pixel is dropped
+ * when either map carries one of the n_drop drop_labels there (:404-410).  Per pair: status_out[i]; n_labels_out[i] = U, the number
+ * of distinct values of both maps over the pixels that stay; labels_out[i * MAX_LABELS ..] those values ascending;
+ * tables_out[i * MAX_LABELS^2 + a * U + b] = #{annot == labels[a] and segm == labels[b]} (row stride U).  A pair with more than
+ * MAX_LABELS labels gets IMSEGM_SCORE_TOO_MANY_LABELS and nothing else; the other pairs are not affected.  One upload per array,
+ * one chain of launches over all pairs, one download.  Returns -1 (nothing launched) for a null array, a negative count, more than
+ * 2^20 pairs, an unknown dtype, a size that is negative or above 2^40 and more than MAX_DROP drop labels. */
+IMSEGM_API int imsegm_score_pairs(imsegm_ctx *ctx, int n_pairs, const void *const *annots, const void *const *segms, const int64_t *sizes,
+                                  int dtype, const int32_t *drop_labels, int n_drop, int32_t *status_out, int32_t *n_labels_out,
+                                  int32_t *labels_out, int64_t *tables_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,7 @@ _SIGNATURES = {
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    'imsegm_score_pairs': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -1974,6 +1975,74 @@ def annot_quantize_nearest_pixel(image, colors, ctx=None):
     _check(load_library().imsegm_annot_quantize_nearest_pixel(ctx._h, _ptr(image), image.shape[0], image.shape[1], _ptr(colors), len(colors),
                                                               _ptr(out)))
     return out
+
+
+#: ``IMSEGM_SCORE_*`` of include/imsegm_hip.h: the label cap of ``imsegm_score_pairs``, the length of its drop list and the geometry of
+#: its pixel kernels (lanes of a workgroup, pixels a lane loads per step, steps of a workgroup, last label count with per-wave tables)
+SCORE_MAX_LABELS, SCORE_MAX_DROP = 64, 64
+SCORE_THREADS, SCORE_RUN, SCORE_CHUNK_STEPS, SCORE_WAVE_TABLE_LABELS = 256, 8, 4, 32
+#: pixels of a pair one workgroup owns
+SCORE_CHUNK_PIXELS = SCORE_THREADS * SCORE_RUN * SCORE_CHUNK_STEPS
+#: what ``score_pairs`` returns in place of ``(labels, table)`` for a pair with more than ``SCORE_MAX_LABELS`` labels
+SCORE_TOO_MANY_LABELS = 'too many labels'
+#: bytes of maps ``score_pairs`` sends up in one call of ``imsegm_score_pairs``; a longer batch is split between pairs (a single
+#: pair above the budget still goes in a call of its own).  1 GiB holds sixteen 4096 x 4096 int32 pairs and keeps the context's scratch,
+#: which never shrinks, at a size that leaves the rest of the device's memory to the sessions.
+SCORE_BATCH_BYTES = 1 << 30
+_SCORE_DTYPES = {np.dtype(np.int32): 0, np.dtype(np.uint8): 1}
+
+
+def _score_call(annots, segms, dtype, drop, ctx):
+    count = len(annots)
+    pointers = (_vp * count)(*[_ptr(arr) for arr in annots]), (_vp * count)(*[_ptr(arr) for arr in segms])
+    sizes = np.array([arr.size for arr in annots], dtype=np.int64)
+    status, n_labels = np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.int32)
+    labels = np.empty((count, SCORE_MAX_LABELS), dtype=np.int32)
+    tables = np.empty((count, SCORE_MAX_LABELS * SCORE_MAX_LABELS), dtype=np.int64)
+    _check(load_library().imsegm_score_pairs(ctx._h, count, pointers[0], pointers[1], _ptr(sizes), _SCORE_DTYPES[dtype], _ptr(drop), len(drop),
+                                             _ptr(status), _ptr(n_labels), _ptr(labels), _ptr(tables)))
+    results = []
+    for i in range(count):
+        if status[i] != 0:
+            results.append(SCORE_TOO_MANY_LABELS)
+            continue
+        used = int(n_labels[i])
+        results.append((labels[i, :used].copy(), tables[i, :used * used].reshape(used, used).copy()))
+    return results
+
+
+def score_pairs(annots, segms, drop_labels=None, ctx=None):
+    """``imsegm_score_pairs``: per pair of equally sized arrays ``(labels int32 [U] ascending, table int64 [U, U])`` -- the distinct
+    values of both arrays over the elements where neither carries one of ``drop_labels``, and ``table[a, b]`` = number of those elements
+    with ``annot == labels[a]`` and ``segm == labels[b]`` -- or ``SCORE_TOO_MANY_LABELS`` for a pair with more than ``SCORE_MAX_LABELS``
+    of them.  All arrays are C-contiguous and of ONE dtype, int32 or uint8; empty pairs give U = 0.  Batches above
+    ``SCORE_BATCH_BYTES`` go up in several calls."""
+    annots, segms = list(annots), list(segms)
+    if len(annots) != len(segms):
+        raise ValueError('one segmentation per annotation')
+    drop = np.ascontiguousarray([] if drop_labels is None else drop_labels, dtype=np.int32).ravel()
+    if len(drop) > SCORE_MAX_DROP:
+        raise ValueError('a drop list holds at most %i labels' % SCORE_MAX_DROP)
+    if not annots:
+        return []
+    dtype = annots[0].dtype
+    if dtype not in _SCORE_DTYPES:
+        raise ValueError('the arrays must be int32 or uint8')
+    for annot, segm in zip(annots, segms):
+        for arr in (annot, segm):
+            if not isinstance(arr, np.ndarray) or arr.dtype != dtype or not arr.flags.c_contiguous:
+                raise ValueError('the arrays must be C-contiguous and of one dtype, int32 or uint8')
+        if annot.size != segm.size:
+            raise ValueError('the arrays of a pair must have one size')
+    ctx = ctx or default_context()
+    results, first, held = [], 0, 0
+    for i in range(len(annots) + 1):
+        here = 2 * annots[i].nbytes if i < len(annots) else 0
+        if i == len(annots) or (i > first and held + here > SCORE_BATCH_BYTES):
+            results += _score_call(annots[first:i], segms[first:i], dtype, drop, ctx)
+            first, held = i, 0
+        held += here
+    return results
 
 
 def ray_features_binary2d(seg_binary, positions, directions, edge, ctx=None):

@@ -11,6 +11,20 @@ features and the trained model, so they exist here, written against scikit-learn
 * :func:`create_classif_search_train_export` -- scaler -> (PCA) -> classifier, trained once or after a search
   (``classification.py:656-759``).
 
+Scoring class maps against annotations -- how every experiment ends -- is here too, with the reference's signatures, defaults,
+return types, keys and error types (``classification.py:305-471, 635-655, 1265-1366``): :data:`METRIC_AVERAGES`,
+:func:`relabel_sequential`, :func:`compute_classif_metrics`, :func:`compute_classif_stat_segm_annot`,
+:func:`compute_stat_per_image`, :func:`compute_tp_tn_fp_fn`, :func:`compute_metric_fpfn_tpfn` and :func:`compute_metric_tpfp_tpfn`.
+Everything they report is a function of the contingency table of the two maps over the labels present.  Each keeps a host
+statement (scikit-learn and numpy on the vectors) and takes ``on=None | 'host' | 'device'`` (environment: ``IMSEGM_SCORING_ON``;
+the rules of the switch are ``_hip.resolve_place``, and ``'device'`` without a device raises).  On the device one call of
+``imsegm_score_pairs`` (csrc/scoring.hip) returns the sorted labels and the exact table of every pair, and the scores are a few
+fp64 operations on its integers (:func:`_metrics_from_table`).  The host statement also answers, whatever ``on`` says, what the
+device does not take: arrays that are not integers within int32, more than 64 labels in a pair, more than 64 drop labels or one
+that is not an int32 integer, an average other than macro / weighted / micro / binary, ``relabel=True`` with a label above
+:data:`RELABEL_MAX_LABEL` or without a non-negative label on either side, and inputs that leave no element.  With ``on=None`` the
+functions named in :data:`HOST_BY_DEFAULT` run on the host although a device is present (tools/time_scoring.py).
+
 Every other name of the reference module resolves to the reference's own function when a reference package is installed
 behind the ``imsegm`` overlay (module ``__getattr__``).
 """
@@ -20,7 +34,9 @@ import random
 
 import numpy as np
 
-from pyimsegm_amd.utilities import reference_attribute
+from pyimsegm_amd import _hip
+from pyimsegm_amd.labeling import max_overlap_unique_lut
+from pyimsegm_amd.utilities import ImageDimensionError, reference_attribute
 
 #: classifier the pipelines train when none is named (``classification.py:47``)
 DEFAULT_CLASSIF_NAME = 'RandForest'
@@ -180,3 +196,420 @@ class CrossValidateGroups(object):
         for first in range(0, len(self._order), self._per_fold):
             held_out = self._order[first:first + self._per_fold]
             yield self._samples(set(self._order) - set(held_out)), self._samples(held_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# scoring class maps against annotations (reference classification.py:305-471, 635-655, 1265-1366)
+# ---------------------------------------------------------------------------------------------------------------------
+#: averages ``compute_classif_metrics`` reports when none are named (``classification.py:69``)
+METRIC_AVERAGES = ('macro', 'weighted')
+#: averages :func:`_metrics_from_table` restates; any other one takes the host statement
+_TABLE_AVERAGES = ('macro', 'weighted', 'micro', 'binary')
+#: ``relabel=True`` from the table builds the dense overlap of the labels 0 .. max: above this label the host relabels the pixels
+RELABEL_MAX_LABEL = 4095
+#: functions that run on the host with ``on=None`` although a device is present (profiles/scoring_time.json); ``on='device'``
+#: still takes the device
+HOST_BY_DEFAULT = frozenset()
+
+
+def _place(on, name):
+    """'host' or 'device' for the public function ``name``: ``_hip.resolve_place`` on IMSEGM_SCORING_ON and -- when neither the
+    keyword nor the variable says anything -- ``HOST_BY_DEFAULT``"""
+    place, explicit = _hip.resolve_place(on, 'IMSEGM_SCORING_ON', True)
+    return place if explicit or name not in HOST_BY_DEFAULT else 'host'
+
+
+def relabel_sequential(labels, uq_labels=None):
+    """ the labels numbered 0, 1, ... in the order of ``uq_labels`` (default: their sorted distinct values), as a list
+    (``classification.py:635-653``)
+
+    :param list(int) labels: all labels
+    :param list(int) uq_labels: unique labels
+    :return list:
+    """
+    labels = np.asarray(labels)
+    if uq_labels is None:
+        uq_labels = np.unique(labels)
+    lut = np.zeros(np.max(uq_labels) + 1)
+    for number, label in enumerate(uq_labels):
+        lut[label] = number
+    return lut[labels].astype(labels.dtype).tolist()
+
+
+# ---- the table and what follows from it ----
+
+def contingency_host(y_true, y_pred):
+    """the numpy statement of ``imsegm_score_pairs`` for one pair of equally long integer vectors: (labels [U] ascending over
+    both, int64 table [U, U] with ``table[a, b]`` = number of elements with ``y_true == labels[a]`` and ``y_pred == labels[b]``)"""
+    y_true, y_pred = np.asarray(y_true).ravel(), np.asarray(y_pred).ravel()
+    labels, dense = np.unique(np.concatenate([y_true, y_pred]), return_inverse=True)
+    dense = dense.ravel()
+    flat = dense[:len(y_true)].astype(np.int64) * len(labels) + dense[len(y_true):]
+    return labels, np.bincount(flat, minlength=len(labels) ** 2).reshape(len(labels), len(labels)).astype(np.int64)
+
+
+def _divide_or_zero(numerator, denominator):
+    """scikit-learn's ``_prf_divide`` with its default ``zero_division``: 0 where nothing is in the denominator"""
+    numerator, denominator = np.asarray(numerator, dtype=np.float64), np.asarray(denominator, dtype=np.float64)
+    empty = denominator == 0.
+    result = numerator / np.where(empty, 1., denominator)
+    result[empty] = 0.
+    return result
+
+
+def _prf_from_table(table, average):
+    """``metrics.precision_recall_fscore_support(y_true, y_pred, average=average)`` of scikit-learn 1.7 from the table over the
+    labels present (for 'binary' over 0 / 1 with 1 the positive label): (precision, recall, f1, None); ValueError where
+    scikit-learn raises one ('binary' with more than two labels)"""
+    hits, true_sum, pred_sum = np.diag(table), table.sum(axis=1), table.sum(axis=0)
+    if average == 'binary':
+        if len(table) > 2:
+            raise ValueError("Target is multiclass but average='binary'")
+        # one label only: it is label 0 and the positive label 1 has no element
+        hits, true_sum, pred_sum = (part[1:2] if len(table) == 2 else np.zeros(1, dtype=np.int64) for part in (hits, true_sum, pred_sum))
+    elif average == 'micro':
+        hits, true_sum, pred_sum = (np.array([part.sum()]) for part in (hits, true_sum, pred_sum))
+    precision, recall = _divide_or_zero(hits, pred_sum), _divide_or_zero(hits, true_sum)
+    f_score = _divide_or_zero(2. * hits.astype(np.float64), 1. * true_sum.astype(np.float64) + pred_sum.astype(np.float64))
+    if average == 'weighted' and true_sum.sum() != 0:
+        return tuple(float(np.average(part, weights=true_sum)) for part in (precision, recall, f_score)) + (None, )
+    return tuple(float(np.nanmean(part)) for part in (precision, recall, f_score)) + (None, )
+
+
+def _ars_from_table(table):
+    """``metrics.adjusted_rand_score`` from the table: scikit-learn's pair-confusion formula on Python integers"""
+    n_samples = int(table.sum())
+    by_true, by_pred = [int(v) for v in table.sum(axis=1)], [int(v) for v in table.sum(axis=0)]
+    cells = [[int(v) for v in row] for row in table]
+    sum_squares = sum(v * v for row in cells for v in row)
+    both = sum_squares - n_samples                                                       # pairs together in both maps
+    pred_only = sum(v * by_pred[b] for row in cells for b, v in enumerate(row)) - sum_squares
+    true_only = sum(v * by_true[a] for a, row in enumerate(cells) for v in row) - sum_squares
+    neither = n_samples ** 2 - pred_only - true_only - sum_squares
+    if true_only == 0 and pred_only == 0:
+        return 1.0
+    # (scikit-learn: tn = neither, fp = pred_only, fn = true_only, tp = both)
+    return 2.0 * (both * neither - true_only * pred_only) / ((both + true_only) * (true_only + neither) + (both + pred_only) * (pred_only + neither))
+
+
+def _metrics_from_table(labels, table, metric_averages):
+    """the dictionary of :func:`compute_classif_metrics` from the sorted labels present and their contingency table (at least one
+    element): every value is a few fp64 operations on exact integers.  At most two labels count as 0 / 1 (the reference relabels
+    them so); an average scikit-learn refuses gives -1 four times (the reference catches it so)."""
+    table = np.asarray(table, dtype=np.int64)
+    result = {'ARS': _ars_from_table(table), 'accuracy': float(np.trace(table) / table.sum()), 'confusion': table.tolist()}
+    for average in metric_averages:
+        try:
+            values = _prf_from_table(table, average)
+        except ValueError:
+            values = (-1, ) * 4
+        result.update(zip(['%s_%s' % (name, average) for name in ('precision', 'recall', 'f1', 'support')], values))
+    return result
+
+
+def _confusion_cells(labels, table, label_positive=None):
+    """:func:`compute_tp_tn_fp_fn` from the labels present and their table"""
+    labels = [int(label) for label in labels]
+    if len(labels) > 2:
+        logging.debug('too many labels: %r', labels)
+        return np.nan, np.nan, np.nan, np.nan
+    if len(labels) < 2:
+        logging.debug('only one label: %r', labels)
+        return int(np.sum(table)), 0, 0, 0
+    positive = labels.index(label_positive) if label_positive is not None and label_positive in labels else 1
+    negative = 1 - positive
+    # (the reference's names: "fp" counts the positive annotation with a negative segmentation, "fn" the other way round)
+    return table[positive, positive], table[negative, negative], table[positive, negative], table[negative, positive]
+
+
+def _ratio_fpfn_tpfn(tp, fp, fn):
+    if tp == np.nan:                 # (never holds, as in the reference: NaN cells run through the division)
+        return np.nan
+    if (fp + fn) == 0:
+        return 0.
+    return float(fp + fn) / float(tp + fn)
+
+
+def _ratio_tpfp_tpfn(tp, fp, fn):
+    if tp == np.nan:
+        return np.nan
+    if (tp + fn) == 0:
+        return 0.
+    return float(tp + fp) / float(tp + fn)
+
+
+def _present(labels, table):
+    """labels and table without the labels no element carries on either side"""
+    keep = (table.sum(axis=0) + table.sum(axis=1)) > 0
+    return np.asarray(labels)[keep], table[np.ix_(keep, keep)]
+
+
+def _relabel_table(labels, table):
+    """``relabel_max_overlap_unique(y_true, y_pred, keep_bg=False)`` applied to the COLUMNS of the table instead of the pixels:
+    (labels, table) of the relabelled pair, or None where the host has to relabel the pixels (no non-negative label on a side, a
+    label above ``RELABEL_MAX_LABEL``)"""
+    labels = np.asarray(labels, dtype=np.int64)
+    in_true, in_pred = table.sum(axis=1) > 0, table.sum(axis=0) > 0
+    top_true, top_pred = int(labels[in_true].max()), int(labels[in_pred].max())
+    if min(top_true, top_pred) < 0 or max(top_true, top_pred) > RELABEL_MAX_LABEL:
+        return None
+    if int(labels[in_pred].min()) < -(top_pred + 1):
+        return None                  # (the host's look-up has no entry that far from its end: the reference's IndexError is its to raise)
+    overlap = np.zeros((top_true + 1, top_pred + 1), dtype=np.int64)
+    counted = labels >= 0
+    overlap[np.ix_(labels[counted & in_true], labels[counted & in_pred])] = table[np.ix_(counted & in_true, counted & in_pred)]
+    lut = np.array(max_overlap_unique_lut(overlap, keep_bg=False), dtype=np.int64)
+    renamed = np.where(labels < 0, labels, lut[np.clip(labels, 0, top_pred)])          # negative labels keep their column
+    union = np.unique(np.concatenate([labels[in_true], renamed[in_pred]]))
+    moved = np.zeros((len(union), len(union)), dtype=np.int64)
+    rows, cols = np.searchsorted(union, labels[in_true]), np.searchsorted(union, renamed[in_pred])
+    np.add.at(moved, np.ix_(rows, cols), table[np.ix_(in_true, in_pred)])
+    return union, moved
+
+
+def _device_vector(arr):
+    """the array as the flat C-contiguous uint8 / int32 vector ``_hip.score_pairs`` takes, or None: not integers, outside int32"""
+    arr = np.asarray(arr)
+    if arr.dtype.kind not in 'iu':
+        return None
+    if arr.dtype != np.uint8:
+        if arr.size and (arr.dtype.itemsize > 4 or arr.dtype == np.uint32) and (int(arr.min()) < -2 ** 31 or int(arr.max()) >= 2 ** 31):
+            return None
+        arr = arr.astype(np.int32, copy=False)
+    return np.ascontiguousarray(arr).ravel()
+
+
+def _device_drop(drop_labels):
+    """the drop list as int32, or None where the device does not take it"""
+    if drop_labels is None:
+        return np.zeros(0, dtype=np.int32)
+    try:
+        drop = np.asarray(list(drop_labels))
+    except TypeError:
+        return None
+    if drop.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if drop.ndim != 1 or drop.dtype.kind not in 'iu' or len(drop) > _hip.SCORE_MAX_DROP or drop.min() < -2 ** 31 or drop.max() >= 2 ** 31:
+        return None
+    return drop.astype(np.int32)
+
+
+def _device_tables(pairs, drop_labels):
+    """(labels, table) over the labels present per ``(y_true, y_pred)`` of ``pairs`` from ONE ``_hip.score_pairs`` call; None in
+    place of a pair the host statement has to take: arrays the device does not take, too many labels, no element left"""
+    results = [None] * len(pairs)
+    drop = _device_drop(drop_labels)
+    if drop is None:
+        return results
+    vectors = [(_device_vector(y_true), _device_vector(y_pred)) for y_true, y_pred in pairs]
+    taken = [i for i, (v_true, v_pred) in enumerate(vectors) if v_true is not None and v_pred is not None and v_true.size == v_pred.size]
+    if not taken:
+        return results
+    if any(vector.dtype != np.uint8 for i in taken for vector in vectors[i]):       # one dtype per call: int32 unless all are bytes
+        vectors = [tuple(v if v is None else v.astype(np.int32, copy=False) for v in pair) for pair in vectors]
+    scored = _hip.score_pairs([vectors[i][0] for i in taken], [vectors[i][1] for i in taken], drop)
+    for i, answer in zip(taken, scored):
+        if answer != _hip.SCORE_TOO_MANY_LABELS and len(answer[0]):
+            results[i] = (answer[0].astype(np.int64), answer[1])
+    return results
+
+
+# ---- the public functions ----
+
+def _metrics_host(y_true, y_pred, metric_averages):
+    """the host statement of :func:`compute_classif_metrics`: scikit-learn on the vectors"""
+    from sklearn import metrics
+    logging.debug('unique lbs true: %r, predict %r', np.unique(y_true), np.unique(y_pred))
+    present = np.unique(np.hstack((y_true, y_pred)))
+    if len(present) <= 2:
+        # pos_label=1 has to be a label: two labels count as 0 / 1 for the statistic
+        y_true, y_pred = relabel_sequential(y_true, present), relabel_sequential(y_pred, present)
+    result = {'ARS': metrics.adjusted_rand_score(y_true, y_pred), 'accuracy': metrics.accuracy_score(y_true, y_pred),
+              'confusion': metrics.confusion_matrix(y_true, y_pred).tolist()}
+    for average in metric_averages:
+        keys = ['%s_%s' % (name, average) for name in ('precision', 'recall', 'f1', 'support')]
+        try:
+            values = metrics.precision_recall_fscore_support(y_true, y_pred, average=average)
+        except Exception:
+            logging.exception('metrics.precision_recall_fscore_support')
+            values = [-1] * 4
+        result.update(zip(keys, values))
+    return result
+
+
+def compute_classif_metrics(y_true, y_pred, metric_averages=METRIC_AVERAGES, on=None):
+    """ standard metrics for multi-class classification (``classification.py:305-371``): ARS, accuracy, the confusion matrix over
+    the labels present and precision / recall / F1 / support per average
+
+    :param list(int) y_true: annotation
+    :param list(int) y_pred: prediction
+    :param str|list(str) metric_averages: averages of ``precision_recall_fscore_support``
+    :param str on: None, 'host' or 'device'
+    :return dict(float):
+    """
+    y_true, y_pred = np.array(y_true), np.array(y_pred)
+    if y_true.shape != y_pred.shape:
+        raise ValueError('prediction (%i) and annotation (%i) should be equal' % (len(y_true), len(y_pred)))
+    if _place(on, 'compute_classif_metrics') == 'device' and all(average in _TABLE_AVERAGES for average in metric_averages):
+        counted = _device_tables([(y_true, y_pred)], None)[0]
+        if counted is not None:
+            return _metrics_from_table(counted[0], counted[1], metric_averages)
+    return _metrics_host(y_true, y_pred, metric_averages)
+
+
+def _relabel_host(y_true, y_pred):
+    """``relabel_max_overlap_unique(y_true, y_pred, keep_bg=False)`` on the vectors in numpy: overlap of the non-negative labels,
+    the table of ``labeling.max_overlap_unique_lut``, negative labels stay"""
+    extents = [int(np.max(y_true)) + 1, int(np.max(y_pred)) + 1]
+    overlap = np.zeros(extents, dtype=np.int64)
+    counted = (y_true >= 0) & (y_pred >= 0)
+    np.add.at(overlap, (y_true[counted], y_pred[counted]), 1)
+    renamed = np.array(max_overlap_unique_lut(overlap, keep_bg=False))[y_pred].astype(np.int64)
+    renamed[y_pred < 0] = y_pred[y_pred < 0]
+    return renamed
+
+
+def _stat_from_vectors(y_true, y_pred, name, drop_labels, relabel):
+    """the host statement of :func:`compute_classif_stat_segm_annot` on the flat vectors"""
+    if drop_labels is not None:
+        keep = np.ones(y_true.shape, dtype=bool)
+        for label in drop_labels:
+            keep[y_true == label] = False
+            keep[y_pred == label] = False
+        y_true, y_pred = y_true[keep], y_pred[keep]
+    if relabel:
+        y_pred = _relabel_host(y_true, y_pred)
+    stat = _metrics_host(y_true, y_pred, ['macro'])
+    if len(np.unique(y_pred)) == 2:
+        stat['(FP+FN)/(TP+FN)'] = compute_metric_fpfn_tpfn(y_true, y_pred, on='host')
+        stat['(TP+FP)/(TP+FN)'] = compute_metric_tpfp_tpfn(y_true, y_pred, on='host')
+    stat['name'] = name
+    return stat
+
+
+def _stat_from_table(labels, table, name, relabel):
+    """:func:`compute_classif_stat_segm_annot` from the labels present and their table, or None where the host has to relabel"""
+    if relabel:
+        moved = _relabel_table(labels, table)
+        if moved is None:
+            return None
+        labels, table = moved
+    stat = _metrics_from_table(labels, table, ['macro'])
+    if np.count_nonzero(table.sum(axis=0)) == 2:
+        tp, _, fp, fn = _confusion_cells(labels, table)
+        stat['(FP+FN)/(TP+FN)'] = _ratio_fpfn_tpfn(tp, fp, fn)
+        stat['(TP+FP)/(TP+FN)'] = _ratio_tpfp_tpfn(tp, fp, fn)
+    stat['name'] = name
+    return stat
+
+
+def _stats(triples, drop_labels, relabel, place):
+    """the dictionaries of all ``(annot, segm, name)``: the pairs the device takes in one call, the others by the host statement"""
+    triples = list(triples)
+    for annot, segm, _ in triples:
+        if segm.shape != annot.shape:
+            raise ImageDimensionError('dimension do not match for segm: %r - annot: %r' % (segm.shape, annot.shape))
+    counted = _device_tables([(annot, segm) for annot, segm, _ in triples], drop_labels) if place == 'device' else [None] * len(triples)
+    stats = []
+    for (annot, segm, name), answer in zip(triples, counted):
+        stat = _stat_from_table(answer[0], answer[1], name, relabel) if answer is not None else None
+        stats.append(stat if stat is not None else _stat_from_vectors(annot.ravel(), segm.ravel(), name, drop_labels, relabel))
+    return stats
+
+
+def compute_classif_stat_segm_annot(annot_segm_name, drop_labels=None, relabel=False, on=None):
+    """ classification statistic between an annotation and a segmentation (``classification.py:374-421``): the metrics with the
+    macro average over the elements where neither map carries a drop label, the two binary ratios when the segmentation holds
+    exactly two labels, and the name
+
+    :param tuple(ndarray,ndarray,str) annot_segm_name: annotation, segmentation, name
+    :param list(int) drop_labels: labels to be ignored
+    :param bool relabel: relabel the segmentation such that its labels match the annotation's best
+    :param str on: None, 'host' or 'device'
+    :return dict:
+    """
+    annot, segm, name = annot_segm_name
+    return _stats([(annot, segm, name)], drop_labels, relabel, _place(on, 'compute_classif_stat_segm_annot'))[0]
+
+
+def compute_stat_per_image(segms, annots, names=None, nb_workers=2, drop_labels=None, relabel=False, on=None):
+    """ statistic over several segmentations with annotations (``classification.py:424-471``): one row per image, indexed by
+    its name.  On the device all pairs go through one ``score_pairs`` call.
+
+    :param list(ndarray) segms: segmentations
+    :param list(ndarray) annots: annotations
+    :param list(str) names: list of names
+    :param int nb_workers: accepted for the reference's callers; neither place starts workers
+    :param list(int) drop_labels: labels to be ignored
+    :param bool relabel: whether relabel
+    :param str on: None, 'host' or 'device'
+    :return DF:
+    """
+    import pandas as pd
+    if len(segms) != len(annots):
+        raise RuntimeError('size of segment. (%i) amd annot. (%i) should be equal' % (len(segms), len(annots)))
+    if not names:
+        names = map(str, range(len(segms)))
+    frame = pd.DataFrame(_stats(zip(annots, segms, names), drop_labels, relabel, _place(on, 'compute_stat_per_image')))
+    frame.set_index('name', inplace=True)
+    return frame
+
+
+def compute_tp_tn_fp_fn(annot, segm, label_positive=None, on=None):
+    """ TruePositive, TrueNegative, FalsePositive, FalseNegative of two maps with two labels between them
+    (``classification.py:1265-1310``); four NaN for more labels, ``(size, 0, 0, 0)`` for one.  As in the reference "FP" counts the
+    positive annotation under a negative segmentation and "FN" the other way round.
+
+    :param ndarray annot: annotation
+    :param ndarray segm: segmentation
+    :param int label_positive: the positive label (default and when absent: the larger one)
+    :param str on: None, 'host' or 'device'
+    :return tuple(float,float,float,float):
+    """
+    y_true, y_pred = np.asarray(annot).ravel(), np.asarray(segm).ravel()
+    if _place(on, 'compute_tp_tn_fp_fn') == 'device' and y_true.shape == y_pred.shape:
+        counted = _device_tables([(y_true, y_pred)], None)[0]
+        if counted is not None:
+            return _confusion_cells(counted[0], counted[1], label_positive)
+    present = np.unique([y_true, y_pred]).tolist()
+    if len(present) > 2:
+        logging.debug('too many labels: %r', present)
+        return np.nan, np.nan, np.nan, np.nan
+    if len(present) < 2:
+        logging.debug('only one label: %r', present)
+        return len(y_true), 0, 0, 0
+    if label_positive is None or label_positive not in present:
+        label_positive = present[-1]
+    present.remove(label_positive)
+    label_negative = present[0]
+    tp = np.sum((y_true == label_positive) & (y_pred == label_positive))
+    tn = np.sum((y_true == label_negative) & (y_pred == label_negative))
+    fp = np.sum((y_true == label_positive) & (y_pred == label_negative))
+    fn = np.sum((y_true == label_negative) & (y_pred == label_positive))
+    return tp, tn, fp, fn
+
+
+def compute_metric_fpfn_tpfn(annot, segm, label_positive=None, on=None):
+    """ the measure (FP + FN) / (TP + FN) of :func:`compute_tp_tn_fp_fn` (``classification.py:1313-1337``)
+
+    :param ndarray annot: annotation
+    :param ndarray segm: segmentation
+    :param int label_positive: the positive label
+    :param str on: None, 'host' or 'device'
+    :return float:
+    """
+    tp, _, fp, fn = compute_tp_tn_fp_fn(annot, segm, label_positive, on=on)
+    return _ratio_fpfn_tpfn(tp, fp, fn)
+
+
+def compute_metric_tpfp_tpfn(annot, segm, label_positive=None, on=None):
+    """ the measure (TP + FP) / (TP + FN) of :func:`compute_tp_tn_fp_fn` (``classification.py:1340-1366``)
+
+    :param ndarray annot: annotation
+    :param ndarray segm: segmentation
+    :param int label_positive: the positive label
+    :param str on: None, 'host' or 'device'
+    :return float:
+    """
+    tp, _, fp, fn = compute_tp_tn_fp_fn(annot, segm, label_positive, on=on)
+    return _ratio_tpfp_tpfn(tp, fp, fn)

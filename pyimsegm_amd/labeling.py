@@ -309,8 +309,14 @@ def relabel_max_overlap_unique(seg_ref, seg_relabel, keep_bg=False):
     seg_ref, seg_relabel = np.asarray(seg_ref), np.asarray(seg_relabel)
     if seg_ref.shape != seg_relabel.shape:
         raise ImageDimensionError('Reference segm. %r and input segm. %r should match' % (seg_ref.shape, seg_relabel.shape))
-    overlap = compute_labels_overlap_matrix(seg_ref, seg_relabel)
-    lut = [-1] * (np.max(seg_relabel) + 1)
+    lut = max_overlap_unique_lut(compute_labels_overlap_matrix(seg_ref, seg_relabel), keep_bg)
+    return _keep_negative(np.array(lut)[seg_relabel].astype(np.int64), seg_relabel)
+
+
+def max_overlap_unique_lut(overlap, keep_bg=False):
+    """the look-up table of :func:`relabel_max_overlap_unique` from the overlap matrix of the two maps (rows: reference labels,
+    columns: labels ``0 .. max`` of the map to relabel; the matrix is used up): a list with the new label of every column"""
+    lut = [-1] * overlap.shape[1]
     if keep_bg:
         lut[0] = 0
         overlap[0, :] = 0
@@ -334,7 +340,7 @@ def relabel_max_overlap_unique(seg_ref, seg_relabel, keep_bg=False):
         if lut[idx] == -1:
             lut[idx] = max(free for free in range(len(lut)) if free not in taken)
             taken.add(lut[idx])
-    return _keep_negative(np.array(lut)[seg_relabel].astype(np.int64), seg_relabel)
+    return lut
 
 
 def relabel_max_overlap_merge(seg_ref, seg_relabel, keep_bg=False):
