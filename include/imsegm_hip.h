@@ -129,6 +129,16 @@ IMSEGM_API int imsegm_image2d_set_labels(imsegm_image2d *img, const int32_t *lab
  * tile path of csrc/connectivity.hip and were redone by the general one (results are identical; tests use it to make sure
  * ordinary inputs stay on the fast path). */
 IMSEGM_API long imsegm_debug_conn_general_runs(void);
+/* Diagnostic (no reference counterpart): which kernels finished the last single-map connectivity pass of this process -- the
+ * counters the host reads at the synchronisations it makes anyway (no kernel, copy or synchronisation of its own).  28 ints:
+ *   [0]      1 when the 2-D tile path was attempted, [1] 1 when the general path ran, [2] rounds of the general path that
+ *            truncated an oversize component (0: none reached max_size), [3] unused
+ *   [4..19]  the 16 counters of the tile attempt (csrc/connectivity.hip CNT_*: 0 oversize, 1 small, 3 kept, 4 wave-BFS rejects,
+ *            9 a tile beyond its slots, 10 / 11 components handed to the 128 K tile / to the LDS-frontier kernel)
+ *   [20..27] the counters of the general path's last tail (0 oversize, 1 small, 3 kept, 4 components the thread BFS took from
+ *            the wave kernel, 5 / 6 big / little bounding boxes)
+ * The batch entry does not record. */
+IMSEGM_API int imsegm_debug_conn_last(int32_t *out28);
 /* Diagnostic (no reference counterpart): 2-D SLIC runs of this process whose sweeps 2..max_iter ran in the ONE persistent launch
  * of csrc/slic.hip (k_slic_sweeps), and how many of those gave the image back to the per-sweep launches (results are identical;
  * tests use it to make sure ordinary images stay on the persistent path, bench.py to know how many sweeps one launch covers). */

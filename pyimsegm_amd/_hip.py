@@ -118,6 +118,7 @@ _SIGNATURES = {
     'imsegm_image2d_set_labels': (C.c_int, [_vp, _vp, C.c_int]),
     'imsegm_image2d_enforce_connectivity': (C.c_int, [_vp, _vp, C.c_long, C.c_long, C.c_int, _vp]),
     'imsegm_debug_conn_general_runs': (C.c_long, []),
+    'imsegm_debug_conn_last': (C.c_int, [_vp]),
     'imsegm_debug_slic_sweep_runs': (C.c_int, [_vp, _vp]),
     'imsegm_debug_gc_grid_fallbacks': (C.c_long, []),
     'imsegm_debug_exclusive_scan': (C.c_int, [_vp, C.c_int, _vp, _ip]),
@@ -1526,6 +1527,22 @@ class DeviceArray(object):
         self.owner = owner          # keeps the session alive
         self.__cuda_array_interface__ = {'shape': tuple(shape), 'typestr': typestr, 'data': (int(ptr), False),
                                          'version': 2, 'strides': None}
+
+
+#: names of the counters of csrc/connectivity.hip (CNT_*) by index
+CONN_COUNTERS = {'over': 0, 'small': 1, 'cursor': 2, 'kept': 3, 'fallback': 4, 'big': 5, 'little': 6, 'lroot': 8, 'flag': 9,
+                 'fb': 10, 'fb2': 11}
+
+
+def conn_last():
+    """which kernels finished the last single-map connectivity pass of this process (imsegm_debug_conn_last): a dict with
+    ``tile`` (counters of the tile attempt by name, None when none was made), ``general`` (counters of the general path's tail,
+    None when it did not run) and ``oversize_rounds``; for tests"""
+    raw = np.zeros(28, np.int32)
+    _check(load_library().imsegm_debug_conn_last(_ptr(raw)))
+    tile = {k: int(raw[4 + i]) for k, i in CONN_COUNTERS.items()} if raw[0] else None
+    general = {k: int(raw[20 + i]) for k, i in CONN_COUNTERS.items() if i < 8} if raw[1] else None
+    return {'tile': tile, 'general': general, 'oversize_rounds': int(raw[2])}
 
 
 def gc_grid_fallbacks():

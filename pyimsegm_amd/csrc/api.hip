@@ -307,6 +307,16 @@ int imsegm_image2d_upload(imsegm_image2d *im, const void *host_pixels, int dtype
 
 long imsegm_debug_conn_general_runs(void) { return conn_general_runs(); }
 
+int imsegm_debug_conn_last(int32_t *out28)
+{
+    if (!out28) {
+        set_error("null argument");
+        return -1;
+    }
+    conn_last(out28);
+    return 0;
+}
+
 void imsegm_debug_reload_env(void) { reload_knobs(); }
 
 long imsegm_debug_gc_grid_fallbacks(void) { return gc_grid_fallbacks(); }

@@ -752,6 +752,57 @@ k_small_bfs_fallback(const int32_t *__restrict__ list_all, const int32_t *__rest
     }
 }
 
+// Start label 1 and a FIRST segment below min_size: the reference writes `adjacent` = 0 over it, which is the mask label there, so
+// the scan seeds its remaining voxels again -- each time over the whole component, now with more labelled neighbours -- and so on
+// for every small component all of whose earlier neighbours are still 0.  "Already labelled" is then no longer "smaller root", and
+// the concurrent BFS kernels above do not apply: this replays the scan itself, one thread, over the small components (every other
+// component has an earlier neighbour, so with a kept first component none of this can happen and the kernel returns at once).
+// adjptr[root] = the kept root the component takes its label from, -1 if it stays 0.  HOP2: as in k_small_bfs_wave.
+template <bool HOP2>
+__global__ void __launch_bounds__(256)
+k_small_rescan(const int32_t *__restrict__ parent, const int32_t *__restrict__ csize, const int32_t *__restrict__ counters,
+               int D, int H, int W, int min_size, int32_t *queue, uint8_t *visited, int32_t *adjptr, size_t zs)
+{
+    ZSHIFT(parent, zs); ZSHIFT(csize, zs); ZSHIFT(counters, zs); ZSHIFT(queue, zs); ZSHIFT(visited, zs); ZSHIFT(adjptr, zs);
+    if (HOP2 && counters[CNT_FLAG]) return;
+    if (csize[0] >= min_size) return;                    // (block-uniform; voxel 0 is the root of its component)
+    const int n = D * H * W;
+    uint8_t *done = visited + n;                         // per root: labelled by now
+    for (size_t i = threadIdx.x; i < 2 * (size_t)n; i += 256) visited[i] = 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int v = 0; v < n; ++v) {
+        int r = parent[v];
+        if (HOP2) r = parent[r];
+        if (csize[r] >= min_size || done[r]) continue;
+        int adj = -1, qs = 1;
+        queue[0] = v;
+        visited[v] = 1;
+        for (int i = 0; i < qs; ++i) {
+            const int p = queue[i];
+            for (int j = 0; j < 6; ++j) {
+                const int t = neighbour(p, D, H, W, j);
+                if (t < 0) continue;
+                int c = parent[t];
+                if (HOP2) c = parent[c];
+                if (c == r) {
+                    if (!visited[t]) {
+                        visited[t] = 1;
+                        queue[qs++] = t;
+                    }
+                } else if (csize[c] >= min_size) {
+                    if (c < v) adj = c;                  // (a kept component is labelled from its first voxel on)
+                } else if (done[c]) {
+                    adj = adjptr[c];
+                }
+            }
+        }
+        for (int i = 0; i < qs; ++i) visited[queue[i]] = 0;
+        if (adj >= 0) done[r] = 1;
+        adjptr[r] = adj;
+    }
+}
+
 // (four voxels per lane where the arrays are 16-byte aligned)
 __global__ void __launch_bounds__(256)
 k_write_labels(const int32_t *__restrict__ parent, const int32_t *__restrict__ newlabel, int n, int32_t *out,
@@ -937,6 +988,9 @@ static int conn_tail(const int32_t *csize_final, int32_t *adjptr, int D, int H, 
                        bbox, D, H, W, w.queue, capacity, adjptr, fallback_list, (size_t)0);
     hipLaunchKernelGGL(k_small_bfs_fallback, 64, 64, 0, st, w.list, fallback_list, w.counters, w.parent, csize_final, D, H,
                        W, capacity, w.queue, w.visited, w.counters + CNT_CURSOR, adjptr);
+    if (start_label == 1)                             // (w.queue and both halves of the byte scratch are free by now)
+        hipLaunchKernelGGL(k_small_rescan<false>, 1, 256, 0, st, w.parent, csize_final, w.counters, D, H, W, min_size, w.queue, w.visited,
+                           adjptr, (size_t)0);
     hipLaunchKernelGGL(k_small_resolve, 64, 64, 0, st, w.list, w.counters, csize_final, adjptr, min_size, w.newlabel);
     hipLaunchKernelGGL(k_write_labels, cdiv(cdiv(n, 4), 256), 256, 0, st, w.parent, w.newlabel, n, labels_out, (const int32_t *)nullptr, (size_t)0);
     HIP_TRY(hipGetLastError());
@@ -962,13 +1016,22 @@ static int conn_tail(const int32_t *csize_final, int32_t *adjptr, int D, int H, 
 //                   (+2 rings) staged in LDS as one byte per cell
 //   k_small_resolve, k_lroot_labels, k_write_labels   chains of merged components, labels of the local roots, and
 //                   out[p] = newlabel[parent[p]]
-// Anything the fast path cannot take (more than 64 local components in a tile, list capacities, a frontier of more
+// Anything the fast path cannot take (more than 256 local components in a tile -- CT_SLOTS --, list capacities, a frontier of more
 // than 64 cells and a bounding box the old wave kernel cannot stage either, an oversize component) raises a flag /
 // counter that the host reads at its single synchronisation, and the general path above runs instead.
 constexpr int CT_W = 64, CT_H = 32, CT_SLOTS = 256;      // (config-4 images: up to 83 local components in a tile)
 constexpr int CONN_KEPT_CAP = 1 << 16, CONN_FB_CAP = 4096;
 static_assert(2 * CONN_KEPT_CAP + 16 * CONN_FB_CAP <= CONN_DENSE_INTS, "dense scratch of the tile path");
 static_assert(CT_W * CT_H == CONN_TILE_PIXELS && CT_SLOTS == CONN_TILE_SLOTS, "sizes used by conn_i32_bytes (slic.h)");
+
+// What the last single-map call of this process went through (diagnostic, imsegm_debug_conn_last): the counters the host holds
+// after the synchronisations it makes anyway.  Relaxed atomics: plain stores, and no data race between sessions on other threads.
+enum { CL_TILE_TRIED = 0, CL_GENERAL_RAN = 1, CL_OVERSIZE_ROUNDS = 2, CL_TILE = 4, CL_GENERAL = 20, CL_INTS = 28 };
+static std::atomic<int32_t> g_conn_last[CL_INTS];
+void conn_last(int32_t *out)
+{
+    for (int i = 0; i < CL_INTS; ++i) out[i] = g_conn_last[i].load(std::memory_order_relaxed);
+}
 
 struct ConnDense {
     int32_t *lroots, *lsize, *lbox, *ntile, *kept, *sorted, *fb_list, *fb_reject, *fb_bbox, *fb2_list, *fb2_bbox;
@@ -1525,6 +1588,9 @@ static int conn_fast_2d(const int32_t *labels_in, int H, int W, int min_size, in
     // sends the image to the general path
     hipLaunchKernelGGL((k_small_bfs_wave<8192, 2048, true>), dim3(nz > 1 ? 64 : 256, 1, nz), 64, 0, st, d.fb2_list, w.counters, w.counters + CNT_FB2,
                        w.parent, d.fb2_bbox, 1, H, W, (const int32_t *)nullptr, CONN_FB_CAP, w.adjptr, d.fb_reject, zs);
+    if (start_label == 1)                             // (ymax_g in w.queue has been read for the last time)
+        hipLaunchKernelGGL(k_small_rescan<true>, dim3(1, 1, nz), 256, 0, st, w.parent, w.csize, w.counters, 1, H, W, min_size, w.queue,
+                           w.visited, w.adjptr, zs);
     hipLaunchKernelGGL(k_lroot_labels, lgrid, 256, 0, st, d.lroots, d.ntile, n_slots, w.counters, w.parent, w.csize, w.adjptr, min_size,
                        w.newlabel, zs);
     hipLaunchKernelGGL(k_write_labels, dim3(cdiv(cdiv(n, 4), 256), 1, nz), 256, 0, st, w.parent, w.newlabel, n, labels_out,
@@ -1539,6 +1605,10 @@ static int conn_fast_2d(const int32_t *labels_in, int H, int W, int min_size, in
         HIP_TRY(hipMemcpyAsync(host_counters.data(), stage, (size_t)nz * 16 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
+    if (nz == 1) {
+        g_conn_last[CL_TILE_TRIED].store(1, std::memory_order_relaxed);
+        for (int i = 0; i < 16; ++i) g_conn_last[CL_TILE + i].store(host_counters[i], std::memory_order_relaxed);
+    }
     for (unsigned b = 0; b < nz; ++b) {
         const int32_t *hc = host_counters.data() + (size_t)16 * b;
         ok[b] = hc[CNT_FLAG] == 0 && hc[CNT_OVER] == 0 && hc[CNT_FALLBACK] == 0 && hc[CNT_KEPT] <= CONN_KEPT_CAP &&
@@ -1579,6 +1649,9 @@ int launch_enforce_connectivity(const int32_t *labels_in, int D, int H, int W, l
     const int max_size = (int)std::min<long>(max_size_l, 0x7fffffff);
     uint8_t *state = w.visited + n;       // second half of the byte scratch (2 * n bytes)
     int32_t host_counters[16];
+    int oversize_rounds = 0;
+    g_conn_last[CL_TILE_TRIED].store(0, std::memory_order_relaxed);
+    g_conn_last[CL_GENERAL_RAN].store(0, std::memory_order_relaxed);
 
     if (D == 1 && !knobs().conn_general) {
         bool ok = false;
@@ -1613,6 +1686,7 @@ int launch_enforce_connectivity(const int32_t *labels_in, int D, int H, int W, l
             HIP_TRY(hipStreamSynchronize(st));
             int n_over = host_counters[CNT_OVER];
             if (n_over > 0) {
+                ++oversize_rounds;
                 if ((long)n_over * max_size > (long)n) {
                     set_error("enforce_connectivity: internal queue overflow");
                     return -1;
@@ -1634,6 +1708,9 @@ int launch_enforce_connectivity(const int32_t *labels_in, int D, int H, int W, l
     }
     int n_kept = host_counters[CNT_KEPT];
     *n_labels_out_host = n_kept > 0 ? start_label + n_kept : 1;
+    g_conn_last[CL_GENERAL_RAN].store(1, std::memory_order_relaxed);
+    g_conn_last[CL_OVERSIZE_ROUNDS].store(oversize_rounds, std::memory_order_relaxed);
+    for (int i = 0; i < 8; ++i) g_conn_last[CL_GENERAL + i].store(host_counters[i], std::memory_order_relaxed);
     return 0;
 }
 

@@ -179,6 +179,7 @@ static inline size_t conn_i32_bytes(size_t n, size_t H = 0, size_t W = 0)
 int launch_label_connected(int32_t *labels_inout, size_t n, int n_labels, int32_t *first, uint32_t *bitmap, int32_t *blocksum,
                            int32_t *counters, int32_t *total_dev, hipStream_t st);
 long conn_general_runs();      // diagnostic: 2-D maps that left the tile path so far
+void conn_last(int32_t *out);  // diagnostic: the host's counters of the last single-map call (28 ints, include/imsegm_hip.h)
 long gc_grid_fallbacks();      // diagnostic: grid-wide cuts given up (a workgroup not resident) and redone by the single workgroup
 int launch_enforce_connectivity(const int32_t *labels_in, int D, int H, int W, long min_size, long max_size,
                                 int start_label, ConnWork w, int32_t *labels_out, int *n_labels_out_host,
