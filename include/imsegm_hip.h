@@ -41,7 +41,7 @@ extern "C" {
 
 /* status of imsegm_object_shapes for a map it does not take -- more objects than the caller's capacity, or more than two label
  * values that span IMSEGM_OBJECT_SHAPES_MAX_SPAN or more: nothing is wrong with the context and no error message is set -- the
- * caller evaluates the map on the host */
+ * caller evaluates the map on the host.  imsegm_cut_objects returns it in the same sense for a request outside its caps */
 #define IMSEGM_E_OBJECT_CAPS (-5)
 
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
@@ -791,6 +791,44 @@ IMSEGM_API int imsegm_rg_criterion(imsegm_rg *rg, const int32_t *labels, const d
 IMSEGM_API int imsegm_object_shapes(imsegm_ctx *ctx, const int32_t *segm, int height, int width, const float *directions,
                                     int n_angles, int max_objects, int *n_objects_out, int32_t *labels_out, int64_t *moments_out,
                                     int32_t *centres_out, float *rays_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Cutting every labelled object of an image out, centred and turned level (imsegm/utilities/data_io.py cut_object :1060-1128 as
+ * experiments_ovary_detect/run_cut_segmented_objects.py :93-101 loops it over the labels of an annotation); csrc/cut_objects.hip.
+ * Integers on the device up to the moments, then two composed nearest-neighbour index maps in fp64 without fused operations: same
+ * call, same bytes.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_CUT_OBJECTS_MAX_LABELS 1024     /* labels of one call: the ascending list lives in LDS */
+#define IMSEGM_CUT_OBJECTS_MAX_CHANNELS 4      /* interleaved uint8 channels of the image */
+#define IMSEGM_CUT_MOMENT_WORDS 10             /* int64 per label: count, sum r, sum c, sum r^2, sum c^2, sum r c, r min, r max, c min, c max */
+#define IMSEGM_CUT_GEOMETRY_DOUBLES 8          /* per label: shift s_r, s_c; matrix m00, m01, m10, m11; offset o_r, o_c */
+#define IMSEGM_CUT_FRAME_INTS 6                /* per label: canvas height, width; window r0, r1, c0, c1 (half open) on the canvas */
+/* The fp64 step between the moments and the index maps, supplied by the caller so that it is stated once (the package hands in
+ * the function its host statement uses: centroid = sum / count, scikit-image 0.18.3's orientation, scipy.ndimage.rotate's matrix,
+ * offset and canvas shape).  moments: n_labels x IMSEGM_CUT_MOMENT_WORDS (a label without a pixel has count 0, minima
+ * 0x7f7f7f7f, maxima -1); to fill: geometry_out n_labels x IMSEGM_CUT_GEOMETRY_DOUBLES and frames_out n_labels x
+ * IMSEGM_CUT_FRAME_INTS.  Canvas pixel (i, j) reads the shifted frame at x = ((0 + i m_0) + j m_1) + o per axis, which reads the
+ * source at k + s per axis; at either step a coordinate below 0 or above n - 1 is outside, else the index is floor(x + 0.5).
+ * Outside the window the turned mask must be False.  A return value other than 0 ends the call with -1. */
+typedef int (*imsegm_cut_geometry_fn)(void *user, int n_labels, int allow_rotate, int height, int width, const int64_t *moments,
+                                      double *geometry_out, int32_t *frames_out);
+/* Replaces [cut_object(img, segm == l, padding, use_mask, bg_color, allow_rotate) for l in labels] for a uint8 image (host,
+ * height x width x channels interleaved), an int32 label map (host, height x width) and n_labels strictly ascending labels: the
+ * moments and boxes of all labels in one pass, `geometry` on the host, the exact box of every turned mask inside its window, the
+ * crops (box widened by add_padding :1039-1057 against the canvas) written by one launch and brought down by one copy.  A pixel
+ * from outside the source is 0; with use_mask a crop pixel whose turned mask is False gets bg_color (channels bytes).  The image
+ * and the map are uploaded once each.  Results: moments_out (may be NULL) as handed to the hook; boxes_out[4 k ..] = r0, c0, r1,
+ * c1 of crop k on its canvas; offsets_out[k] (n_labels + 1 entries) = where its (r1 - r0) x (c1 - c0) x channels bytes start in
+ * *packed_out, page-locked memory of the context that stays valid until the next call on it.  *first_empty_out = -1, or the
+ * first label whose turned mask has no pixel (regionprops(...)[0] of the reference raises): then nothing else is written.
+ * Returns 0; IMSEGM_E_OBJECT_CAPS -- no message, the caller evaluates on the host -- for more than
+ * IMSEGM_CUT_OBJECTS_MAX_LABELS labels, more than IMSEGM_CUT_OBJECTS_MAX_CHANNELS channels, 2^31 pixels or more, a padding above
+ * 2^20 (all before anything is launched) and more than 2^30 bytes of crops; -1 with a message for null arguments, sizes below 1, a
+ * negative padding, labels that do not ascend and what the hook refuses. */
+IMSEGM_API int imsegm_cut_objects(imsegm_ctx *ctx, const uint8_t *image, const int32_t *segm, int height, int width, int channels,
+                                  const int32_t *labels, int n_labels, int padding, int use_mask, const uint8_t *bg_color,
+                                  int allow_rotate, imsegm_cut_geometry_fn geometry, void *user, int64_t *moments_out,
+                                  int32_t *boxes_out, int64_t *offsets_out, const uint8_t **packed_out, int *first_empty_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the

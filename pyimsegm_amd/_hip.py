@@ -206,6 +206,8 @@ _SIGNATURES = {
     'imsegm_object_shapes': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _ip, _vp, _vp, _vp, _vp]),
     'imsegm_annot_match': (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, C.c_int, C.c_int, _vp, C.POINTER(C.c_int64)]),
     'imsegm_annot_paint': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp]),
+    'imsegm_cut_objects': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _ip]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
@@ -1893,6 +1895,69 @@ def object_shapes(segm, directions, max_objects=1024, ctx=None):
     _check(status)
     n = count.value
     return n, labels[:n], moments[:n], centres[:n], rays[:n]
+
+
+#: ``IMSEGM_CUT_OBJECTS_MAX_LABELS`` / ``IMSEGM_CUT_OBJECTS_MAX_CHANNELS``
+CUT_OBJECTS_MAX_LABELS, CUT_OBJECTS_MAX_CHANNELS = 1024, 4
+#: ``imsegm_cut_geometry_fn``
+CUT_GEOMETRY_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                              C.POINTER(C.c_int32))
+
+
+def cut_objects(image, segm, labels, padding, use_mask, bg_color, allow_rotate, geometry, ctx=None):
+    """``imsegm_cut_objects``: the crops of all ``labels`` (strictly ascending int32) of the C-contiguous int32 map ``segm`` [H, W] out
+    of the C-contiguous uint8 ``image`` [H, W, C] in one call: (crops -- a list of uint8 arrays [h, w, C] --, moments int64 [n, 10],
+    boxes int32 [n, 4] on the canvases).  ``geometry(moments_row, (H, W), allow_rotate)`` returns the dict of
+    ``utilities.data_io._cut_geometry``; an exception it raises (``IndexError`` for a label without a pixel) is raised here.  A label
+    whose turned mask is empty raises ``IndexError`` as well.  A request outside the caps (``IMSEGM_E_OBJECT_CAPS``) gives None --
+    no error."""
+    if image.dtype != np.uint8 or image.ndim != 3 or not image.flags.c_contiguous or image.size == 0:
+        raise ValueError('the image must be a non-empty C-contiguous uint8 array [H, W, C]')
+    if segm.dtype != np.int32 or segm.shape != image.shape[:2] or not segm.flags.c_contiguous:
+        raise ValueError('the label map must be a C-contiguous int32 array of the height and width of the image')
+    height, width, channels = image.shape
+    labels = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    n = len(labels)
+    bg = np.zeros(max(channels, 1), dtype=np.uint8)
+    bg[...] = bg_color
+    raised = []
+
+    def hook(user, n_labels, rotate, hook_height, hook_width, moments, geometry_out, frames_out):
+        try:
+            for k in range(n_labels):
+                g = geometry([int(moments[10 * k + i]) for i in range(10)], (hook_height, hook_width), bool(rotate))
+                row = (g['shift'][0], g['shift'][1], g['matrix'][0, 0], g['matrix'][0, 1], g['matrix'][1, 0], g['matrix'][1, 1],
+                       g['offset'][0], g['offset'][1])
+                for i, value in enumerate(row):
+                    geometry_out[8 * k + i] = float(value)
+                for i, value in enumerate(tuple(g['canvas']) + tuple(g['window'])):
+                    frames_out[6 * k + i] = int(value)
+            return 0
+        except BaseException as ex:                    # (an exception must not cross the C frames)
+            raised.append(ex)
+            return 1
+
+    moments, boxes = np.zeros((n, 10), dtype=np.int64), np.zeros((n, 4), dtype=np.int32)
+    offsets, packed, first_empty = np.zeros(n + 1, dtype=np.int64), _vp(), C.c_int(-1)
+    ctx = ctx or default_context()
+    callback = CUT_GEOMETRY_FN(hook)                   # (alive until the call returns)
+    status = load_library().imsegm_cut_objects(ctx._h, _ptr(image), _ptr(segm), height, width, channels, _ptr(labels), n, int(padding),
+                                               int(bool(use_mask)), _ptr(bg), int(bool(allow_rotate)), C.cast(callback, _vp),
+                                               None, _ptr(moments), _ptr(boxes), _ptr(offsets), C.byref(packed), C.byref(first_empty))
+    if raised:
+        raise raised[0]
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    if first_empty.value >= 0:
+        raise IndexError('list index out of range')         # regionprops(...)[0] of the reference on the turned mask
+    crops = []
+    if n:
+        flat = np.ctypeslib.as_array(C.cast(packed, C.POINTER(C.c_uint8)), shape=(max(int(offsets[n]), 1), ))
+        for k in range(n):
+            shape = (int(boxes[k, 2] - boxes[k, 0]), int(boxes[k, 3] - boxes[k, 1]), channels)
+            crops.append(flat[offsets[k]:offsets[k + 1]].reshape(shape).copy())
+    return crops, moments, boxes
 
 
 #: ``IMSEGM_ANNOT_MAX_COLORS``: entries of a colour table of the ``imsegm_annot_*`` calls
