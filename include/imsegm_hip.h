@@ -41,7 +41,8 @@ extern "C" {
 
 /* status of imsegm_object_shapes for a map it does not take -- more objects than the caller's capacity, or more than two label
  * values that span IMSEGM_OBJECT_SHAPES_MAX_SPAN or more: nothing is wrong with the context and no error message is set -- the
- * caller evaluates the map on the host.  imsegm_cut_objects returns it in the same sense for a request outside its caps */
+ * caller evaluates the map on the host.  imsegm_cut_objects and the imsegm_center_* / imsegm_correct_segm calls return it in the
+ * same sense for a request outside their caps */
 #define IMSEGM_E_OBJECT_CAPS (-5)
 
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
@@ -829,6 +830,37 @@ IMSEGM_API int imsegm_cut_objects(imsegm_ctx *ctx, const uint8_t *image, const i
                                   const int32_t *labels, int n_labels, int padding, int use_mask, const uint8_t *bg_color,
                                   int allow_rotate, imsegm_cut_geometry_fn geometry, void *user, int64_t *moments_out,
                                   int32_t *boxes_out, int64_t *offsets_out, const uint8_t **packed_out, int *first_empty_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Centre-level annotations from maps of annotated eggs (experiments_ovary_centres/run_create_annotation.py of the reference:
+ * load_correct_segm :68-83, segm_set_center_levels :100-132, compute_eggs_center :52-65); csrc/center_annotation.hip and the
+ * label-aware disc kernels of csrc/morphology.hip.  Integers up to the fp64 operations numpy takes: same call, same bytes.  All
+ * arrays are host arrays.  Every entry returns IMSEGM_E_OBJECT_CAPS -- no message, the caller evaluates on the host -- for what it
+ * does not take: more than 65535 rows, 2^31 pixels or more, height^2 + width^2 > 2^32 - 1, more than
+ * IMSEGM_CENTER_ANNOT_MAX_LABELS labels, an opening radius of a level above IMSEGM_MORPH_MAX_RADIUS; -1 with a message for null
+ * arguments, sizes below 1, radii outside [0, IMSEGM_MORPH_MAX_RADIUS], more than IMSEGM_CENTER_ANNOT_MAX_LEVELS levels and
+ * levels that descend.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_CENTER_ANNOT_MAX_LABELS 1024    /* label values 1 .. 1024 own a slot of the per-label tables */
+#define IMSEGM_CENTER_ANNOT_MAX_LEVELS 8       /* one bit per level in a byte per pixel */
+/* load_correct_segm after the read: img > 0 (img_is_i32: int32 pixels, otherwise uint8), opening with disk(sel_radius) (0: none),
+ * 4-connected components with fewer than min_size pixels removed -> seg_out (uint8 0 / 1, may be NULL); its 8-connected components
+ * numbered from 1 in raster order of their first pixels -> labels_out (int32, may be NULL), their number -> *n_labels_out. */
+IMSEGM_API int imsegm_correct_segm(imsegm_ctx *ctx, const void *img, int img_is_i32, int height, int width, int sel_radius,
+                                   int min_size, uint8_t *seg_out, int32_t *labels_out, int *n_labels_out);
+/* segm_set_center_levels without the save and compute_eggs_center, for the labels 1 .. max_label of `labels` (int32; other values
+ * are background).  levels: n_levels ascending doubles; n_levels = 0 computes the centres only.  levels_out (uint8, may be NULL
+ * then): 0, or i + 1 for the highest level i whose opened mask holds the pixel.  counts_out (int64 [max_label + 1]): the pixels
+ * of every label, 0 for an absent one; centres_out (double [2 (max_label + 1)]): column mean, row mean -- the quotient of two
+ * exact integer sums.  The fp64 radius, disc and opening radius of every (label, level) are computed on the host side of the
+ * call between two launches (one small download, one small upload). */
+IMSEGM_API int imsegm_center_levels(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int max_label, const double *levels,
+                                    int n_levels, uint8_t *levels_out, int64_t *counts_out, double *centres_out);
+/* create_annot_centers without the files: the two calls above with the label map staying on the device.  counts_out and
+ * centres_out hold IMSEGM_CENTER_ANNOT_MAX_LABELS + 1 rows; *n_labels_out = the number of labels (rows 1 .. n are filled). */
+IMSEGM_API int imsegm_create_annot_centers(imsegm_ctx *ctx, const void *img, int img_is_i32, int height, int width, int sel_radius,
+                                           int min_size, const double *levels, int n_levels, uint8_t *levels_out, int *n_labels_out,
+                                           int64_t *counts_out, double *centres_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the

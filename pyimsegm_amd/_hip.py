@@ -208,6 +208,9 @@ _SIGNATURES = {
     'imsegm_annot_paint': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp, _vp, _vp]),
     'imsegm_cut_objects': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _ip]),
+    'imsegm_correct_segm': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip]),
+    'imsegm_center_levels': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    'imsegm_create_annot_centers': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _vp]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
@@ -1958,6 +1961,69 @@ def cut_objects(image, segm, labels, padding, use_mask, bg_color, allow_rotate, 
             shape = (int(boxes[k, 2] - boxes[k, 0]), int(boxes[k, 3] - boxes[k, 1]), channels)
             crops.append(flat[offsets[k]:offsets[k + 1]].reshape(shape).copy())
     return crops, moments, boxes
+
+
+#: ``IMSEGM_CENTER_ANNOT_MAX_LABELS`` / ``IMSEGM_CENTER_ANNOT_MAX_LEVELS``
+CENTER_ANNOT_MAX_LABELS, CENTER_ANNOT_MAX_LEVELS = 1024, 8
+
+
+def _egg_map(img):
+    if img.ndim != 2 or img.dtype not in (np.uint8, np.int32) or not img.flags.c_contiguous or img.size == 0:
+        raise ValueError('the egg map must be a non-empty C-contiguous 2-D uint8 or int32 array')
+    return int(img.dtype == np.int32)
+
+
+def correct_segm(img, sel_radius, min_size, ctx=None):
+    """``imsegm_correct_segm`` on a C-contiguous 2-D uint8 or int32 map: (seg uint8 H x W, labels int32 H x W, number of labels), or
+    None for a map outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    is_i32 = _egg_map(img)
+    seg, labels, n_labels = np.empty(img.shape, dtype=np.uint8), np.empty(img.shape, dtype=np.int32), C.c_int(0)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_correct_segm(ctx._h, _ptr(img), is_i32, img.shape[0], img.shape[1], int(sel_radius),
+                                                int(np.clip(min_size, -2 ** 31, 2 ** 31 - 1)), _ptr(seg), _ptr(labels), C.byref(n_labels))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return seg, labels, n_labels.value
+
+
+def center_levels(labels, max_label, levels, ctx=None):
+    """``imsegm_center_levels`` on a 2-D integer label map whose largest value is ``max_label`` (1 .. CENTER_ANNOT_MAX_LABELS):
+    (level map uint8 H x W -- None without levels --, counts int64 [max_label], centres float64 [max_label, 2] as (X, Y), rows of the
+    labels 1 .. max_label), or None for a request outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    if labels.ndim != 2 or labels.size == 0:
+        raise ValueError('the label map must be a non-empty 2-D array')
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    levels = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    max_label = int(max_label)
+    out = np.empty(labels.shape, dtype=np.uint8) if len(levels) else None
+    counts, centres = np.zeros(max_label + 1, dtype=np.int64), np.zeros((max_label + 1, 2), dtype=np.float64)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_center_levels(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], max_label, _ptr(levels),
+                                                 len(levels), _ptr(out), _ptr(counts), _ptr(centres))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out, counts[1:], centres[1:]
+
+
+def create_annot_centers(img, sel_radius, min_size, levels, ctx=None):
+    """``imsegm_create_annot_centers`` on a C-contiguous 2-D uint8 or int32 map: (level map uint8 H x W, counts int64 [n], centres
+    float64 [n, 2] as (X, Y)) of the n labels, or None for a request outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    is_i32 = _egg_map(img)
+    levels = np.ascontiguousarray(levels, dtype=np.float64).ravel()
+    out, n_labels = np.empty(img.shape, dtype=np.uint8), C.c_int(0)
+    counts = np.zeros(CENTER_ANNOT_MAX_LABELS + 1, dtype=np.int64)
+    centres = np.zeros((CENTER_ANNOT_MAX_LABELS + 1, 2), dtype=np.float64)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_create_annot_centers(ctx._h, _ptr(img), is_i32, img.shape[0], img.shape[1], int(sel_radius),
+                                                        int(np.clip(min_size, -2 ** 31, 2 ** 31 - 1)), _ptr(levels), len(levels), _ptr(out),
+                                                        C.byref(n_labels), _ptr(counts), _ptr(centres))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    n = n_labels.value
+    return out, counts[1:n + 1], centres[1:n + 1]
 
 
 #: ``IMSEGM_ANNOT_MAX_COLORS``: entries of a colour table of the ``imsegm_annot_*`` calls

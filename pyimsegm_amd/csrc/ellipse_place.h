@@ -17,6 +17,17 @@ constexpr int ELLIPSE_PLACE_MAX_COORD = 1 << 30;
 // its angle.  Both come from the host, so that no kernel evaluates a transcendental or a ceil.
 constexpr int ELLIPSE_GEOM_INTS = 8;
 
+// scikit-image 0.18.3's inside test of draw.ellipse for the offsets (a, b) of a pixel from the centre:
+// ((a cos + b sin) / r_rad)^2 + ((a sin - b cos) / c_rad)^2 < 1, every product, sum and quotient rounded on its own, the comparison
+// strict (ellipse_place.hip on integer offsets; center_annotation.hip on the offsets of draw.disk: equal radii, sin 0, cos 1)
+__device__ __forceinline__ bool ellipse_inside_offsets(double a, double b, double sn, double cs, double r_rad, double c_rad)
+{
+#pragma clang fp contract(off)
+    const double u = (a * cs + b * sn) / r_rad;
+    const double v = (a * sn - b * cs) / c_rad;
+    return u * u + v * v < 1.0;
+}
+
 // counts[v] += number of pixels with value v for 1 <= v < ELLIPSE_PLACE_LABELS (counts zeroed by the caller); *beyond = 1 when a
 // value >= ELLIPSE_PLACE_LABELS is met
 int launch_ellipse_label_counts(const int32_t *segm, size_t n_pixels, int32_t *counts, int32_t *beyond, hipStream_t st);

@@ -35,15 +35,10 @@ __device__ __forceinline__ Ellipse load_ellipse(const int32_t *geom, const doubl
     return el;
 }
 
-// ((a cos + b sin) / r_rad)^2 + ((a sin - b cos) / c_rad)^2 < 1 for the integer offsets (a, b) of a pixel from the centre: every
-// product, sum and quotient rounds on its own, the comparison is strict
+// the inside test of ellipse_place.h for the integer offsets of a pixel from the integer centre
 __device__ __forceinline__ bool inside_ellipse(const Ellipse &el, int row, int col)
 {
-#pragma clang fp contract(off)
-    const double a = (double)(row - el.r), b = (double)(col - el.c);
-    const double u = (a * el.cs + b * el.sn) / (double)el.r_rad;
-    const double v = (a * el.sn - b * el.cs) / (double)el.c_rad;
-    return u * u + v * v < 1.0;
+    return ellipse_inside_offsets((double)(row - el.r), (double)(col - el.c), el.sn, el.cs, (double)el.r_rad, (double)el.c_rad);
 }
 
 __global__ __launch_bounds__(256) void k_ellipse_label_counts(const int32_t *__restrict__ segm, size_t n_pixels,

@@ -17,6 +17,18 @@ int launch_fill_holes_split(const int32_t *segm, int H, int W, int32_t *parent, 
 // out = erosion (dilate == 0) or dilation (dilate == 1) of the mask `in` by the disc dy^2 + dx^2 <= r^2, pixels outside the image
 // not counted (1 <= r <= MORPH_MAX_RADIUS; in != out)
 int launch_disc_morph(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, hipStream_t st);
+// The same erosion / dilation for all objects of a label map at once (the levels of center_annotation.hip): a pixel belongs to the
+// mask of its own label only -- bit `level` of the byte in[p] for the erosion, in[p] != 0 for the dilation --, its radius is
+// radius[label * MORPH_LEVEL_SLOTS + level] (at most r, the halo of the launch, 0 <= r <= MORPH_MAX_RADIUS), labels outside
+// 1 .. max_label are background.  The erosion writes 0 / 1 into every byte of out; the dilation writes level + 1 where it finds a
+// survivor and leaves the other bytes as they are.
+constexpr int MORPH_LEVEL_SLOTS = 8;
+struct MorphLabels {
+    const int32_t *labels = nullptr;
+    const int32_t *radius = nullptr;
+    int level = 0, max_label = 0;
+};
+int launch_disc_morph_labelled(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, const MorphLabels &ml, hipStream_t st);
 // rays of P positions on seg_bg with edge 'up' into rays_bg and on seg_fg with edge 'down' into rays_fg (P x A float32 each, either
 // may be null), one launch
 int launch_boundary_rays(const uint8_t *seg_bg, const uint8_t *seg_fg, int H, int W, const int32_t *positions, int P, const float *grad,

@@ -65,9 +65,25 @@ k_holes_write(const int32_t *__restrict__ segm, const int32_t *__restrict__ pare
 //     the first hit.
 // LDS: (64 + 2 r)^2 + 64 (64 + 2 r) bytes: 14 852 at r = 15, 49 152 at r = 64 (DESIGN.md section 4 on the tile and the occupancy).
 constexpr int MO_TILE = 64, MO_SEG = 16;
+//
+// LABELLED: the same tiles for all objects of a label map at once (center_annotation.hip): the mask of a pixel is that of its OWN
+// label -- bit `level` of the code byte for the erosion, the eroded byte for the dilation -- and a pixel of another label is
+// outside it; the radius of a pixel is radius[label * MORPH_LEVEL_SLOTS + level] <= r, r being the halo of the launch.  One byte of
+// LDS per pixel still: bit 0 as above, bit 1 "the label differs from the pixel above", bit 2 "... from the pixel to the left" (both
+// inside the image).  A column run ends at a label change -- as a hit for the erosion, as "nothing beyond" for the dilation -- so
+// run[ty][c] is the distance to the nearest hit among the pixels of the label of (ty, c); the row search of a pixel stops on
+// either side where the label changes, for the erosion with a hit.  The dilation writes level + 1 into `out` where it finds a
+// survivor and leaves every other byte as it is: the levels are launched in ascending order, the highest one stays.
+template <int TARGET, bool LABELLED> __device__ __forceinline__ int morph_step(int d, int cap, uint8_t here, uint8_t change)
+{
+    if (here & 1) return 0;
+    if (LABELLED && (change & 2)) return TARGET ? cap : 1;
+    return min(d + 1, cap);
+}
 
-template <int TARGET>
-__global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out)
+template <int TARGET, bool LABELLED>
+__global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out,
+                                                    MorphLabels ml)
 {
     extern __shared__ uint8_t morph_lds[];
     const int LW = MO_TILE + 2 * r;
@@ -81,7 +97,18 @@ __global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ 
         for (int lx = lane; lx < LW; lx += 64) {
             const int x = x0 + lx;
             uint8_t v = 0;
-            if (iny && x >= 0 && x < W) v = (in[(size_t)y * W + x] != 0) == (TARGET != 0);
+            if (iny && x >= 0 && x < W) {
+                const size_t i = (size_t)y * W + x;
+                if (LABELLED) {
+                    const int l = ml.labels[i];
+                    const bool own = l >= 1 && l <= ml.max_label;
+                    const bool set = own && (TARGET ? in[i] != 0 : ((in[i] >> ml.level) & 1) != 0);
+                    v = (uint8_t)((set == (TARGET != 0) ? 1 : 0) | (y > 0 && ml.labels[i - W] != l ? 2 : 0) |
+                                  (x > 0 && ml.labels[i - 1] != l ? 4 : 0));
+                } else {
+                    v = (in[i] != 0) == (TARGET != 0);
+                }
+            }
             hit[ly * LW + lx] = v;
         }
     }
@@ -92,29 +119,53 @@ __global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ 
         const int t0 = seg * MO_SEG;                   // first tile row of the lane; LDS row of tile row t is t + r
         int d = cap;
         for (int ly = t0; ly < t0 + r + MO_SEG; ++ly) {
-            d = hit[ly * LW + c] ? 0 : min(d + 1, cap);
+            const uint8_t here = hit[ly * LW + c];
+            d = morph_step<TARGET, LABELLED>(d, cap, here, here);                       // (the change between ly - 1 and ly sits on ly)
             if (ly >= t0 + r) run[(ly - r) * LW + c] = (uint8_t)d;
         }
         d = cap;
         for (int ly = t0 + MO_SEG - 1 + 2 * r; ly >= t0 + r; --ly) {
-            d = hit[ly * LW + c] ? 0 : min(d + 1, cap);
+            const uint8_t below = LABELLED && ly + 1 < LW ? hit[(ly + 1) * LW + c] : (uint8_t)0;
+            d = morph_step<TARGET, LABELLED>(d, cap, hit[ly * LW + c], below);          // (the change between ly and ly + 1 on ly + 1)
             if (ly <= t0 + MO_SEG - 1 + r) run[(ly - r) * LW + c] = (uint8_t)min(d, (int)run[(ly - r) * LW + c]);
         }
     }
     __syncthreads();
     const int x = blockIdx.x * MO_TILE + lane;
     if (x >= W) return;
-    const int r2 = r * r;
     for (int ty = wave; ty < MO_TILE; ty += 4) {
         const int y = blockIdx.y * MO_TILE + ty;
         if (y >= H) break;
         const uint8_t *line = run + ty * LW + lane + r;
         bool found = false;
-        for (int k = 0; k <= r && !found; ++k) {
-            const int lim = r2 - k * k, a = line[-k], b = line[k];
-            found = a * a <= lim || b * b <= lim;
+        if (LABELLED) {
+            const int l = ml.labels[(size_t)y * W + x];
+            const bool own = l >= 1 && l <= ml.max_label;
+            if (own) {
+                const int rr = min(ml.radius[l * MORPH_LEVEL_SLOTS + ml.level], r), r2 = rr * rr;
+                const uint8_t *flags = hit + (ty + r) * LW + lane + r;
+                bool left = true, right = true;                // the side has not met another label yet
+                found = (int)line[0] * (int)line[0] <= r2;
+                for (int k = 1; k <= rr && !found; ++k) {
+                    if (left && (flags[1 - k] & 4)) left = false, found = !TARGET;
+                    if (right && (flags[k] & 4)) right = false, found = found || !TARGET;
+                    const int lim = r2 - k * k, a = line[-k], b = line[k];
+                    found = found || (left && a * a <= lim) || (right && b * b <= lim);
+                }
+            }
+            if (TARGET) {
+                if (found) out[(size_t)y * W + x] = (uint8_t)(ml.level + 1);
+            } else {
+                out[(size_t)y * W + x] = own && !found;
+            }
+        } else {
+            const int r2 = r * r;
+            for (int k = 0; k <= r && !found; ++k) {
+                const int lim = r2 - k * k, a = line[-k], b = line[k];
+                found = a * a <= lim || b * b <= lim;
+            }
+            out[(size_t)y * W + x] = TARGET ? found : !found;
         }
-        out[(size_t)y * W + x] = TARGET ? found : !found;
     }
 }
 
@@ -173,9 +224,26 @@ int launch_disc_morph(const uint8_t *in, int H, int W, int r, int dilate, uint8_
     const size_t lds = (size_t)LW * LW + (size_t)MO_TILE * LW;
     const dim3 grid(cdiv(W, MO_TILE), cdiv(H, MO_TILE));
     if (dilate)
-        hipLaunchKernelGGL(k_disc_morph<1>, grid, 256, lds, st, in, H, W, r, out);
+        hipLaunchKernelGGL((k_disc_morph<1, false>), grid, 256, lds, st, in, H, W, r, out, MorphLabels());
     else
-        hipLaunchKernelGGL(k_disc_morph<0>, grid, 256, lds, st, in, H, W, r, out);
+        hipLaunchKernelGGL((k_disc_morph<0, false>), grid, 256, lds, st, in, H, W, r, out, MorphLabels());
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_disc_morph_labelled(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, const MorphLabels &ml, hipStream_t st)
+{
+    if (r < 0 || r > MORPH_MAX_RADIUS || !ml.labels || !ml.radius || ml.level < 0 || ml.level >= MORPH_LEVEL_SLOTS || ml.max_label < 1) {
+        set_error("disc morphology of a label map: a halo outside [0, IMSEGM_MORPH_MAX_RADIUS] or no tables");
+        return -1;
+    }
+    const int LW = MO_TILE + 2 * r;
+    const size_t lds = (size_t)LW * LW + (size_t)MO_TILE * LW;
+    const dim3 grid(cdiv(W, MO_TILE), cdiv(H, MO_TILE));
+    if (dilate)
+        hipLaunchKernelGGL((k_disc_morph<1, true>), grid, 256, lds, st, in, H, W, r, out, ml);
+    else
+        hipLaunchKernelGGL((k_disc_morph<0, true>), grid, 256, lds, st, in, H, W, r, out, ml);
     HIP_TRY(hipGetLastError());
     return 0;
 }

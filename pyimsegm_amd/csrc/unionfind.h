@@ -67,12 +67,13 @@ __device__ __forceinline__ int run_start_lane(unsigned long long starts, int lan
 }
 
 // ---- 4-connected labelling of the pixels of a 2-D map that a predicate on their value selects, by row segments -----------------
-// (k_holes_* of morphology.hip on the pixels <= 0, k_os_cc_* of object_shapes.hip on the pixels != 0.)  A wave covers 64
+// (k_holes_* of morphology.hip on the pixels <= 0, k_os_cc_* of object_shapes.hip on the pixels != 0, k_ca_cc_* of
+// center_annotation.hip on the set bytes of a mask.)  A wave covers 64
 // consecutive pixels of row y, lane = x & 63, and every lane of the wave calls.  run_label_init: every selected pixel starts out
 // pointing at the first pixel of its run INSIDE its segment, every other pixel at itself, so the unions that are left lie where a
 // run crosses a segment and where a run meets the row above for the first time.
-template <typename Selected>
-__device__ __forceinline__ void run_label_init(const int32_t *__restrict__ segm, int32_t *__restrict__ parent, int y, int x, int W,
+template <typename Map, typename Selected>
+__device__ __forceinline__ void run_label_init(const Map *__restrict__ segm, int32_t *__restrict__ parent, int y, int x, int W,
                                                Selected selected)
 {
     const int lane = threadIdx.x & 63;
@@ -87,8 +88,8 @@ __device__ __forceinline__ void run_label_init(const int32_t *__restrict__ segm,
 
 // run_label_merge: p and the pixel above it are tied when p starts a run of its segment or the pixel above p - 1 is not selected:
 // otherwise p - 1 is tied to the pixel above it, which shares a run (and a segment) with the pixel above p
-template <typename Selected>
-__device__ __forceinline__ void run_label_merge(const int32_t *__restrict__ segm, int32_t *parent, int y, int x, int W, Selected selected)
+template <typename Map, typename Selected>
+__device__ __forceinline__ void run_label_merge(const Map *__restrict__ segm, int32_t *parent, int y, int x, int W, Selected selected)
 {
     const int lane = threadIdx.x & 63;
     const size_t row = (size_t)y * W;
