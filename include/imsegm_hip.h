@@ -45,6 +45,13 @@ extern "C" {
  * same sense for a request outside their caps */
 #define IMSEGM_E_OBJECT_CAPS (-5)
 
+/* status of imsegm_forest_proba / imsegm_image2d_forest_proba (and of the imsegm_image2d_segment that takes the probabilities of
+ * the latter) for a forest or a table they refuse -- a non-finite value in the table (or one that leaves float32's range), more
+ * than IMSEGM_FOREST_MAX_CLASSES classes, IMSEGM_FOREST_MAX_FEATURES columns or IMSEGM_FOREST_MAX_TREES trees, a node whose
+ * child, feature or leaf row is out of range: nothing is written to the outputs, nothing is wrong with the context -- the
+ * caller evaluates the model on the host */
+#define IMSEGM_E_FOREST_INPUT (-6)
+
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
 typedef struct imsegm_image2d imsegm_image2d;   /* device-resident state of one H x W image */
 
@@ -366,7 +373,8 @@ typedef struct {
  * graph_cuts.py:729-731), classes_[graph_labels] (classes_lut, may be NULL) and the gathers graph_labels[slic],
  * proba[slic] (imsegm/graph_cuts.py:660-747, imsegm/pipelines.py:96-109,232-240).  One stream, one synchronisation at
  * the end.  Outputs (each may be NULL): segm_out H x W int32, soft_out H x W x C float64, graph_labels_out K int32
- * (before classes_lut), proba_out K x C. */
+ * (before classes_lut), proba_out K x C.  With gmm == NULL and proba == NULL (version >= 102) the probabilities are those the last
+ * imsegm_image2d_forest_proba left on the device for this label map and feature table; without them the call fails as before. */
 IMSEGM_API int imsegm_image2d_segment(imsegm_image2d *img, const imsegm_gmm *gmm, const double *proba, int n_classes,
                                       const double *pairwise, int edge_type, double edge_cost, int use_graphcut,
                                       const int32_t *classes_lut, int32_t *segm_out, double *soft_out,
@@ -929,6 +937,45 @@ IMSEGM_API int imsegm_annot_quantize_nearest_pixel(imsegm_ctx *ctx, const uint8_
 IMSEGM_API int imsegm_score_pairs(imsegm_ctx *ctx, int n_pairs, const void *const *annots, const void *const *segms, const int64_t *sizes,
                                   int dtype, const int32_t *drop_labels, int n_drop, int32_t *status_out, int32_t *n_labels_out,
                                   int32_t *labels_out, int64_t *tables_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * random-forest class models (version >= 102): predict_proba of sklearn Pipeline([StandardScaler,] clf), clf a
+ * RandomForestClassifier, ExtraTreesClassifier or DecisionTreeClassifier with one output, bit for bit (n_jobs = 1):
+ *   z = float32((x - mean) / scale)     two fp64 operations, then round to nearest even (scikit-learn's input validation)
+ *   per tree, in estimators_ order: from node 0, left while z[feature] <= threshold, until a leaf
+ *   proba = (0 + row(leaf of tree 0) + row(leaf of tree 1) + ...) / n_trees   in fp64, in that order, one division
+ * A tree is stored in preorder: the left child of node i is node i + 1, only the right child is kept.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_FOREST_MAX_CLASSES 16       /* the cut's own limit */
+#define IMSEGM_FOREST_MAX_FEATURES 256
+#define IMSEGM_FOREST_MAX_TREES 1024
+#define IMSEGM_FOREST_MAX_TREE_NODES (1 << 23)   /* the right child has 23 bits */
+#define IMSEGM_FOREST_ROWS 256             /* rows of the table a workgroup walks at a time: one per lane */
+#define IMSEGM_FOREST_LDS_NODES 4096       /* a tree of up to this many nodes (32 KB) is walked in LDS, a larger one in global memory */
+typedef struct {
+    float threshold;              /* the largest float32 <= the float64 threshold of scikit-learn (0 in a leaf) */
+    int32_t word;                 /* >= 0: feature | right child << 8 (index inside the tree); < 0: a leaf, ~word its row of leaf_values */
+} imsegm_forest_node;
+/* zero-initialised by callers, as imsegm_gmm */
+typedef struct {
+    int n_features, n_classes, n_trees;
+    int n_nodes, n_leaves;                 /* of all trees together */
+    const double *scaler_mean;             /* [F] StandardScaler.mean_ or NULL */
+    const double *scaler_scale;            /* [F] StandardScaler.scale_ or NULL */
+    const imsegm_forest_node *nodes;       /* [n_nodes], tree after tree */
+    const int32_t *tree_start;             /* [n_trees + 1] first node of every tree, n_nodes last */
+    const double *leaf_values;             /* [n_leaves][C] what the tree's predict_proba returns in that leaf */
+} imsegm_forest;
+/* proba_out [n_rows][C] of the host table [n_rows][n_columns] (float64, n_columns == forest->n_features).  The forest is checked
+ * on the host before it goes up (sizes, every child, feature and leaf row in range, children behind their parent: every path ends
+ * in a leaf); returns IMSEGM_E_FOREST_INPUT with proba_out untouched for what it refuses. */
+IMSEGM_API int imsegm_forest_proba(imsegm_ctx *ctx, const imsegm_forest *forest, const double *table, int n_rows, int n_columns,
+                                   double *proba_out);
+/* the same on the resident feature table of a 2-D or volume session (imsegm_image2d_features_color, ...): K x C probabilities
+ * stay resident, and the next imsegm_image2d_segment with gmm == NULL and proba == NULL takes them.  proba_out may be NULL: the
+ * call then does not wait, and a table the forest refuses shows as IMSEGM_E_FOREST_INPUT of that segment call.  Any call that
+ * changes the label map or the feature table drops the probabilities, as it drops the prepared graph. */
+IMSEGM_API int imsegm_image2d_forest_proba(imsegm_image2d *img, const imsegm_forest *forest, double *proba_out);
 
 #ifdef __cplusplus
 }

@@ -51,9 +51,16 @@ class HipFitCapsError(HipError):
     features, 8 components, 16 restarts) -- nothing is wrong with the context, the caller fits on the host"""
 
 
+class HipForestInputError(HipError):
+    """``IMSEGM_E_FOREST_INPUT`` of include/imsegm_hip.h: the forest entry points refuse this table (a value that is not finite in
+    float32) or this forest (more than 16 classes, 256 features or 1 024 trees, a node index out of range) -- nothing was
+    written, nothing is wrong with the context, the caller evaluates the model on the host"""
+
+
 IMSEGM_E_FUSED_PATH = -3
 IMSEGM_E_FIT_CAPS = -4
 IMSEGM_E_OBJECT_CAPS = -5
+IMSEGM_E_FOREST_INPUT = -6
 
 
 _lib = None
@@ -67,6 +74,12 @@ class GmmParams(C.Structure):
     _fields_ = [('n_features', C.c_int), ('n_classes', C.c_int), ('scaler_mean', _vp), ('scaler_scale', _vp),
                 ('prec_chol', _vp), ('mu_proj', _vp), ('log_det', _vp), ('log_weights', _vp), ('const_term', C.c_double),
                 ('n_inputs', C.c_int), ('pca_components_t', _vp), ('pca_shift', _vp), ('pca_scale', _vp)]
+
+
+class ForestParams(C.Structure):
+    """``imsegm_forest`` of include/imsegm_hip.h"""
+    _fields_ = [('n_features', C.c_int), ('n_classes', C.c_int), ('n_trees', C.c_int), ('n_nodes', C.c_int), ('n_leaves', C.c_int),
+                ('scaler_mean', _vp), ('scaler_scale', _vp), ('nodes', _vp), ('tree_start', _vp), ('leaf_values', _vp)]
 
 
 class TermsDebug(C.Structure):
@@ -215,6 +228,8 @@ _SIGNATURES = {
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     'imsegm_score_pairs': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    'imsegm_forest_proba': (C.c_int, [_vp, C.POINTER(ForestParams), _vp, C.c_int, C.c_int, _vp]),
+    'imsegm_image2d_forest_proba': (C.c_int, [_vp, C.POINTER(ForestParams), _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -280,7 +295,8 @@ def reload_env():
 def _check(status):
     if status != 0:
         message = load_library().imsegm_last_error().decode('utf-8', 'replace')
-        raise {IMSEGM_E_FUSED_PATH: HipFusedPathError, IMSEGM_E_FIT_CAPS: HipFitCapsError}.get(status, HipError)(message)
+        raise {IMSEGM_E_FUSED_PATH: HipFusedPathError, IMSEGM_E_FIT_CAPS: HipFitCapsError,
+               IMSEGM_E_FOREST_INPUT: HipForestInputError}.get(status, HipError)(message)
 
 
 _device_count = {}
@@ -641,6 +657,179 @@ class DeviceGmm(object):
         self.params = par
 
 
+#: a node of a packed tree (``imsegm_forest_node``): the float32 threshold rounded DOWN from scikit-learn's float64 one, and a word
+#: -- not negative: ``feature | right child << 8`` (the left child is the next node), negative: a leaf, ``~word`` its row of the
+#: leaf table
+FOREST_NODE = np.dtype([('threshold', '<f4'), ('word', '<i4')])
+FOREST_MAX_CLASSES, FOREST_MAX_FEATURES, FOREST_MAX_TREES, FOREST_MAX_TREE_NODES = 16, 256, 1024, 1 << 23
+#: rows a workgroup of the walk takes at a time, and the largest tree it stages in LDS (the tests take their sizes from here)
+FOREST_ROWS, FOREST_LDS_NODES = 256, 4096
+
+
+def forest_threshold(threshold64):
+    """the largest float32 that is <= each float64 threshold: ``float32(x) <= threshold64`` is ``float32(x) <= forest_threshold(...)``"""
+    threshold64 = np.asarray(threshold64, dtype=np.float64)
+    with np.errstate(over='ignore'):
+        rounded = threshold64.astype(np.float32)
+    above = rounded.astype(np.float64) > threshold64
+    rounded[above] = np.nextafter(rounded[above], np.float32(-np.inf))
+    return rounded
+
+
+def _forest_steps(model):
+    """(scaler or None, classifier) of a model the forest entry points take, or the reason why they do not, as a string"""
+    from sklearn.ensemble import ExtraTreesClassifier, RandomForestClassifier
+    from sklearn.pipeline import Pipeline
+    from sklearn.preprocessing import StandardScaler
+    from sklearn.tree import DecisionTreeClassifier
+    steps = [st for _, st in model.steps] if isinstance(model, Pipeline) else [model]
+    clf = steps[-1]
+    front = steps[:-1]
+    scaler = front.pop(0) if front and type(front[0]) is StandardScaler else None
+    if front:
+        return 'only an optional StandardScaler in front of the classifier is evaluated on the device'
+    if type(clf) not in (RandomForestClassifier, ExtraTreesClassifier, DecisionTreeClassifier):
+        return '%s is not a random forest, extra trees or a decision tree' % type(clf).__name__
+    if not hasattr(clf, 'tree_' if type(clf) is DecisionTreeClassifier else 'estimators_'):
+        return 'the classifier is not fitted'
+    if clf.n_outputs_ != 1:
+        return 'the classifier has more than one output'
+    trees = [clf] if type(clf) is DecisionTreeClassifier else list(clf.estimators_)
+    if not 1 <= len(trees) <= FOREST_MAX_TREES:
+        return 'the device takes 1 .. %d trees' % FOREST_MAX_TREES
+    if len(clf.classes_) > FOREST_MAX_CLASSES or clf.n_features_in_ > FOREST_MAX_FEATURES:
+        return 'the device takes at most %d classes and %d features' % (FOREST_MAX_CLASSES, FOREST_MAX_FEATURES)
+    if max(tree.tree_.node_count for tree in trees) > FOREST_MAX_TREE_NODES:
+        return 'a tree has more than 2^23 nodes'
+    return scaler, clf
+
+
+def _leaf_rows(tree, rows):
+    """what ``DecisionTreeClassifier.predict_proba`` of the installed scikit-learn returns in the leaves ``rows`` of ``tree``: the
+    stored class fractions as they are (1.3 and later); before that the stored class weights divided by their sum"""
+    import sklearn
+    values = np.array(tree.tree_.value[rows, 0, :tree.n_classes_], dtype=np.float64)
+    if tuple(int(part) for part in sklearn.__version__.split('.')[:2]) < (1, 3):
+        normalizer = values.sum(axis=1)[:, np.newaxis]
+        normalizer[normalizer == 0.0] = 1.0
+        values /= normalizer
+    return values
+
+
+class DeviceForest(object):
+    """the arrays of a fitted ``Pipeline([StandardScaler,] clf)`` -- ``clf`` a ``RandomForestClassifier``, ``ExtraTreesClassifier``
+    or ``DecisionTreeClassifier`` with one output -- that the device needs for ``predict_proba`` (``imsegm_forest`` of
+    include/imsegm_hip.h), all plain numpy: ``nodes`` (:data:`FOREST_NODE`, tree after tree, every tree in preorder so that the
+    left child is the next node), ``tree_start`` (int32, T + 1), ``leaf_values`` (float64, leaves x C, what the tree's own
+    ``predict_proba`` returns there), ``scaler_mean`` / ``scaler_scale`` or None, and ``threshold64``, scikit-learn's thresholds in
+    the order of ``nodes`` (for the tests of the rounding).  ``DeviceForest(model)`` is None for a model the device does not take
+    (:func:`forest_refusal` says why); :meth:`from_arrays` builds one by hand."""
+
+    def __new__(cls, model=None):
+        self = object.__new__(cls)
+        if model is None:
+            return self
+        parts = _forest_steps(model)
+        if isinstance(parts, str):
+            return None
+        self._pack(*parts)
+        return self
+
+    def __init__(self, model=None):
+        pass
+
+    @classmethod
+    def from_arrays(cls, nodes, tree_start, leaf_values, n_features, scaler_mean=None, scaler_scale=None, classes=None):
+        self = cls()
+        self.nodes = np.ascontiguousarray(nodes, dtype=FOREST_NODE)
+        self.tree_start = np.ascontiguousarray(tree_start, dtype=np.int32)
+        self.leaf_values = np.ascontiguousarray(leaf_values, dtype=np.float64)
+        if self.nodes.ndim != 1 or self.tree_start.ndim != 1 or len(self.tree_start) < 2 or self.leaf_values.ndim != 2:
+            raise ValueError('nodes [N], tree_start [T + 1] and leaf_values [L, C] are expected')
+        self.n_features, self.n_classes, self.n_trees = int(n_features), int(self.leaf_values.shape[1]), len(self.tree_start) - 1
+        self.scaler_mean = None if scaler_mean is None else np.ascontiguousarray(scaler_mean, dtype=np.float64)
+        self.scaler_scale = None if scaler_scale is None else np.ascontiguousarray(scaler_scale, dtype=np.float64)
+        for vector in (self.scaler_mean, self.scaler_scale):
+            if vector is not None and vector.shape != (self.n_features, ):
+                raise ValueError('a scaler vector holds one value per feature')
+        self.classes = None if classes is None else np.asarray(classes)
+        self.threshold64 = self.nodes['threshold'].astype(np.float64)
+        return self
+
+    def _pack(self, scaler, clf):
+        trees = [clf] if hasattr(clf, 'tree_') else list(clf.estimators_)
+        nodes, thresholds, values, starts, n_leaves = [], [], [], [0], 0
+        for tree in trees:
+            inner = tree.tree_
+            left, right, feature = inner.children_left.tolist(), inner.children_right.tolist(), inner.feature
+            # preorder: a node, its left subtree, its right subtree (scikit-learn's depth-first builder lays its trees out so; its
+            # best-first builder, max_leaf_nodes, does not)
+            order, stack = [], [0]
+            while stack:
+                node = stack.pop()
+                order.append(node)
+                if left[node] >= 0:
+                    stack.append(right[node])
+                    stack.append(left[node])
+            order = np.array(order, dtype=np.int64)
+            place = np.empty(len(order), dtype=np.int64)
+            place[order] = np.arange(len(order))
+            is_leaf = inner.children_left[order] < 0
+            packed = np.zeros(len(order), dtype=FOREST_NODE)
+            threshold64 = np.where(is_leaf, 0.0, inner.threshold[order])
+            packed['threshold'] = forest_threshold(threshold64)
+            word = feature[order].astype(np.int64) | (place[inner.children_right[order]] << 8)
+            word[is_leaf] = ~(n_leaves + np.arange(int(is_leaf.sum()), dtype=np.int64))
+            packed['word'] = word.astype(np.int32)
+            nodes.append(packed)
+            thresholds.append(threshold64)
+            values.append(_leaf_rows(tree, order[is_leaf]))
+            n_leaves += int(is_leaf.sum())
+            starts.append(starts[-1] + len(order))
+        self.nodes = np.concatenate(nodes)
+        self.threshold64 = np.concatenate(thresholds)
+        self.tree_start = np.array(starts, dtype=np.int32)
+        self.leaf_values = np.ascontiguousarray(np.concatenate(values, axis=0))
+        self.n_features, self.n_classes, self.n_trees = int(clf.n_features_in_), len(clf.classes_), len(trees)
+        self.scaler_mean = self.scaler_scale = None
+        if scaler is not None:
+            if scaler.with_mean:
+                self.scaler_mean = np.ascontiguousarray(scaler.mean_, dtype=np.float64)
+            if scaler.with_std:
+                self.scaler_scale = np.ascontiguousarray(scaler.scale_, dtype=np.float64)
+        self.classes = np.asarray(clf.classes_)
+
+    def params(self):
+        """the ``imsegm_forest`` of the arrays as they are now (it points into them: keep the forest alive over the call)"""
+        par = ForestParams()
+        par.n_features, par.n_classes, par.n_trees = self.n_features, self.n_classes, self.n_trees
+        par.n_nodes, par.n_leaves = len(self.nodes), len(self.leaf_values)
+        for name in ('scaler_mean', 'scaler_scale', 'nodes', 'tree_start', 'leaf_values'):
+            setattr(par, name, _ptr(getattr(self, name)))
+        return par
+
+
+def forest_refusal(model):
+    """why ``DeviceForest(model)`` is None, or None when it is not"""
+    parts = _forest_steps(model)
+    return parts if isinstance(parts, str) else None
+
+
+def forest_proba(forest, table, out=None, ctx=None):
+    """``imsegm_forest_proba``: the probabilities (n x C float64) of a :class:`DeviceForest` on a host table (n x F float64).
+    Raises :class:`HipForestInputError`, with ``out`` untouched, for a table or a forest the device refuses."""
+    ctx = ctx or default_context()
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.ndim != 2:
+        raise ValueError('the table is n x F')
+    if out is None:
+        out = np.empty((len(table), forest.n_classes), dtype=np.float64)
+    elif out.shape != (len(table), forest.n_classes) or out.dtype != np.float64 or not out.flags.c_contiguous:
+        raise ValueError('out must be a C-contiguous float64 array of n x C')
+    _check(load_library().imsegm_forest_proba(ctx._h, C.byref(forest.params()), _ptr(table), len(table), table.shape[1], _ptr(out)))
+    return out
+
+
 @functools.lru_cache(maxsize=64)
 def gaussian_taps(sigma, truncate=4.0):
     """half of the kernel of ``scipy.ndimage.gaussian_filter1d(sigma)`` (taps[0] = centre), computed
@@ -776,6 +965,14 @@ class Image2D(object):
         _check(load_library().imsegm_image2d_features_color(self._h, mask, _ptr(out)))
         return out
 
+    def forest_proba(self, forest, to_host=False):
+        """``imsegm_image2d_forest_proba``: the probabilities of a :class:`DeviceForest` on the resident feature table, left on the
+        device for the next :meth:`segment` with neither ``gmm`` nor ``proba``.  Without ``to_host`` nothing waits and None is
+        returned (a table the forest refuses then shows as :class:`HipForestInputError` of that ``segment``); with it, K x C float64."""
+        out = np.empty((self.n_labels, forest.n_classes), dtype=np.float64) if to_host else None
+        _check(load_library().imsegm_image2d_forest_proba(self._h, C.byref(forest.params()), _ptr(out)))
+        return out
+
     def graph_prepare(self):
         """enqueue the graph of the resident label map (neighbour pairs, centres, edges, arcs) ahead of :meth:`segment`, without
         a synchronisation (``imsegm_image2d_graph_prepare``): it depends on the label map alone, so it can run while the host fits
@@ -806,7 +1003,9 @@ class Image2D(object):
             raise ValueError('pairwise cost must be square')
         k = self.n_labels
         pr = None
-        if gmm is None:
+        if gmm is None and proba is None:
+            pass            # (the probabilities :meth:`forest_proba` left on this label map and table, or the library's error)
+        elif gmm is None:
             pr = np.ascontiguousarray(proba, dtype=np.float64)
             if pr.ndim != 2 or pr.shape[0] < k or pr.shape[1] != nc:
                 raise ValueError('proba %r does not fit %d superpixels x %d classes' % (pr.shape, k, nc))

@@ -25,6 +25,11 @@ that is not an int32 integer, an average other than macro / weighted / micro / b
 :data:`RELABEL_MAX_LABEL` or without a non-negative label on either side, and inputs that leave no element.  With ``on=None`` the
 functions named in :data:`HOST_BY_DEFAULT` run on the host although a device is present (tools/time_scoring.py).
 
+The trained classifier is evaluated by :func:`predict_proba`: ``model.predict_proba`` on the host, or -- ``on='device'``, environment
+``IMSEGM_CLASSIF_ON``, default 'host' -- a random forest, extra trees or a single decision tree behind an optional scaler on the
+device (csrc/forest.hip), with the bytes of scikit-learn's ``n_jobs=1`` result.  :func:`forest_proba_host` is the numpy statement
+of that evaluation on the packed arrays of :class:`_hip.DeviceForest` (DESIGN.md has the definition).
+
 Every other name of the reference module resolves to the reference's own function when a reference package is installed
 behind the ``imsegm`` overlay (module ``__getattr__``).
 """
@@ -166,6 +171,134 @@ def convert_set_features_labels_2_dataset(imgs_features, imgs_labels, drop_label
         tags += np.asarray(labels).tolist()
         sizes.append(len(labels))
     return np.array(rows), np.array(tags, dtype=int), sizes
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# evaluating the trained classifier: tree ensembles on the device, bit for bit
+# ---------------------------------------------------------------------------------------------------------------------
+def forest_proba_host(packed, table, _defect=None):
+    """ the numpy statement of ``predict_proba`` for a packed forest (:class:`_hip.DeviceForest`): what the device computes and what
+    ``model.predict_proba(table)`` of scikit-learn returns with ``n_jobs=1``, byte for byte.
+
+    1. scale in float64, ``(x - mean_) / scale_``: two IEEE operations, a true division.  (A float32 table stays float32 inside
+       ``StandardScaler.transform``: either operation is then rounded to float32 on its own; the device takes float64 tables.)
+    2. round to float32, as scikit-learn's input validation does;
+    3. per tree, in order: from node 0, left while ``z[feature] <= threshold`` -- the threshold the largest float32 that is not
+       above scikit-learn's float64 one, which decides every float32 value the same way;
+    4. the leaf's row of ``leaf_values``;
+    5. summed over the trees in order, in float64, from zeros; one division by the number of trees.
+
+    ``_defect`` (tests only) breaks one step: 'lt' compares with ``<``, 'reverse' adds the trees last to first, 'divide_per_tree'
+    divides every row before it is added.
+
+    :param packed: :class:`_hip.DeviceForest`
+    :param ndarray table: n x F, float64 or float32
+    :return ndarray: n x C float64
+    """
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[1] != packed.n_features:
+        raise ValueError('the table is n x %d' % packed.n_features)
+    narrow = table.dtype == np.float32
+    scaled = table.astype(np.float64)
+    if packed.scaler_mean is not None:
+        scaled = scaled - packed.scaler_mean
+        if narrow:
+            scaled = scaled.astype(np.float32).astype(np.float64)
+    if packed.scaler_scale is not None:
+        scaled = scaled / packed.scaler_scale
+    with np.errstate(over='ignore'):
+        z = scaled.astype(np.float32)
+    if not (np.isfinite(table).all() and np.isfinite(z).all()):
+        raise ValueError('the table holds a value that is not finite in float32')
+    rows = np.arange(len(z))
+    total = np.zeros((len(z), packed.n_classes), dtype=np.float64)
+    order = range(packed.n_trees)
+    for tree in (reversed(order) if _defect == 'reverse' else order):
+        nodes = packed.nodes[packed.tree_start[tree]:packed.tree_start[tree + 1]]
+        threshold, word = nodes['threshold'], nodes['word'].astype(np.int64)
+        at = np.zeros(len(z), dtype=np.int64)
+        walking = rows[word[at] >= 0]
+        for _ in range(len(nodes)):                # (a path visits a node once)
+            if not len(walking):
+                break
+            here = word[at[walking]]
+            value = z[walking, here & 0xff]
+            left = value < threshold[at[walking]] if _defect == 'lt' else value <= threshold[at[walking]]
+            at[walking] = np.where(left, at[walking] + 1, here >> 8)
+            walking = walking[word[at[walking]] >= 0]
+        contribution = packed.leaf_values[~word[at]]
+        total += contribution / packed.n_trees if _defect == 'divide_per_tree' else contribution
+    return total if _defect == 'divide_per_tree' else total / packed.n_trees
+
+
+_device_forests = None
+
+
+def device_forest(model):
+    """:class:`_hip.DeviceForest` of a fitted model (cached per model object as long as its trees are the same objects), or None
+    with the reason: ``(forest, reason)``"""
+    global _device_forests
+    import weakref
+    if _device_forests is None:
+        _device_forests = weakref.WeakKeyDictionary()
+    try:
+        steps = [st for _, st in model.steps] if hasattr(model, 'steps') else [model]
+        clf = steps[-1]
+        # (what the packed arrays are formed from: a refit replaces them)
+        key = [getattr(steps[0], 'mean_', None), getattr(steps[0], 'scale_', None), getattr(clf, 'tree_', None)] \
+            + list(getattr(clf, 'estimators_', ()))
+        hit = _device_forests.get(model)
+        if hit is not None and len(hit[0]) == len(key) and all(a is b for a, b in zip(hit[0], key)):
+            return hit[1], None
+        reason = _hip.forest_refusal(model)
+        if reason is not None:
+            return None, reason
+        forest = _hip.DeviceForest(model)
+        _device_forests[model] = (key, forest)
+        return forest, None
+    except Exception as ex:       # private scikit-learn layout changed, a model that cannot be weakly referenced ...
+        return None, 'the model could not be packed: %s' % (ex, )
+
+
+def classif_place(on):
+    """'host' or 'device' for the ``on`` / ``classif_on`` keywords: None reads IMSEGM_CLASSIF_ON, unset means 'host'; any other value
+    is a ValueError and 'device' without a device a :class:`_hip.HipUnavailableError` (``_hip.resolve_place``)"""
+    place, explicit = _hip.resolve_place(on, 'IMSEGM_CLASSIF_ON', True)
+    return place if explicit else 'host'
+
+
+def device_table(forest, features):
+    """``features`` as the float64 table the device takes for ``forest``, or None with the reason: ``(table, reason)``"""
+    table = np.asarray(features)
+    if table.ndim != 2 or table.dtype not in (np.float64, np.float32) or table.shape[1] != forest.n_features:
+        return None, 'the table is not a dense n x %d array of float64 or float32' % forest.n_features
+    if table.dtype == np.float32 and (forest.scaler_mean is not None or forest.scaler_scale is not None):
+        return None, 'a float32 table is scaled in float32 by scikit-learn'
+    return table.astype(np.float64, copy=False), None
+
+
+def predict_proba(model, features, on=None):
+    """ class probabilities of a trained classifier: ``model.predict_proba(features)``, or the same bytes (for ``n_jobs=1``; with
+    more jobs scikit-learn adds the trees in the order its threads finish) from the device for the models :class:`_hip.DeviceForest`
+    packs.  Asked for the device, a model or a table it does not take is evaluated on the host and the reason logged at INFO.
+
+    :param obj model: fitted classifier or ``Pipeline``
+    :param ndarray features: n x F
+    :param str on: None, 'host' or 'device'; None: IMSEGM_CLASSIF_ON, unset: 'host'
+    :return ndarray: n x C
+    """
+    if classif_place(on) == 'device':
+        forest, reason = device_forest(model)
+        table = None
+        if forest is not None:
+            table, reason = device_table(forest, features)
+        if table is not None:
+            try:
+                return _hip.forest_proba(forest, table)
+            except _hip.HipForestInputError as ex:
+                reason = str(ex)
+        logging.info('class model evaluated on the host: %s', reason)
+    return model.predict_proba(features)
 
 
 class CrossValidateGroups(object):

@@ -129,7 +129,7 @@ int imsegm_ctx_copy(imsegm_ctx *ctx, void *dst, const void *src, size_t bytes, i
 }
 
 const char *imsegm_last_error(void) { return g_error.c_str(); }
-int imsegm_version(void) { return 101; }
+int imsegm_version(void) { return 102; }
 
 int imsegm_init(int hardware_queues)
 {
@@ -275,7 +275,7 @@ void imsegm_image2d_destroy(imsegm_image2d *im)
     DevBuf *all[] = { &im->img, &im->labA, &im->labB, &im->nearest, &im->labels, &im->conn_i32, &im->conn_u8, &im->small,
                       &im->cent, &im->tiles, &im->feat, &im->graph, &im->gather_lut, &im->gather_out_i, &im->gather_out_f,
                       &im->tex_planes, &im->tex_resp, &im->tex_small, &im->tex_aux, &im->vol_cent, &im->annot, &im->hist, &im->featK, &im->seg,
-                      &im->gseg, &im->narrow, &im->conv };
+                      &im->gseg, &im->narrow, &im->conv, &im->forest };
     for (auto b : all) b->release();
     if (im->slic_fail_host) (void)hipHostFree(im->slic_fail_host);
     if (im->slic_exec) (void)hipGraphExecDestroy(im->slic_exec);
@@ -301,6 +301,7 @@ int imsegm_image2d_upload(imsegm_image2d *im, const void *host_pixels, int dtype
     im->dtype = dtype;
     im->conv_source = false;
     im->feat_mask = 0;
+    im->forest_ready = false;
     im->place_F = 0;
     return 0;
 }
@@ -387,6 +388,7 @@ int imsegm_image2d_device_ptr(imsegm_image2d *im, int which, void **ptr_out)
         set_error("device_ptr: buffer not available");
         return -1;
     }
+    if (which == 3) im->forest_ready = false;          // (the caller may write the table through this pointer)
     *ptr_out = b->p;
     return 0;
 }

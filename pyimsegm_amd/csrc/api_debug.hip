@@ -56,7 +56,7 @@ int imsegm_debug_image2d_poison(imsegm_image2d *im, uint32_t word, size_t *bytes
     DevBuf *all[] = { &im->img, &im->labA, &im->labB, &im->nearest, &im->labels, &im->conn_i32, &im->conn_u8, &im->small,
                       &im->cent, &im->tiles, &im->feat, &im->graph, &im->gather_lut, &im->gather_out_i, &im->gather_out_f,
                       &im->tex_planes, &im->tex_resp, &im->tex_small, &im->tex_aux, &im->vol_cent, &im->annot, &im->hist, &im->featK, &im->seg,
-                      &im->gseg, &im->narrow, &im->conv };
+                      &im->gseg, &im->narrow, &im->conv, &im->forest };
     for (auto b : all)
         if (fill(*b, word, st, total)) return -1;
     HIP_TRY(hipStreamSynchronize(st));
@@ -73,6 +73,7 @@ int imsegm_debug_image2d_poison(imsegm_image2d *im, uint32_t word, size_t *bytes
     im->conv_source = false;                               // no converted image
     im->gplan = GraphPlan();
     im->graph_ready = false;
+    im->forest_ready = false;
     im->feat_mask = 0;                                     // no resident feature table, no placement pending
     im->feat_F = 0;
     im->place_F = 0;

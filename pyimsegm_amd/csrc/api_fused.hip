@@ -181,6 +181,7 @@ int imsegm_image2d_features_color(imsegm_image2d *im, int feature_mask, double *
     if (launch_features_assemble(ss.mean, ss.energy, ss.var, K, feature_mask, im->featK.as<double>(), st, table_F, col0)) return -1;
     ctx->end(sp);
     im->feat_mask = table_F == F ? feature_mask : 8;          // (8: a table of several descriptor groups)
+    im->forest_ready = false;
     im->feat_F = table_F;
     if (features_out) {
         HIP_TRY(hipMemcpyAsync(features_out, im->featK.p, (size_t)K * F * 8, hipMemcpyDeviceToHost, st));
@@ -357,7 +358,9 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         return -1;
     }
     const int K = im->n_labels, C = n_classes;
-    if (C < 1 || C > 16 || !pairwise || (!gmm && !proba)) {
+    // neither a class model nor probabilities: those the last imsegm_image2d_forest_proba left for this label map and table
+    const bool from_forest = !gmm && !proba && im->forest_ready && im->forest_K == K && im->forest_C == C;
+    if (C < 1 || C > 16 || !pairwise || (!gmm && !proba && !from_forest)) {
         set_error("segment: 1..16 classes, a pairwise matrix and either a class model or probabilities are required");
         return -1;
     }
@@ -397,6 +400,8 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
     param_fill(bh, host, K, pairwise, classes_lut, gmm, proba);
     HIP_TRY(hipMemcpyAsync(bh.base, host, up_bytes, hipMemcpyHostToDevice, st));
     ctx->mark_stage_in_flight();
+    if (from_forest)
+        HIP_TRY(hipMemcpyAsync(bh.base + bh.par.o_pr, im->forest.as<unsigned char>() + 256, (size_t)K * C * 8, hipMemcpyDeviceToDevice, st));
     int32_t *misc = bh.misc();
     bh.K_dev = misc; bh.E_dev = misc + 1;
     // ---- graph: neighbour pairs + centres, then the symmetric CSR (im->gseg)
@@ -439,8 +444,9 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
     if (soft_out) HIP_TRY(hipMemcpyAsync(soft_out, im->gather_out_f.p, n * C * 8, hipMemcpyDeviceToHost, st));
     if (graph_labels_out) HIP_TRY(hipMemcpyAsync(graph_labels_out, bh.at<int32_t>(bh.scr.d_gl), (size_t)K * 4, hipMemcpyDeviceToHost, st));
     if (proba_out) HIP_TRY(hipMemcpyAsync(proba_out, bh.at<double>(bh.scr.d_proba), (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
-    int32_t hmisc[4] = { 0, 0, 0, 0 }, hgraph[4] = { 0, 0, 0, 0 };
+    int32_t hmisc[4] = { 0, 0, 0, 0 }, hgraph[4] = { 0, 0, 0, 0 }, hforest = 0;
     HIP_TRY(hipMemcpyAsync(hmisc, misc, sizeof(hmisc), hipMemcpyDeviceToHost, st));
+    if (from_forest) HIP_TRY(hipMemcpyAsync(&hforest, im->forest.p, 4, hipMemcpyDeviceToHost, st));
     if (prepared || g.table) HIP_TRY(hipMemcpyAsync(hgraph, ghead, sizeof(hgraph), hipMemcpyDeviceToHost, st));
     if (debug_out) {
         if (debug_out->unary) HIP_TRY(hipMemcpyAsync(debug_out->unary, bh.at<double>(bh.scr.d_unary), (size_t)K * C * 8, hipMemcpyDeviceToHost, st));
@@ -449,6 +455,11 @@ static int segment_impl(imsegm_image2d *im, const imsegm_gmm *gmm, const double 
         if (debug_out->energy) HIP_TRY(hipMemcpyAsync(debug_out->energy, misc + 4, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
+    if (hforest) {                               // (imsegm_image2d_forest_proba did not wait: its refusal of the table shows here)
+        im->forest_ready = false;
+        set_error("forest: the resident table holds a value that is not finite in float32");
+        return IMSEGM_E_FOREST_INPUT;
+    }
     const int E = prepared ? hgraph[1] : hmisc[1];
     if (g.table && hgraph[2]) {
         set_error("segment: too many labels for the fused path (a label with more than 64 neighbours in the neighbour table)");

@@ -281,6 +281,7 @@ int imsegm_image2d_slic(imsegm_image2d *im, int minmax_normalize, int n_segments
     im->have_labels = true;
     im->labels_connected = false;
     im->graph_ready = false;
+    im->forest_ready = false;
     if (n_labels_out) *n_labels_out = n_labels;
     return 0;
 }
@@ -313,6 +314,7 @@ int imsegm_image2d_set_labels(imsegm_image2d *im, const int32_t *labels, int n_l
     im->have_labels = true;
     im->labels_connected = false;
     im->graph_ready = false;
+    im->forest_ready = false;
     return 0;
 }
 
@@ -343,6 +345,7 @@ int imsegm_image2d_enforce_connectivity(imsegm_image2d *im, const int32_t *label
     im->have_labels = true;
     im->labels_connected = false;
     im->graph_ready = false;
+    im->forest_ready = false;
     if (n_labels_out) *n_labels_out = n_labels;
     return 0;
 }

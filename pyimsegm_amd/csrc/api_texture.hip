@@ -194,6 +194,7 @@ int imsegm_image2d_lm_features_sep(imsegm_image2d *im, const double *weights, co
     // called for the resident table (no host copy asked for): imsegm_image2d_segment reads it by feat_F; with a host copy the
     // table counts as consumed, as before
     im->feat_mask = features_out ? 0 : 8;
+    im->forest_ready = false;
     im->feat_F = table_F;
     if (features_out) {
         HIP_TRY(hipMemcpyAsync(features_out, im->featK.p, (size_t)K * F * 8, hipMemcpyDeviceToHost, st));

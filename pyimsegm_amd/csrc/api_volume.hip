@@ -42,6 +42,7 @@ int imsegm_volume_upload(imsegm_image2d *im, const void *host_voxels, int dtype,
     im->vol_off = slic_offset;
     im->vol_scale = slic_scale;
     im->tex_ready = false;
+    im->forest_ready = false;
     im->feat_mask = 0;            // (a recycled session: the feature table of the previous volume is not this one's)
     return 0;
 }
@@ -175,6 +176,7 @@ int imsegm_volume_slic(imsegm_image2d *im, int n_segments, double compactness, c
     im->have_labels = true;
     im->labels_connected = enforce_connectivity != 0;
     im->graph_ready = false;
+    im->forest_ready = false;
     if (n_labels_out) *n_labels_out = n_labels;
     return 0;
 }
@@ -249,6 +251,7 @@ int imsegm_volume_label_cc(imsegm_image2d *im, int *n_labels_out)
     HIP_TRY(hipStreamSynchronize(st));
     im->n_labels = total + 1;          // 0 = background, components 1 .. total
     im->graph_ready = false;
+    im->forest_ready = false;
     if (n_labels_out) *n_labels_out = im->n_labels;
     return 0;
 }

@@ -91,7 +91,7 @@ void param_fill(BackHalf &b, unsigned char *row, int K, const double *pairwise, 
         memcpy(row + P.o_mp, gmm->mu_proj, (size_t)C * F * 8);
         memcpy(row + P.o_ld, gmm->log_det, (size_t)C * 8);
         memcpy(row + P.o_lw, gmm->log_weights, (size_t)C * 8);
-    } else {
+    } else if (proba) {                                          // (null: the caller copies them on the device)
         memcpy(row + P.o_pr, proba, (size_t)K * C * 8);
     }
 }

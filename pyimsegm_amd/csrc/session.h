@@ -181,7 +181,10 @@ struct imsegm_image2d {
     // tex_aux: scratch of the statistics of a Leung-Malik response (median, gradient) -- tex_planes / tex_resp stay as they are
     DevBuf img, labA, labB, nearest, labels, conn_i32, conn_u8, small, cent, tiles, feat, graph, gather_lut, gather_out_i, gather_out_f,
         tex_planes, tex_resp, tex_small, tex_aux, vol_cent, annot, hist, featK, seg, gseg, narrow,
-        conv;                                   // the image in another colour space (colorspace.hip): float64 interleaved H x W x 3
+        conv,                                   // the image in another colour space (colorspace.hip): float64 interleaved H x W x 3
+        forest;                                 // 256 bytes of status (word 0: the table was refused) | K x C probabilities of imsegm_image2d_forest_proba
+    bool forest_ready = false;                  // `forest` belongs to the current label map and feature table (whatever changes either clears this)
+    int forest_K = 0, forest_C = 0;
     bool conv_source = false;                   // `conv` is what the statistic entry points read (imsegm_image2d_convert_color)
     GraphPlan gplan;                            // the graph imsegm_image2d_graph_prepare has enqueued into `gseg` ...
     bool graph_ready = false;                   // ... for the current label map (any call that changes the labels clears this)

@@ -208,6 +208,19 @@ def _convert_place(convert_on):
     return where
 
 
+def _resident_forest(model, classif_on):
+    """:class:`_hip.DeviceForest` of ``model`` when ``classif_on`` (None: IMSEGM_CLASSIF_ON, unset: 'host') asks for the device and
+    the model is one it takes -- :func:`classification.predict_proba` has the rules --, else None (asked for the device: with the
+    reason logged at INFO)"""
+    from pyimsegm_amd.classification import classif_place, device_forest
+    if classif_place(classif_on) != 'device':
+        return None
+    forest, reason = device_forest(model)
+    if forest is None:
+        logging.info('class model evaluated on the host: %s', reason)
+    return forest
+
+
 class _ResidentImage(object):
     """one image on the device: superpixels + features, then the fused class model / graph cut / gathers"""
 
@@ -264,26 +277,43 @@ class _ResidentImage(object):
         return self._slic
 
     def segment(self, proba, gc_regul, gc_edge_type, debug_visual=None, classes=None, to_host=True, want_soft=True,
-                model=None, segm_dtype=None, soft_dtype=None):
+                model=None, segm_dtype=None, soft_dtype=None, classif_on=None):
         """ graph cut + gathers.  ``proba``: K x C from the host, or None with ``model`` = a mixture the device evaluates
-        on the resident features.  Everything runs in one fused call (:meth:`_hip.Image2D.segment`) unless the edge
+        on the resident features -- or, with ``classif_on`` 'device', a tree ensemble (:func:`_resident_forest`): its
+        probabilities are computed on the resident table and the fused call takes them from there, nothing goes down or up and
+        nothing waits in between.  Everything runs in one fused call (:meth:`_hip.Image2D.segment`) unless the edge
         type needs the image on the host (``'color'``). """
         image = self.image
-        gmm = None
+        gmm = forest = None
+        fused = gc_edge_type in _hip.EDGE_TYPES and (gc_edge_type != 'features' or self.resident_features)
         if proba is None:
             gmm = _device_gmm(model) if self.resident_features else None
-            if gmm is None:
+            if gmm is None and self.resident_features:
+                forest = _resident_forest(model, classif_on)
+                if forest is not None and forest.n_features != self._table_columns:
+                    forest = None               # (scikit-learn's own error for the table, below)
+            if forest is not None:
+                try:
+                    proba = self.sess.forest_proba(forest, to_host=not fused)
+                except _hip.HipForestInputError as ex:
+                    logging.info('class model evaluated on the host: %s', ex)
+                    forest = None
+            if gmm is None and forest is None:
                 proba = predict_proba(model, self.features)
-        nb_classes = gmm.n_classes if gmm is not None else np.shape(proba)[1]
-        if gc_edge_type in _hip.EDGE_TYPES and (gc_edge_type != 'features' or self.resident_features):
+        nb_classes = gmm.n_classes if gmm is not None else forest.n_classes if forest is not None else np.shape(proba)[1]
+        if fused:
             from pyimsegm_amd.graph_cuts import compute_pairwise_cost, insert_gc_debug_images
             pairwise = compute_pairwise_cost(gc_regul, (self.nb_labels, nb_classes))
             use_gc = not (np.isscalar(gc_regul) and gc_regul <= 0)
             cls = None if classes is None else np.asarray(classes)
-            res = self.sess.segment(pairwise, gc_edge_type, gmm=gmm, proba=proba, use_graphcut=use_gc,
-                                    classes=None if cls is None else cls.astype(np.int32), want_segm=to_host,
-                                    want_soft=to_host and want_soft, debug=debug_visual is not None,
-                                    keep_soft_on_device=want_soft and not to_host, segm_dtype=segm_dtype, soft_dtype=soft_dtype)
+            keywords = dict(use_graphcut=use_gc, classes=None if cls is None else cls.astype(np.int32), want_segm=to_host,
+                            want_soft=to_host and want_soft, debug=debug_visual is not None,
+                            keep_soft_on_device=want_soft and not to_host, segm_dtype=segm_dtype, soft_dtype=soft_dtype)
+            try:
+                res = self.sess.segment(pairwise, gc_edge_type, gmm=gmm, proba=proba, **keywords)
+            except _hip.HipForestInputError as ex:       # (the forest call did not wait: its refusal of the table shows here)
+                logging.info('class model evaluated on the host: %s', ex)
+                res = self.sess.segment(pairwise, gc_edge_type, proba=predict_proba(model, self.features), **keywords)
             if debug_visual is not None:
                 insert_gc_debug_images(debug_visual, self.slic, res['graph_labels'], res['unary'], res['edges'],
                                        res['edge_weights'])
@@ -509,7 +539,7 @@ def estim_model_classes_group(list_images, nb_classes, dict_features, sp_size=30
 
 def segment_color2d_slic_features_model_graphcut(image, model_pipeline, dict_features, sp_size=30, sp_regul=0.2, gc_regul=1.,
                                                  gc_edge_type='model', debug_visual=None, segm_dtype=None, soft_dtype=None,
-                                                 convert_on=None):
+                                                 convert_on=None, classif_on=None):
     """ segmentation with a given (pre-trained) model: superpixels, features, predict, GraphCut
 
     :param ndarray image: input RGB image
@@ -520,6 +550,9 @@ def segment_color2d_slic_features_model_graphcut(image, model_pipeline, dict_fea
         100 MB a 2048 x 2048 x 3 float64 array takes), ``False``: it is not produced at all; None: float64 as the reference
     :param str convert_on: (not in the reference) where 'color_<space>' feature groups are converted: 'host' or 'device'; None:
         IMSEGM_CONVERT_ON
+    :param str classif_on: (not in the reference) where a random forest, extra trees or a decision tree behind an optional scaler
+        is evaluated: 'host' (scikit-learn, the default) or 'device' (on the resident feature table, with the bytes of
+        scikit-learn's ``n_jobs=1`` result; any other model stays on the host); None: IMSEGM_CLASSIF_ON
     :return tuple(ndarray,ndarray): segmentation H x W, soft segmentation H x W x nb_classes
     """
     logging.info('PIPELINE Superpixels-Features-Model-GraphCut')
@@ -528,14 +561,14 @@ def segment_color2d_slic_features_model_graphcut(image, model_pipeline, dict_fea
         fast = _segment_color2d_one_call(image, model_pipeline, dict_features, sp_size, sp_regul, gc_regul, gc_edge_type)
         if fast is not None:
             return fast
-    res = _ResidentImage(image, dict_features, sp_size, sp_regul, features_to_host=_device_gmm(model_pipeline) is None,
-                         convert_on=convert_on)
+    on_device = _device_gmm(model_pipeline) is not None or _resident_forest(model_pipeline, classif_on) is not None
+    res = _ResidentImage(image, dict_features, sp_size, sp_regul, features_to_host=not on_device, convert_on=convert_on)
     try:
         res.fill_debug(debug_visual)
         classes = getattr(model_pipeline, 'classes_', None)
         segm, segm_soft = res.segment(None, gc_regul, gc_edge_type, debug_visual, classes=classes, model=model_pipeline,
                                       want_soft=soft_dtype is not False, segm_dtype=segm_dtype,
-                                      soft_dtype=None if soft_dtype is False else soft_dtype)
+                                      soft_dtype=None if soft_dtype is False else soft_dtype, classif_on=classif_on)
     finally:
         res.close()
     return segm, segm_soft
@@ -543,14 +576,15 @@ def segment_color2d_slic_features_model_graphcut(image, model_pipeline, dict_fea
 
 def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeline, dict_features, sp_size=30,
                                                        sp_regul=0.2, gc_regul=1., gc_edge_type='model', group=None,
-                                                       nb_workers=NB_WORKERS):
+                                                       nb_workers=NB_WORKERS, classif_on=None):
     """ segment a batch of equally-sized images with a given model, sharded over the GPUs of one node
 
     Multi-GPU counterpart of mapping :func:`segment_color2d_slic_features_model_graphcut` over a
     process pool (reference ``run_segm_slic_model_graphcut.py:505-514``): one process per GPU, image *i* goes to
     rank ``i mod world``, the label maps are gathered on rank 0 over RCCL.  Without a process group it processes the
     images on this GPU, ``nb_workers`` of them in flight at a time (worker threads with one HIP stream each; a thread
-    spends its time inside two C calls per image, outside the interpreter lock).
+    spends its time inside two C calls per image, outside the interpreter lock).  ``classif_on``: where a tree ensemble is
+    evaluated, as in :func:`segment_color2d_slic_features_model_graphcut`.
 
     :return list(ndarray): label maps on rank 0 (``None`` on the other ranks)
     """
@@ -574,6 +608,8 @@ def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeli
                 if own:
                     group.close()
 
+    on_forest = not on_device and _resident_forest(model_pipeline, classif_on) is not None
+
     def _segment(image):
         # as segment_color2d_slic_features_model_graphcut, minus what a batch does not need: the soft
         # segmentation is not computed and the session buffers are recycled from image to image
@@ -581,9 +617,10 @@ def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeli
                                          want_soft=False, reuse=True)
         if fast is not None:
             return fast[0]
-        res = _ResidentImage(image, dict_features, sp_size, sp_regul, reuse=True, features_to_host=not on_device)
+        res = _ResidentImage(image, dict_features, sp_size, sp_regul, reuse=True, features_to_host=not (on_device or on_forest))
         try:
-            segm, _ = res.segment(None, gc_regul, gc_edge_type, classes=classes, want_soft=False, model=model_pipeline)
+            segm, _ = res.segment(None, gc_regul, gc_edge_type, classes=classes, want_soft=False, model=model_pipeline,
+                                  classif_on=classif_on)
         finally:
             res.close()
         return segm
@@ -592,10 +629,10 @@ def segment_batch_color2d_slic_features_model_graphcut(list_images, model_pipeli
         """a finished image whose label map is still in its session's HBM buffer (RCCL gather, zero copy)"""
 
         def __init__(self, image):
-            self.res = _ResidentImage(image, dict_features, sp_size, sp_regul, reuse=True, features_to_host=not on_device)
+            self.res = _ResidentImage(image, dict_features, sp_size, sp_regul, reuse=True, features_to_host=not (on_device or on_forest))
             try:
                 self.res.segment(None, gc_regul, gc_edge_type, classes=classes, to_host=False, want_soft=False,
-                                 model=model_pipeline)
+                                 model=model_pipeline, classif_on=classif_on)
                 self.ctx = self.res.sess.ctx
                 self.device_ptr = _hip.segm_device_array(self.res.sess).__cuda_array_interface__['data'][0]
             except BaseException:
