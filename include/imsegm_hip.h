@@ -864,6 +864,13 @@ IMSEGM_API int imsegm_correct_segm(imsegm_ctx *ctx, const void *img, int img_is_
  * call between two launches (one small download, one small upload). */
 IMSEGM_API int imsegm_center_levels(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int max_label, const double *levels,
                                     int n_levels, uint8_t *levels_out, int64_t *counts_out, double *centres_out);
+/* Diagnostic (no reference counterpart; tests): what imsegm_center_levels holds in front of its code pass, by the function that
+ * entry calls, stopped there.  d2_out (uint32 [height * width]): the squared distance of every pixel of a label 1 .. max_label to
+ * the nearest pixel of another value, 0 for other pixels; a map of one value has no such pixel and gets (y + 1)^2 + x^2.
+ * max2_out (uint32 [max_label + 1]): the largest d2 of every label; sums_out (int64 [3 (max_label + 1)]): pixel count, row sum,
+ * column sum.  Slot 0 stays 0.  Caps and errors as imsegm_center_levels. */
+IMSEGM_API int imsegm_debug_center_distances(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int max_label,
+                                             uint32_t *d2_out, uint32_t *max2_out, int64_t *sums_out);
 /* create_annot_centers without the files: the two calls above with the label map staying on the device.  counts_out and
  * centres_out hold IMSEGM_CENTER_ANNOT_MAX_LABELS + 1 rows; *n_labels_out = the number of labels (rows 1 .. n are filled). */
 IMSEGM_API int imsegm_create_annot_centers(imsegm_ctx *ctx, const void *img, int img_is_i32, int height, int width, int sel_radius,

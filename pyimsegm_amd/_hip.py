@@ -223,6 +223,7 @@ _SIGNATURES = {
                                      _vp, _vp, _ip]),
     'imsegm_correct_segm': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _ip]),
     'imsegm_center_levels': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    'imsegm_debug_center_distances': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     'imsegm_create_annot_centers': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _vp]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
@@ -2204,6 +2205,25 @@ def center_levels(labels, max_label, levels, ctx=None):
         return None
     _check(status)
     return out, counts[1:], centres[1:]
+
+
+def center_distances(labels, max_label, ctx=None):
+    """diagnostic (``imsegm_debug_center_distances``; tests): what ``imsegm_center_levels`` holds in front of its code pass -- (d2 uint32
+    H x W, max2 uint32 [max_label], sums int64 [max_label, 3] = pixel count, row sum, column sum; rows of the labels 1 .. max_label),
+    or None for a request outside the caps"""
+    if labels.ndim != 2 or labels.size == 0:
+        raise ValueError('the label map must be a non-empty 2-D array')
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    max_label = int(max_label)
+    d2 = np.empty(labels.shape, dtype=np.uint32)
+    max2, sums = np.zeros(max_label + 1, dtype=np.uint32), np.zeros((max_label + 1, 3), dtype=np.int64)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_debug_center_distances(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], max_label, _ptr(d2),
+                                                          _ptr(max2), _ptr(sums))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return d2, max2[1:], sums[1:]
 
 
 def create_annot_centers(img, sel_radius, min_size, levels, ctx=None):

@@ -118,6 +118,22 @@ int correct_run(imsegm_ctx *ctx, unsigned char *dev, const CaPlan &p, int is_i32
     return 0;
 }
 
+// the labels on the device at o_labels -> d2 at o_b (with_distances), max2, pixel counts and sums of the labels in the zeroed tables:
+// what the level chain runs in front of its code pass (imsegm_debug_center_distances stops here)
+int levels_front(imsegm_ctx *ctx, unsigned char *dev, const CaPlan &p, int H, int W, int max_label, bool with_distances)
+{
+    hipStream_t st = ctx->stream;
+    const int32_t *labels = reinterpret_cast<int32_t *>(dev + p.o_labels);
+    uint32_t *d2 = with_distances ? reinterpret_cast<uint32_t *>(dev + p.o_b) : nullptr;
+    HIP_TRY(hipMemsetAsync(dev + p.o_tables, 0, p.tables_bytes, st));
+    if (with_distances &&
+        launch_ca_distances(labels, H, W, max_label, reinterpret_cast<uint32_t *>(dev + p.o_a), reinterpret_cast<int *>(dev + p.o_foreign), d2,
+                            st))
+        return -1;
+    return launch_ca_reduce(labels, d2, H, W, max_label, reinterpret_cast<uint32_t *>(dev + p.o_max2),
+                            reinterpret_cast<unsigned long long *>(dev + p.o_sums), st);
+}
+
 // the labels on the device at o_labels -> the level map at o_m2 (n_levels > 0), counts and centres of the labels 0 .. max_label on
 // the host.  Returns IMSEGM_E_OBJECT_CAPS when a level asks for an opening above IMSEGM_MORPH_MAX_RADIUS.
 int levels_run(imsegm_ctx *ctx, unsigned char *dev, const CaPlan &p, int H, int W, int max_label, const double *levels, int n_levels,
@@ -128,14 +144,8 @@ int levels_run(imsegm_ctx *ctx, unsigned char *dev, const CaPlan &p, int H, int 
     uint32_t *d2 = n_levels ? reinterpret_cast<uint32_t *>(dev + p.o_b) : nullptr;
     uint32_t *max2 = reinterpret_cast<uint32_t *>(dev + p.o_max2), *lcount = reinterpret_cast<uint32_t *>(dev + p.o_lcount);
     uint8_t *code = dev + p.o_m0, *tmp = dev + p.o_m1, *out = dev + p.o_m2;
-    HIP_TRY(hipMemsetAsync(dev + p.o_tables, 0, p.tables_bytes, st));
-    if (n_levels) {
-        HIP_TRY(hipMemcpyAsync(dev + p.o_levels, levels, (size_t)n_levels * 8, hipMemcpyHostToDevice, st));
-        if (launch_ca_distances(labels, H, W, max_label, reinterpret_cast<uint32_t *>(dev + p.o_a), reinterpret_cast<int *>(dev + p.o_foreign),
-                                d2, st))
-            return -1;
-    }
-    if (launch_ca_reduce(labels, d2, H, W, max_label, max2, reinterpret_cast<unsigned long long *>(dev + p.o_sums), st)) return -1;
+    if (n_levels) HIP_TRY(hipMemcpyAsync(dev + p.o_levels, levels, (size_t)n_levels * 8, hipMemcpyHostToDevice, st));
+    if (levels_front(ctx, dev, p, H, W, max_label, n_levels > 0)) return -1;
     if (n_levels &&
         launch_ca_code(labels, d2, H, W, max_label, max2, reinterpret_cast<double *>(dev + p.o_levels), n_levels, code, lcount, st))
         return -1;
@@ -196,6 +206,25 @@ int levels_run(imsegm_ctx *ctx, unsigned char *dev, const CaPlan &p, int H, int 
 }
 
 }  // namespace
+
+int ca_debug_distances(imsegm_ctx *ctx, const int32_t *labels, int H, int W, int max_label, uint32_t *d2_out, uint32_t *max2_out,
+                       int64_t *sums_out)
+{
+    if (const int status = check_size("debug_center_distances", H, W)) return status;
+    if (bind(ctx)) return -1;
+    hipStream_t st = ctx->stream;
+    const size_t n = (size_t)H * W, slots = (size_t)max_label + 1;
+    const CaPlan p = ca_plan(H, W);
+    if (ctx->gc_buf.ensure(p.bytes)) return -1;
+    unsigned char *dev = ctx->gc_buf.as<unsigned char>();
+    HIP_TRY(hipMemcpyAsync(dev + p.o_labels, labels, n * 4, hipMemcpyHostToDevice, st));
+    if (levels_front(ctx, dev, p, H, W, max_label, true)) return -1;
+    HIP_TRY(hipMemcpyAsync(d2_out, dev + p.o_b, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(max2_out, dev + p.o_max2, slots * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sums_out, dev + p.o_sums, slots * 3 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
 
 }  // namespace imsegm
 

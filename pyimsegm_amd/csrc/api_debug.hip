@@ -1,7 +1,9 @@
 // api_debug.hip -- diagnostics for the tests of reused scratch (tests/test_gpu_stale_scratch.py): fill everything a context or a
 // session owns on the device with one word, and put the host-side bookkeeping back to that of a new object.  After the call the
 // object is a new one in all but two respects: its buffers keep their capacity, and they hold the word instead of whatever
-// hipMalloc would have returned.
+// hipMalloc would have returned.  And what imsegm_center_levels holds on the device in front of its code pass
+// (tests/test_gpu_center_annotation_edges.py).
+#include "center_annotation.h"
 #include "session.h"
 
 namespace {
@@ -87,6 +89,21 @@ int imsegm_debug_image2d_poison(imsegm_image2d *im, uint32_t word, size_t *bytes
     im->slic_key.clear();
     if (bytes_out) *bytes_out = total;
     return 0;
+}
+
+int imsegm_debug_center_distances(imsegm_ctx *ctx, const int32_t *labels, int height, int width, int max_label, uint32_t *d2_out,
+                                  uint32_t *max2_out, int64_t *sums_out)
+{
+    if (!labels || !d2_out || !max2_out || !sums_out) {
+        set_error("debug_center_distances: null argument");
+        return -1;
+    }
+    if (max_label < 1) {
+        set_error("debug_center_distances: the largest label must be positive");
+        return -1;
+    }
+    if (max_label > IMSEGM_CENTER_ANNOT_MAX_LABELS) return IMSEGM_E_OBJECT_CAPS;
+    return imsegm::ca_debug_distances(ctx, labels, height, width, max_label, d2_out, max2_out, sums_out);
 }
 
 }  // extern "C"

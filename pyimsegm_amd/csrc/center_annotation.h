@@ -5,6 +5,8 @@
 #include "common.h"
 #include "morphology.h"
 
+struct imsegm_ctx;
+
 namespace imsegm {
 
 // labels 1 .. CA_MAX_LABELS own a slot of the per-label tables, a level one of the MORPH_LEVEL_SLOTS bits of a code byte
@@ -41,5 +43,11 @@ int launch_ca_code(const int32_t *labels, const uint32_t *d2, int H, int W, int 
 // bit i >= 1 of code[p] cleared outside discs[label * CA_MAX_LEVELS + i]; out[p] = bit 0 of code[p] (level 1 of the result)
 int launch_ca_discs(const int32_t *labels, int H, int W, int max_label, const CaDisc *discs, int n_levels, uint8_t *code, uint8_t *out,
                     hipStream_t st);
+
+// (api_center_annotation.hip, for imsegm_debug_center_distances) the front of imsegm_center_levels' chain -- the function that chain
+// calls, up to its code pass -- on a host label map: d2 [H * W], max2 [max_label + 1] and count, row sum, column sum
+// [3 (max_label + 1)] come to the host.  IMSEGM_E_OBJECT_CAPS for a map outside the size caps.
+int ca_debug_distances(imsegm_ctx *ctx, const int32_t *labels, int H, int W, int max_label, uint32_t *d2_out, uint32_t *max2_out,
+                       int64_t *sums_out);
 
 }  // namespace imsegm

@@ -4,6 +4,9 @@
   scikit-image 0.18.3 (tests/golden/center_annotation.npz, made by tests/golden/make_golden_center_annotation.py), centres to the
   last bit;
 * every case of tests/center_annotation_cases.py lies on the side of its rule that it is named for;
+* on the edge tables (``ROW_CASES``, the run-rule maps, ``CORRECT_EDGE_CASES``) the two statements of the squared distance -- the
+  brute-force integer minimum and scipy's per-label distance transform -- agree, the host statement of the correction equals its
+  restatement from scipy's parts, and every case reaches the window, workgroup or size edge it is built for;
 * the public names, the place switch, the errors for bad input, the doctests."""
 import doctest
 
@@ -162,3 +165,93 @@ def test_doctests():
         runner.run(parser.get_doctest(text, dict(annot.__dict__), name, 'tests/doctests/center_annotation.py', 0))
     result = runner.summarize(verbose=False)
     assert result.failed == 0 and result.attempted >= 12
+
+
+# ------------------------------------------------------------------------------------------------
+# the edge tables (the device side: tests/test_gpu_center_annotation_edges.py)
+# ------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize('name', list(C.ROW_CASES))
+def test_row_case_distances_two_ways_and_its_edge(name):
+    case = C.row_case(name)
+    seg = case['seg']
+    assert seg.shape[0] <= 5 and seg.shape[1] <= 780
+    brute = C.brute_force_d2(seg)
+    if brute is None:
+        assert name == 'no_foreign_3x257' and seg.shape == (3, 257)
+    else:
+        assert np.array_equal(brute, C.edt_d2(seg))
+    want = C.expected_d2(seg, int(seg.max()))
+    for r, c, dc, side, dr in case['probes']:
+        assert want[r, c] == dc * dc + dr * dr and seg[r, c] == 1
+        hole = c - dc if side == 'left' else c + dc
+        assert (seg[:, hole] != 1).any() and (seg[r, min(c, hole) + 1:max(c, hole)] == 1).all()
+    if name in ('left_end', 'right_end', 'at_266', 'at_513', 'at_513_egg', 'one_row', 'one_row_left_end'):
+        assert {dc for _, _, dc, _, dr in case['probes'] if dr == 0} == set(C.HANDOVER)
+        if seg.shape[0] > 1:
+            assert {dc for _, _, dc, _, dr in case['probes'] if dr > 0} == set(C.HANDOVER)       # k^2 + g^2 decides
+    if name == 'none_columns':
+        whole = (seg == seg[0]).all(axis=0)
+        assert whole.any() and not whole.all() and want[3].max() >= 256 ** 2
+    if name == 'alternate_columns':
+        assert (want == 1).all() and (seg[:, :-1] != seg[:, 1:]).all()
+
+
+def test_row_cases_probe_every_workgroup_and_side():
+    seen = set()
+    for name in ('left_end', 'right_end', 'at_266', 'at_513'):
+        case = C.row_case(name)
+        last = (case['seg'].shape[1] - 1) // C.WINDOW
+        for _, c, dc, side, _ in case['probes']:
+            seen.add(('first' if c < C.WINDOW else 'last' if c // C.WINDOW == last else 'middle', side, dc >= C.WINDOW))
+    for place in ('first', 'middle', 'last'):
+        assert (place, 'left' if place != 'first' else 'right', True) in seen
+    assert ('first', 'right', True) in seen and ('last', 'left', True) in seen and ('middle', 'right', True) in seen
+    assert {name: C.row_case(name)['probes'][0][3] for name in ('left_end', 'right_end')} == {'left_end': 'left', 'right_end': 'right'}
+    assert {side for _, _, _, side, _ in C.row_case('left_end')['probes']} == {'left'}
+    assert {side for _, _, _, side, _ in C.row_case('right_end')['probes']} == {'right'}
+
+
+def test_run_rule_maps_distances_two_ways():
+    for key, seg in C.run_level_maps():
+        brute = C.brute_force_d2(seg)
+        if brute is not None:
+            assert np.array_equal(brute, C.edt_d2(seg)), key
+
+
+@pytest.mark.parametrize('name', list(C.ROW_CASES))
+def test_row_case_levels_on_the_host(name):
+    """the host statement takes the cases (the device is held to it): level 1 is the egg, the centre the mean of its pixels"""
+    case = C.row_case(name)
+    seg = case['seg']
+    levels = annot.segm_center_levels_host(seg, case['levels'])
+    assert ((levels > 0) == (seg > 0)).all() or name == 'one_column'
+    centres = annot.compute_eggs_center_host(seg)
+    rows, cols = np.nonzero(seg == 1)
+    assert centres[0].tolist() == [cols.sum() / len(cols), rows.sum() / len(rows)]
+
+
+@pytest.mark.parametrize('name', list(C.CORRECT_EDGE_CASES))
+def test_correction_edge_case_equals_scipy_parts(name):
+    case = C.correct_edge_case(name)
+    img, radius, min_size = case['img'], case['sel_radius'], case['min_size']
+    assert img.shape[1] == C.CORRECT_W == 320
+    seg, seg_lb = annot.correct_segm_host(**case)
+    want_seg, want_lb = C.scipy_correct(**case)
+    assert C.same(seg, want_seg) and C.same(seg_lb, want_lb)
+    opened = ndimage.binary_opening(img > 0, structure=C._disc(radius)) if radius else img > 0
+    assert (opened.sum() < (img > 0).sum()) == (radius > 0)
+    parts, count = ndimage.label(opened)
+    sizes = np.bincount(parts.ravel())
+    # a component of exactly min_size pixels made of runs in two workgroups; one of fewer pixels beside it goes
+    exact = [p for p in range(1, count + 1) if sizes[p] == min_size]
+    assert exact and any((parts[:, :256] == p).any() and (parts[:, 256:] == p).any() for p in exact)
+    assert all(seg[parts == p].all() for p in exact) and (sizes[1:] < min_size).any()
+    # a blob across columns 255 / 256 of one row
+    assert (seg[:, 255] & seg[:, 256]).any()
+    # two blobs that touch only diagonally across the boundary: two 4-connected parts, one label
+    r = next(r for r in range(img.shape[0] - 1) if seg[r, 255] and seg[r + 1, 256] and not seg[r, 256] and not seg[r + 1, 255])
+    assert parts[r, 255] != parts[r + 1, 256] and seg_lb[r, 255] == seg_lb[r + 1, 256] > 0
+    assert ndimage.label(seg)[1] == seg_lb.max() + 1
+    assert seg[:, -1].any()                                                 # a run that ends with the row

@@ -6,6 +6,10 @@
   scipy's order of the three fp64 operations per coordinate and its rule for what lies outside the source;
 * integer masks (INT64_MIN outside the turned frame counts as True under ``use_mask``) equal their golden vectors;
 * the canvas window handed to the device contains the box of the turned mask;
+* on every edge case of tests/cut_objects_cases.py (``EDGE_CASES``: rounding ties of the shift, coordinates on the last pixel, turns
+  of exactly 0, +-90 and 180 degrees, one to four channels, ``use_mask`` on and off) the statement equals the reference's statements
+  with scipy's own ``shift`` and ``rotate``, byte for byte; every case reaches the edge it is named for; the run-rule maps
+  (``RUN_MAPS``) reach their branches and their ten words are int64 sums;
 * the doctests run, and ``imsegm.utilities.data_io`` resolves the names without a reference installed."""
 import doctest
 import os
@@ -144,3 +148,98 @@ def test_alias_resolves_without_a_reference():
     env = dict(os.environ, IMSEGM_REFERENCE='', IMSEGM_CUT_OBJECTS_ON='host')
     out = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert out.returncode == 0 and 'resolved' in out.stdout, out.stderr
+
+
+# ------------------------------------------------------------------------------------------------
+# the edge tables (the device side: tests/test_gpu_cut_objects_edges.py)
+# ------------------------------------------------------------------------------------------------
+
+
+def _same(got, want):
+    return got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
+
+
+@pytest.mark.parametrize('name', list(C.EDGE_CASES))
+def test_edge_case_host_statement_equals_scipy(name):
+    base = C.EDGE_CASES[name]
+    channels_seen = set()
+    for tag, inputs in C.edge_variants(name):
+        channels_seen.add(inputs['img'].shape[2:])
+        assert len(set(np.atleast_1d(inputs['bg_color']).tolist())) == np.size(inputs['bg_color'])
+        for label in inputs['labels']:
+            host, scipy_crop = C.edge_host_crop(name, inputs, label), C.edge_scipy_crop(name, inputs, label)
+            assert _same(host, scipy_crop), (name, tag, label, np.argwhere(host != scipy_crop)[:8].tolist() if host.shape == scipy_crop.shape
+                                             else (host.shape, scipy_crop.shape))
+            if 'crop' in base:
+                assert host.shape[:2] == base['crop']
+    assert channels_seen == {(), (1, ), (2, ), (3, ), (4, )}
+
+
+@pytest.mark.parametrize('name', list(C.EDGE_CASES))
+def test_edge_case_reaches_its_edge(name):
+    base = C.EDGE_CASES[name]
+    height, width = base['segm'].shape
+    if not base['allow_rotate']:
+        assert 'crop' in base
+        return
+    ties = np.array([C.edge_ties(name, label) for label in base['labels']])
+    for label in base['labels']:
+        moments = data_io._region_moments(base['segm'] == label)
+        geometry = C.edge_geometry(name, moments, (height, width))
+        assert geometry['angle'] == base['turn'] and abs(geometry['angle']) in (0., 90., 180.)          # exactly
+        assert geometry['centroid'] == (moments[1] / moments[0], moments[2] / moments[0])
+        assert set(np.abs(geometry['matrix']).ravel().tolist()) == {0., 1.}
+    assert ties[:, 0].sum() > 0, 'no shift coordinate at k + 0.5'
+    assert ties[:, 2].sum() > 0, 'no rotation coordinate on the last pixel'
+    if name.startswith(('level', 'upright')):
+        # both centroid coordinates of the rectangle are half-integers; a frame with an even side makes the shift along it one too
+        centroid = C.edge_geometry(name, data_io._region_moments(base['segm'] == 1), (height, width))['centroid']
+        assert all(c - np.floor(c) == 0.5 for c in centroid)
+    if name.startswith('all_borders'):
+        segm = base['segm']
+        assert segm[0].any() and segm[-1].any() and segm[:, 0].any() and segm[:, -1].any()
+
+
+def test_edge_frames_cover_every_parity_and_turn():
+    shapes = {C.EDGE_CASES[name]['segm'].shape for name in C.EDGE_CASES if name.startswith(('level', 'upright'))}
+    assert {(h % 2, w % 2) for h, w in shapes} == {(0, 0), (0, 1), (1, 0)}
+    assert {C.EDGE_CASES[name]['turn'] for name in C.EDGE_CASES} == {0, 90, -90, 180}
+    assert {C.EDGE_CASES[name]['crop'] for name in C.EDGE_CASES if 'crop' in C.EDGE_CASES[name]} == {(16, 64), (17, 65), (33, 129)}
+    # a region's own orientation cannot give the two forced turns
+    assert C.TURNS[180] is not None and C.TURNS[-90] is not None
+
+
+@pytest.mark.parametrize('width', C.RUN_WIDTHS)
+def test_run_rule_maps_reach_their_branches(width):
+    for layout in C.RUN_LAYOUTS:
+        ids = C.run_map(width, layout)
+        img, segm, labels, listed = C.run_cut_inputs(width, layout)
+        assert 3 <= ids.shape[0] <= 6 and ids.shape[1] == width
+        reached = C.run_branches(ids, listed)
+        for need, widths in C.RUN_REACH[layout] + C.RUN_REACH_ALWAYS:
+            if widths is None or width in widths:
+                assert need in reached, (width, layout, need)
+        # the list holds the smallest and the largest value of the map unless that is the unlisted one
+        values = [v for v in np.unique(segm).tolist() if v != C.RUN_CUT_VALUES[C.RUN_UNLISTED_ID]]
+        assert labels[0] == min(values) and labels[-1] == max(values)
+    values = {int(v) for layout in C.RUN_LAYOUTS for v in np.unique(C.run_cut_inputs(width, layout)[1])}
+    assert min(values) < 0 and 0 in values and 2 ** 31 - 1 in values
+    corner = C.run_cut_inputs(width, 'corner')[1]
+    assert (corner == corner[-1, -1]).sum() == 1
+
+
+@pytest.mark.parametrize('width', C.RUN_WIDTHS)
+def test_run_rule_maps_on_the_host(width):
+    """``cut_objects`` on the host is the loop over ``cut_object_host``; the ten words of ``_region_moments`` are int64 sums"""
+    rows_cols = {}
+    for layout in C.RUN_LAYOUTS:
+        img, segm, labels, _ = C.run_cut_inputs(width, layout)
+        rows, cols = rows_cols.setdefault(segm.shape, np.indices(segm.shape).astype(np.int64))
+        crops = data_io.cut_objects(img, segm, labels, padding=1, allow_rotate=False, on='host')
+        for label, crop in zip(labels, crops):
+            mask = segm == label
+            r, c = rows[mask], cols[mask]
+            want = [mask.sum(), r.sum(), c.sum(), (r * r).sum(), (c * c).sum(), (r * c).sum(), r.min(), r.max(), c.min(), c.max()]
+            assert list(data_io._region_moments(mask)) == [int(v) for v in want]
+            box = data_io.add_padding(segm.shape, 1, r.min(), c.min(), r.max() + 1, c.max() + 1)
+            assert _same(crop, img[box[0]:box[2], box[1]:box[3]])
