@@ -52,6 +52,11 @@ extern "C" {
  * caller evaluates the model on the host */
 #define IMSEGM_E_FOREST_INPUT (-6)
 
+/* status of imsegm_dbscan_points for the input scikit-learn's DBSCAN answers with a ValueError -- a coordinate that is not finite,
+ * eps that is not a positive finite number, min_samples below 1: nothing is written to the outputs, nothing is wrong with the
+ * context */
+#define IMSEGM_E_CLUSTER_INPUT (-7)
+
 typedef struct imsegm_ctx imsegm_ctx;           /* one device + one stream */
 typedef struct imsegm_image2d imsegm_image2d;   /* device-resident state of one H x W image */
 
@@ -983,6 +988,28 @@ IMSEGM_API int imsegm_forest_proba(imsegm_ctx *ctx, const imsegm_forest *forest,
  * call then does not wait, and a table the forest refuses shows as IMSEGM_E_FOREST_INPUT of that segment call.  Any call that
  * changes the label map or the feature table drops the probabilities, as it drops the prepared graph. */
 IMSEGM_API int imsegm_image2d_forest_proba(imsegm_image2d *img, const imsegm_forest *forest, double *proba_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * clustering of centre candidates (version >= 103): experiments_ovary_centres/run_center_clustering.py::cluster_center_candidates
+ * :61-83 of the reference -- scikit-learn's DBSCAN(eps, min_samples).fit(points).labels_ and np.mean(points[labels == i], axis=0)
+ * per cluster -- for many sets of 2-D points in one call, one workgroup per set.  The closed form of scikit-learn's scan:
+ *   near(a, b):  dx * dx + dy * dy <= eps * eps in fp64, two rounded products and one rounded sum (no fused multiply-add);
+ *                every point is near itself
+ *   core:        at least min_samples points of the set are near
+ *   clusters:    the connected components of the core points under near, numbered 0, 1, ... by their smallest core index
+ *   border:      a point that is not core takes the smallest cluster number among the core points near it; -1 (noise) without one
+ *   centre:      the sum of the cluster's points in index order, in fp64, over their count
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_DBSCAN_MAX_POINTS 4096      /* points of one set: its coordinates and forest live in the LDS of one compute unit */
+#define IMSEGM_DBSCAN_MAX_SETS 4096        /* sets of one call */
+#define IMSEGM_DBSCAN_MAX_TOTAL (1 << 20)  /* points of one call (the page-locked staging block holds 36 bytes per point) */
+/* points [offsets[nb_sets]][2] as (row, col), offsets [nb_sets + 1] (not descending; set s is the rows offsets[s] .. offsets[s + 1]
+ * - 1, empty sets allowed) -> labels_out [offsets[nb_sets]], counts_out [nb_sets] (clusters per set), centres_out
+ * [offsets[nb_sets]][2]: row offsets[s] + c is the centre of cluster c of set s, the other rows of the set are 0.  Equal bytes from
+ * every call on equal input.  Returns IMSEGM_E_OBJECT_CAPS -- no message, the caller clusters on the host -- outside the three caps
+ * above, and IMSEGM_E_CLUSTER_INPUT with the outputs untouched for what scikit-learn raises a ValueError. */
+IMSEGM_API int imsegm_dbscan_points(imsegm_ctx *ctx, const double *points, const int32_t *offsets, int nb_sets, double eps,
+                                    int min_samples, int32_t *labels_out, int32_t *counts_out, double *centres_out);
 
 #ifdef __cplusplus
 }

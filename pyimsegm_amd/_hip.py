@@ -57,10 +57,17 @@ class HipForestInputError(HipError):
     written, nothing is wrong with the context, the caller evaluates the model on the host"""
 
 
+class HipClusterInputError(HipError, ValueError):
+    """``IMSEGM_E_CLUSTER_INPUT`` of include/imsegm_hip.h: ``imsegm_dbscan_points`` refuses what scikit-learn's DBSCAN answers with a
+    ``ValueError`` (a coordinate that is not finite, ``eps`` that is not positive and finite, ``min_samples`` below 1) -- nothing
+    was written, nothing is wrong with the context"""
+
+
 IMSEGM_E_FUSED_PATH = -3
 IMSEGM_E_FIT_CAPS = -4
 IMSEGM_E_OBJECT_CAPS = -5
 IMSEGM_E_FOREST_INPUT = -6
+IMSEGM_E_CLUSTER_INPUT = -7
 
 
 _lib = None
@@ -231,6 +238,7 @@ _SIGNATURES = {
     'imsegm_score_pairs': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     'imsegm_forest_proba': (C.c_int, [_vp, C.POINTER(ForestParams), _vp, C.c_int, C.c_int, _vp]),
     'imsegm_image2d_forest_proba': (C.c_int, [_vp, C.POINTER(ForestParams), _vp]),
+    'imsegm_dbscan_points': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_double, C.c_int, _vp, _vp, _vp]),
 }
 
 #: every symbol ``include/imsegm_hip.h`` declares
@@ -297,7 +305,7 @@ def _check(status):
     if status != 0:
         message = load_library().imsegm_last_error().decode('utf-8', 'replace')
         raise {IMSEGM_E_FUSED_PATH: HipFusedPathError, IMSEGM_E_FIT_CAPS: HipFitCapsError,
-               IMSEGM_E_FOREST_INPUT: HipForestInputError}.get(status, HipError)(message)
+               IMSEGM_E_FOREST_INPUT: HipForestInputError, IMSEGM_E_CLUSTER_INPUT: HipClusterInputError}.get(status, HipError)(message)
 
 
 _device_count = {}
@@ -2243,6 +2251,39 @@ def create_annot_centers(img, sel_radius, min_size, levels, ctx=None):
     _check(status)
     n = n_labels.value
     return out, counts[1:n + 1], centres[1:n + 1]
+
+
+#: ``IMSEGM_DBSCAN_MAX_POINTS`` / ``IMSEGM_DBSCAN_MAX_SETS`` / ``IMSEGM_DBSCAN_MAX_TOTAL``
+DBSCAN_MAX_POINTS, DBSCAN_MAX_SETS, DBSCAN_MAX_TOTAL = 4096, 4096, 1 << 20
+
+
+def dbscan_points(points_concat, offsets, eps, min_samples, ctx=None, out=None):
+    """``imsegm_dbscan_points``: DBSCAN of the sets ``offsets`` (int32 [S + 1], not descending) cuts out of the C-contiguous float64
+    rows ``points_concat`` [P, 2] as (row, col): (labels int32 [P], cluster counts int32 [S], centres float64 [P, 2] -- row
+    ``offsets[s] + c`` is the centre of cluster c of set s, the other rows are 0).  ``out``: the three arrays to write into.  A
+    request outside the caps (``IMSEGM_E_OBJECT_CAPS``) gives None -- no error; what scikit-learn refuses raises
+    :class:`HipClusterInputError`, a ``ValueError``, and leaves ``out`` as it came."""
+    if points_concat.dtype != np.float64 or points_concat.ndim != 2 or points_concat.shape[1] != 2 or not points_concat.flags.c_contiguous:
+        raise ValueError('the points must be a C-contiguous float64 array [P, 2]')
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32).ravel()
+    nb_sets = len(offsets) - 1
+    if nb_sets < 0 or (nb_sets and int(offsets[-1]) > len(points_concat)):
+        raise ValueError('dbscan_points: the offsets must span the point list')
+    total = len(points_concat)
+    if out is None:
+        out = np.zeros(total, dtype=np.int32), np.zeros(nb_sets, dtype=np.int32), np.zeros((total, 2), dtype=np.float64)
+    labels, counts, centres = out
+    if (labels.dtype != np.int32 or counts.dtype != np.int32 or centres.dtype != np.float64 or labels.shape != (total, )
+            or counts.shape != (nb_sets, ) or centres.shape != (total, 2)
+            or not (labels.flags.c_contiguous and counts.flags.c_contiguous and centres.flags.c_contiguous)):
+        raise ValueError('out: int32 [P], int32 [S] and float64 [P, 2], C-contiguous')
+    ctx = ctx or default_context()
+    status = load_library().imsegm_dbscan_points(ctx._h, _ptr(points_concat), _ptr(offsets), nb_sets, float(eps),
+                                                 int(np.clip(min_samples, -2 ** 31, 2 ** 31 - 1)), _ptr(labels), _ptr(counts), _ptr(centres))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return labels, counts, centres
 
 
 #: ``IMSEGM_ANNOT_MAX_COLORS``: entries of a colour table of the ``imsegm_annot_*`` calls

@@ -129,7 +129,7 @@ int imsegm_ctx_copy(imsegm_ctx *ctx, void *dst, const void *src, size_t bytes, i
 }
 
 const char *imsegm_last_error(void) { return g_error.c_str(); }
-int imsegm_version(void) { return 102; }
+int imsegm_version(void) { return 103; }
 
 int imsegm_init(int hardware_queues)
 {

@@ -1050,6 +1050,45 @@ def shift_ray_features(ray_dist, method='phase'):
     return np.array(ray_dist[steps:].tolist() + ray_dist[:steps].tolist()), shift
 
 
+def shift_ray_features_rows(rays, method='phase'):
+    """ :func:`shift_ray_features` of every row of a P x A table at once: the five periods side by side, the mean taken off per row,
+    ONE ``np.fft.fft(axis=1)`` and one ``argmax`` for the whole table instead of P small ones (numpy transforms every row of a batch
+    with the routine it takes for a single vector, so the spectra are the bits of the row loop); the rotation per row keeps the
+    loop's Python ``round``.  The table has the dtype ``np.array`` gives the loop's lists (float64 for any float table).
+
+    >>> rays, shifts = shift_ray_features_rows(np.array([[43, 46, 44, 39, 28, 18, 12, 10,  9, 12, 22, 28]] * 2))
+    >>> rays.tolist()[1], [round(float(s), 1) for s in shifts]
+    ([46, 44, 39, 28, 18, 12, 10, 9, 12, 22, 28, 43], [41.5, 41.5])
+
+    :param ndarray rays: P x A
+    :return tuple(ndarray,list(float)): the rotated rows, the shifts in degrees
+    """
+    rays = np.asarray(rays)
+    if rays.ndim != 2 or rays.size == 0:
+        return rays, [0.] * (len(rays) if rays.ndim == 2 else 0)
+    nb_angles = rays.shape[1]
+    angle_step = 360 / nb_angles
+    if method == 'phase':
+        periods = np.hstack([rays] * 5)
+        half = periods.shape[1] // 2
+        spectrum = np.fft.fft(periods - np.mean(periods, axis=1, keepdims=True), axis=1) / float(periods.shape[1])
+        rows = np.arange(len(rays))
+        strongest = np.argmax(np.abs(spectrum)[:, :half], axis=1)
+        shifts = np.rad2deg(-np.angle(spectrum)[:, :half][rows, strongest])
+        shifts = [(360 + shift) if shift < 0 else shift for shift in shifts]
+    else:
+        shifts = [float(best * angle_step) for best in np.argmax(rays, axis=1)]
+    steps = np.array([int(round(shift / angle_step)) for shift in shifts], dtype=np.int64)
+    # row[steps:] + row[:steps] of the loop: a step at or beyond the row's end leaves the row as it is, a negative one counts from it
+    steps = np.where(steps >= nb_angles, 0, np.where(steps < 0, np.maximum(steps + nb_angles, 0), steps))
+    turned = np.take_along_axis(rays, (np.arange(nb_angles)[None, :] + steps[:, None]) % nb_angles, axis=1)
+    if turned.dtype.kind == 'f' and turned.dtype.itemsize <= 8:
+        return turned.astype(np.float64), shifts
+    if turned.dtype.kind == 'b' or (turned.dtype.kind == 'i' and turned.dtype.itemsize <= 8):
+        return turned.astype(np.bool_ if turned.dtype.kind == 'b' else np.int64), shifts
+    return np.array(turned.tolist()), shifts
+
+
 def _border_table(segm, border_labels):
     """the label map and the label table ``imsegm_ray_features_labels2d`` takes; a map that int32 does not hold exactly, or more
     labels than the table has room for: the mask, formed on the host, against the table [1]"""
