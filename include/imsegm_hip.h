@@ -557,6 +557,25 @@ IMSEGM_API int imsegm_boundary_distances(imsegm_ctx *ctx, const int32_t *segm_re
  * segm_ref is uploaded. */
 IMSEGM_API int imsegm_image2d_boundary_distances(imsegm_image2d *img, const int32_t *segm_ref, int32_t *points_out, double *dist_out,
                                                  int capacity, int *n_points_out);
+/* The same on label volumes: host int32, depth x height x width, raster order, thick boundaries only.  Volumes with
+ * depth^2 + height^2 + width^2 > 2^32 - 1 or more than 2^30 voxels are refused with an error before anything is launched.
+ * Replaces skimage.segmentation.find_boundaries(segm, mode='thick') as imsegm/labeling.py:708,710 calls it on a 3-D map: mask_out
+ * is host uint8, 1 where a neighbour along z, y or x inside the volume carries another label. */
+IMSEGM_API int imsegm_boundary_mask3d(imsegm_ctx *ctx, const int32_t *labels, int depth, int height, int width, uint8_t *mask_out);
+/* Replaces the distance map of imsegm/labeling.py:710-711 (find_boundaries and scipy.ndimage.distance_transform_edt of the
+ * complement) on a 3-D map.  dist_out: host float64, distance of every voxel to the nearest mask voxel.  A volume without a mask
+ * voxel gives what scipy gives: the distance to (slice -1, row 0, column 0). */
+IMSEGM_API int imsegm_distance_map3d(imsegm_ctx *ctx, const int32_t *labels, int depth, int height, int width, double *dist_out);
+/* Replaces imsegm/labeling.py:684-716 compute_boundary_distances(segm_ref, segm) on 3-D maps: the voxels of the thick boundary of
+ * segm_ref in raster order as points_out[3 i] = slice, [3 i + 1] = row, [3 i + 2] = column, and dist_out[i] = their distance to the
+ * thick boundary of segm.  Only the points travel back.  `capacity` and *n_points_out as in imsegm_boundary_distances: more points
+ * than `capacity` (entries of dist_out, triples of points_out) is an error that still reports the number. */
+IMSEGM_API int imsegm_boundary_distances3d(imsegm_ctx *ctx, const int32_t *segm_ref, const int32_t *segm, int depth, int height,
+                                           int width, int32_t *points_out, double *dist_out, int capacity, int *n_points_out);
+/* The same against the label map a volume session holds (from imsegm_volume_slic or imsegm_volume_label_cc) as `segm`: only
+ * segm_ref is uploaded. */
+IMSEGM_API int imsegm_volume_boundary_distances(imsegm_image2d *vol, const int32_t *segm_ref, int32_t *points_out, double *dist_out,
+                                                int capacity, int *n_points_out);
 /* Replaces the per-pixel Python loop of imsegm/labeling.py:490-523 compute_labels_overlap_matrix(seg1, seg2) (and the matrix
  * relabel_max_overlap_unique :583 and relabel_max_overlap_merge :664 start from): overlap_out[a * n_labels2 + b] = number of
  * positions i < n with seg1[i] == a and seg2[i] == b; pairs with a negative label (or one beyond its extent) are skipped.

@@ -208,6 +208,10 @@ _SIGNATURES = {
     'imsegm_distance_map': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'imsegm_boundary_distances': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip]),
     'imsegm_image2d_boundary_distances': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ip]),
+    'imsegm_boundary_mask3d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_distance_map3d': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_boundary_distances3d': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _ip]),
+    'imsegm_volume_boundary_distances': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ip]),
     'imsegm_labels_overlap': (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int, C.c_int, _vp]),
     'imsegm_ellipse_ransac': (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                         _vp]),
@@ -1574,6 +1578,15 @@ class Volume3D(Image2D):
                 return edges[:ne.value], centres, present.astype(bool)
             cap = ne.value
 
+    def boundary_distances(self, segm_ref):
+        """``imsegm_volume_boundary_distances``: the thick boundary of ``segm_ref`` (points int32 n x 3, raster order) and its
+        distances (float64 n) to the thick boundary of the resident label map; only ``segm_ref`` is uploaded"""
+        segm_ref = np.ascontiguousarray(segm_ref, dtype=np.int32)
+        if segm_ref.shape != self.shape:
+            raise ValueError('reference map %r does not match the session %r' % (segm_ref.shape, self.shape))
+        lib = load_library()
+        return _boundary_distances(lambda *out: lib.imsegm_volume_boundary_distances(self._h, _ptr(segm_ref), *out), self.shape)
+
     def _unsupported(self, *args, **kwargs):
         raise HipError('not available for volumes')
 
@@ -1951,8 +1964,8 @@ def distance_map(labels, mode, label=0, ctx=None):
 def _boundary_distances(call, shape):
     # room for every pixel: virtual memory only, the pages no point reaches are never touched.  The points go back as a view (the
     # caller converts them to int64 and lets the block go), the distances as a copy of their own so that the block is not kept.
-    capacity = int(shape[0]) * int(shape[1])
-    points, dist, count = np.empty((capacity, 2), dtype=np.int32), np.empty(capacity, dtype=np.float64), C.c_int(0)
+    capacity = int(np.prod(shape, dtype=np.int64))
+    points, dist, count = np.empty((capacity, len(shape)), dtype=np.int32), np.empty(capacity, dtype=np.float64), C.c_int(0)
     _check(call(_ptr(points), _ptr(dist), capacity, C.byref(count)))
     return points[:count.value], dist[:count.value].copy()
 
@@ -1963,6 +1976,40 @@ def boundary_distances(segm_ref, segm, ctx=None):
     lib = load_library()
     return _boundary_distances(lambda *out: lib.imsegm_boundary_distances(ctx._h, _ptr(segm_ref), _ptr(segm), segm.shape[0],
                                                                           segm.shape[1], *out), segm.shape)
+
+
+def boundary3d_fits(shape):
+    """whether the volume kernels take a map of this shape (``edt3d_size_ok`` of csrc/boundary3d.hip): three positive extents,
+    squared distances that fit 32 bits and at most 2^30 voxels; looks at the shape only"""
+    if len(shape) != 3 or min(shape) < 1:
+        return False
+    depth, height, width = (int(extent) for extent in shape)
+    return depth**2 + height**2 + width**2 <= 2**32 - 1 and depth * height * width <= 2**30
+
+
+def boundary_mask3d(labels, ctx=None):
+    """``imsegm_boundary_mask3d`` on a contiguous 3-D int32 label map: uint8 D x H x W, 1 on the thick boundary"""
+    ctx = ctx or default_context()
+    out = np.empty(labels.shape, dtype=np.uint8)
+    _check(load_library().imsegm_boundary_mask3d(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], labels.shape[2], _ptr(out)))
+    return out
+
+
+def distance_map3d(labels, ctx=None):
+    """``imsegm_distance_map3d`` on a contiguous 3-D int32 label map: float64 D x H x W, distance to the nearest voxel of the thick
+    boundary"""
+    ctx = ctx or default_context()
+    out = np.empty(labels.shape, dtype=np.float64)
+    _check(load_library().imsegm_distance_map3d(ctx._h, _ptr(labels), labels.shape[0], labels.shape[1], labels.shape[2], _ptr(out)))
+    return out
+
+
+def boundary_distances3d(segm_ref, segm, ctx=None):
+    """``imsegm_boundary_distances3d`` on two contiguous 3-D int32 label maps of one shape: (points int32 n x 3, dist float64 n)"""
+    ctx = ctx or default_context()
+    lib = load_library()
+    return _boundary_distances(lambda *out: lib.imsegm_boundary_distances3d(ctx._h, _ptr(segm_ref), _ptr(segm), segm.shape[0],
+                                                                            segm.shape[1], segm.shape[2], *out), segm.shape)
 
 
 def labels_overlap(seg1, seg2, n_labels1, n_labels2, ctx=None):

@@ -7,6 +7,7 @@
 //   columns   g(y, x) = |y - y'| to the nearest set pixel (y', x) of the column, or NONE       (one thread per column, two sweeps)
 //   rows      d2(y, x) = min over x' of (x - x')^2 + g(y, x')^2                               (uint32, outward search in LDS tiles)
 //   value     sqrt((double)d2)
+// Volumes run the two passes per slice (launch_edt_slices) and add the depth pass of boundary3d.hip.
 // A uint32 converts to fp64 exactly and the fp64 sqrt of hipcc is the correctly rounded IEEE operation unless a fast-math flag
 // relaxes it: pyimsegm_amd/build.py compiles every file of the library with ONE list of flags (build.FLAGS) that holds no
 // -ffast-math, -Ofast, -fapprox-func or -funsafe-math-optimizations and adds -ffp-contract=off; there are no per-file flags, so
@@ -50,15 +51,18 @@ k_boundary_mask(const int32_t *__restrict__ labels, int H, int W, int mode, int 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// column pass: threads along x (a wave reads and writes 64 neighbouring columns of one row), down and up again
+// column pass: threads along x (a wave reads and writes 64 neighbouring columns of one row), down and up again.
+// A volume is a stack of slices (slice = blockIdx.y, `slice_set` = one flag per slice from k_boundary_mask3d): a slice without a
+// set voxel is left alone, the row pass does not read its g.  An image is one slice and passes no flags.
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
-k_edt_columns(const uint8_t *__restrict__ mask, int H, int W, uint32_t *__restrict__ g)
+k_edt_columns(const uint8_t *__restrict__ mask, int H, int W, const int *__restrict__ slice_set, uint32_t *__restrict__ g)
 {
     const int x = blockIdx.x * 64 + threadIdx.x;
-    if (x >= W) return;
-    const uint8_t *m = mask + x;
-    uint32_t *gx = g + x;
+    if (x >= W || (slice_set && slice_set[blockIdx.y] == 0)) return;
+    const size_t slice = (size_t)blockIdx.y * (size_t)H * (size_t)W;
+    const uint8_t *m = mask + slice + x;
+    uint32_t *gx = g + slice + x;
     uint32_t d = EDT_NONE;
 #pragma unroll 8
     for (int y = 0; y < H; ++y) {
@@ -81,20 +85,30 @@ k_edt_columns(const uint8_t *__restrict__ mask, int H, int W, uint32_t *__restri
 // per pixel, the usual one (superpixel boundaries) a few dozen.  No mask at all (any_set == 0): scipy's distance_transform_edt
 // then answers as if ONE zero sat at row -1, column 0 (seen with scipy 1.7 to 1.15: its feature transform starts from index -1 /
 // 0 and nothing overwrites it), i.e. d2 = (y + 1)^2 + x^2 -- restated here, the test compares against scipy at run time.
+// In a volume (slice = blockIdx.z, `slice_set` given) a slice without a set voxel costs no search: its d2 is NONE, which the depth
+// pass of boundary3d.hip never adds to; the answer for a volume without any set voxel is given there.
 // ---------------------------------------------------------------------------------------------------
 constexpr int EDT_B = 256, EDT_T = 256;
 
 __global__ void __launch_bounds__(EDT_B)
-k_edt_rows(const uint32_t *__restrict__ g, int H, int W, const int *__restrict__ any_set, uint32_t *__restrict__ d2_out,
-           double *__restrict__ dist_out)
+k_edt_rows(const uint32_t *__restrict__ g, int H, int W, const int *__restrict__ any_set, const int *__restrict__ slice_set,
+           uint32_t *__restrict__ d2_out, double *__restrict__ dist_out)
 {
     __shared__ uint32_t s_left[EDT_T + EDT_B], s_right[EDT_T + EDT_B];
     const int t = threadIdx.x, x0 = blockIdx.x * EDT_B, x = x0 + t, y = blockIdx.y;
-    const uint32_t *row = g + (size_t)y * W;
+    const size_t slice = (size_t)blockIdx.z * (size_t)H * (size_t)W;
+    const uint32_t *row = g + slice + (size_t)y * W;
     const bool inside = x < W;
     uint32_t best = EDT_NONE;
     bool done = !inside;
-    if (*any_set == 0) {                               // (uniform over the grid)
+    if (slice_set) {                                   // (uniform over the slice)
+        if (slice_set[blockIdx.z] == 0) {
+            done = true;
+        } else if (inside) {
+            const uint32_t g0 = row[x];
+            if (g0 != EDT_NONE) best = g0 * g0;
+        }
+    } else if (*any_set == 0) {                        // (uniform over the grid)
         best = (uint32_t)(y + 1) * (uint32_t)(y + 1) + (uint32_t)x * (uint32_t)x;
         done = true;
     } else if (inside) {
@@ -127,7 +141,7 @@ k_edt_rows(const uint32_t *__restrict__ g, int H, int W, const int *__restrict__
         __syncthreads();                               // the next round overwrites the windows
     }
     if (inside) {
-        const size_t i = (size_t)y * W + x;
+        const size_t i = slice + (size_t)y * W + x;
         if (d2_out) d2_out[i] = best;
         if (dist_out) dist_out[i] = sqrt((double)best);
     }
@@ -176,6 +190,27 @@ k_compact_gather(const uint8_t *__restrict__ mask, const uint32_t *__restrict__ 
     }
 }
 
+// the same for a volume of slices of HW = H * W voxels: (slice, row, column) triples in raster order
+__global__ void __launch_bounds__(256)
+k_compact_gather3d(const uint8_t *__restrict__ mask, const uint32_t *__restrict__ d2, size_t n, size_t HW, int W,
+                   const uint32_t *__restrict__ offsets, int32_t *__restrict__ points, double *__restrict__ dist)
+{
+    const size_t start = (size_t)blockIdx.x * CP_CHUNK;
+    uint32_t base = offsets[blockIdx.x];
+    for (int it = 0; it < CP_ITEMS; ++it) {
+        const size_t i = start + (size_t)it * 256 + threadIdx.x;
+        const bool set = i < n && mask[i];
+        const uint32_t at = block_stable_slot(set, &base);
+        if (set) {
+            const size_t in_slice = i % HW;
+            points[3 * (size_t)at] = (int32_t)(i / HW);
+            points[3 * (size_t)at + 1] = (int32_t)(in_slice / (size_t)W);
+            points[3 * (size_t)at + 2] = (int32_t)(in_slice % (size_t)W);
+            dist[at] = sqrt((double)d2[i]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------
@@ -213,8 +248,17 @@ int launch_edt(const uint8_t *mask, const int *any_set, int H, int W, uint32_t *
         set_error("boundary: more than 65535 rows");
         return -1;
     }
-    hipLaunchKernelGGL(k_edt_columns, cdiv(W, 64), 64, 0, st, mask, H, W, g);
-    hipLaunchKernelGGL(k_edt_rows, dim3(cdiv(W, EDT_B), H), EDT_B, 0, st, g, H, W, any_set, d2_out, dist_out);
+    hipLaunchKernelGGL(k_edt_columns, cdiv(W, 64), 64, 0, st, mask, H, W, (const int *)nullptr, g);
+    hipLaunchKernelGGL(k_edt_rows, dim3(cdiv(W, EDT_B), H), EDT_B, 0, st, g, H, W, any_set, (const int *)nullptr, d2_out, dist_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_edt_slices(const uint8_t *mask, const int *slice_set, int D, int H, int W, uint32_t *g, uint32_t *d2_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_edt_columns, dim3(cdiv(W, 64), D), 64, 0, st, mask, H, W, slice_set, g);
+    hipLaunchKernelGGL(k_edt_rows, dim3(cdiv(W, EDT_B), H, D), EDT_B, 0, st, g, H, W, (const int *)nullptr, slice_set, d2_out,
+                       (double *)nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -235,6 +279,15 @@ int launch_compact_gather(const uint8_t *mask, const uint32_t *d2, size_t n, int
 {
     const int nb = (int)(compact_count_words(n) - 1);
     hipLaunchKernelGGL(k_compact_gather, nb, 256, 0, st, mask, d2, n, W, offsets, points, dist);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_compact_gather3d(const uint8_t *mask, const uint32_t *d2, size_t n, int H, int W, const uint32_t *offsets, int32_t *points,
+                            double *dist, hipStream_t st)
+{
+    const int nb = (int)(compact_count_words(n) - 1);
+    hipLaunchKernelGGL(k_compact_gather3d, nb, 256, 0, st, mask, d2, n, (size_t)H * (size_t)W, W, offsets, points, dist);
     HIP_TRY(hipGetLastError());
     return 0;
 }

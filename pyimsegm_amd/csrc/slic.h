@@ -273,6 +273,24 @@ size_t compact_count_words(size_t n);
 int launch_compact_count(const uint8_t *mask, size_t n, uint32_t *counts, hipStream_t st);
 int launch_compact_gather(const uint8_t *mask, const uint32_t *d2, size_t n, int W, const uint32_t *offsets, int32_t *points,
                           double *dist, hipStream_t st);
+// the column and the row pass in every slice of a D x H x W mask: d2_out = squared distance to the nearest set voxel of the SAME
+// slice, EDT_NONE all over a slice whose flag slice_set[z] is 0 (such a slice is not searched, its g is neither written nor read)
+int launch_edt_slices(const uint8_t *mask, const int *slice_set, int D, int H, int W, uint32_t *g, uint32_t *d2_out, hipStream_t st);
+// launch_compact_gather for a volume: (slice, row, column) triples in points[3 i .. 3 i + 2]
+int launch_compact_gather3d(const uint8_t *mask, const uint32_t *d2, size_t n, int H, int W, const uint32_t *offsets, int32_t *points,
+                            double *dist, hipStream_t st);
+
+// boundary3d.hip ---------------------------------------------------------------------------------
+// mask[D][H][W] = 1 where a neighbour along z, y or x inside the volume carries another label (find_boundaries(mode='thick') in
+// three dimensions).  flags: D + 1 device ints, cleared here; flags[0] is left at 1 when any voxel is set, flags[1 + z] when one of
+// slice z is
+int launch_boundary_mask3d(const int32_t *labels, int D, int H, int W, uint8_t *mask, int *flags, hipStream_t st);
+// exact Euclidean distance of every voxel to the nearest set voxel of `mask`, squared as uint32 in d2_out; with dist_out also its
+// fp64 root.  flags: what launch_boundary_mask3d left for this mask; g: D * H * W words of scratch, d2_out: as many, another
+// block.  The caller has checked edt3d_size_ok
+int edt3d_size_ok(int D, int H, int W);
+int launch_edt3d(const uint8_t *mask, const int *flags, int D, int H, int W, uint32_t *g, uint32_t *d2_out, double *dist_out,
+                 hipStream_t st);
 
 // median.hip -------------------------------------------------------------------------------------
 // on: a float64 source is read as (value * mul) / div (a Leung-Malik response normalised as descriptors.py:1094)

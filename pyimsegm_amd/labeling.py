@@ -16,6 +16,8 @@
 2-D integer label maps whose values fit int32 go through the device.  There is no CPU fallback for them: without the HIP library
 or a GPU the calls raise.  Inputs the device cannot take (float labels, labels outside int32, maps whose squared diagonal does not
 fit 32 bits) are answered by numpy / scipy statements of the same definitions, as ``assume_bg_on_boundary`` does.
+``compute_boundary_distances`` also takes 3-D integer maps to the device (``csrc/boundary3d.hip``, ``imsegm_boundary_distances3d``)
+when one is present, and to the host statement otherwise (``on``, IMSEGM_BOUNDARY3D_ON).
 """
 import numpy as np
 
@@ -146,6 +148,14 @@ def _device_map(arr):
     """a 2-D label map the distance kernels take: ``_device_labels`` and squared distances that fit 32 bits"""
     arr = np.asarray(arr)
     if arr.ndim != 2 or arr.shape[0] > 65535 or arr.shape[0]**2 + arr.shape[1]**2 > 2**32 - 1:
+        return None
+    return _device_labels(arr)
+
+
+def _device_volume(arr):
+    """a 3-D label map the volume kernels take: ``_device_labels`` and a shape within ``_hip.boundary3d_fits``"""
+    arr = np.asarray(arr)
+    if not _hip.boundary3d_fits(arr.shape):
         return None
     return _device_labels(arr)
 
@@ -368,34 +378,45 @@ def relabel_max_overlap_merge(seg_ref, seg_relabel, keep_bg=False):
     return _keep_negative(lut[seg_relabel].astype(np.int64), seg_relabel)
 
 
-def compute_boundary_distances(segm_ref, segm, _session=None):
+def compute_boundary_distances(segm_ref, segm, _session=None, on=None):
     """ distances between the boundaries of two segmentations (reference ``labeling.py:684-716``, the superpixel measure of
     ``run_eval_superpixels.py:108-131``): the pixels of the thick boundary of ``segm_ref`` in row-major order and their
     Euclidean distance to the thick boundary of ``segm``
 
     2-D integer maps go through the device (``imsegm_boundary_distances``: masks, exact distance transform, stable compaction;
-    only the points come back), anything else -- float labels, maps that are not 2-D -- through numpy and
+    only the points come back).  3-D integer maps that fit int32 and the limits of the volume kernels (``_hip.boundary3d_fits``)
+    go through the device when one is present (``imsegm_boundary_distances3d``: the same with a depth pass; points are ``n x 3``)
+    and through the host statement otherwise; ``on`` or the variable IMSEGM_BOUNDARY3D_ON choose for them.  Anything else -- float
+    labels, labels outside int32, other dimensions, oversized volumes -- takes the host statement: numpy and
     ``scipy.ndimage.distance_transform_edt``, which work in any dimension (points are then ``n x ndim``).
 
     :param ndarray segm_ref: reference segmentation
     :param ndarray segm: input segmentation
-    :param _session: (internal) device session that already holds ``segm`` as its label map
-    :return tuple(ndarray,ndarray): points int64 ``n x 2`` and distances float64 ``n``
+    :param _session: (internal) device session that already holds ``segm`` as its label map (an image or a volume session)
+    :param str on: for 3-D maps None (the device when there is one), 'host' or 'device' (raises without one)
+    :return tuple(ndarray,ndarray): points int64 ``n x ndim`` and distances float64 ``n``
     """
+    if on not in (None, 'host', 'device'):
+        raise ValueError("on is 'host' or 'device', not %r" % (on, ))
     segm_ref = np.asarray(segm_ref)
     shape = tuple(_session.shape) if _session is not None else np.shape(segm)
     if segm_ref.shape != shape:
         raise ImageDimensionError('Ref. segm %r and segm %r should match' % (segm_ref.shape, shape))
-    work_ref = _device_map(segm_ref)
+    volume = segm_ref.ndim == 3
+    work_ref = _device_volume(segm_ref) if volume else _device_map(segm_ref)
     if _session is not None:
         if work_ref is None:
             raise ValueError('the reference segmentation must hold integer labels that fit int32')
         points, dist = _session.boundary_distances(work_ref)
         return points.astype(np.int64), dist
-    work = _device_map(segm)
+    if volume:
+        on_device = _hip.resolve_place(on, 'IMSEGM_BOUNDARY3D_ON', True)[0] == 'device'
+        work = _device_volume(segm) if on_device and work_ref is not None else None
+    else:
+        work = _device_map(segm)
     if work_ref is None or work is None:
         from scipy import ndimage
         on_ref = _thick_boundaries(segm_ref)
         return np.argwhere(on_ref).astype(np.int64), ndimage.distance_transform_edt(~_thick_boundaries(segm))[on_ref].ravel()
-    points, dist = _hip.boundary_distances(work_ref, work)
+    points, dist = (_hip.boundary_distances3d if volume else _hip.boundary_distances)(work_ref, work)
     return points.astype(np.int64), dist
