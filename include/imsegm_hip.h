@@ -902,6 +902,37 @@ IMSEGM_API int imsegm_create_annot_centers(imsegm_ctx *ctx, const void *img, int
                                            int64_t *counts_out, double *centres_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Egg segmentation by marker watershed (experiments_ovary_detect/run_ovary_egg-segmentation.py of the reference: segment_watershed
+ * :239-275, method 'watershed_morph'); csrc/watershed.hip with the hole filling and disc kernels of csrc/morphology.hip, the
+ * distance transform of csrc/boundary.hip and the labelling of csrc/center_annotation.hip.  Integers only: same call, same bytes
+ * as the statements of pyimsegm_amd/egg_segmentation.py.  The flood is defined by rounds (DESIGN.md section 4 "Watershed"), not by
+ * scikit-image's queue.  All arrays are host arrays.  Every entry returns IMSEGM_E_OBJECT_CAPS -- no message, the caller evaluates
+ * on the host -- for what it does not take: more than 65535 rows, 2^31 pixels or more, height^2 + width^2 >= 2^31 (the keys are
+ * int32), labels above IMSEGM_WATERSHED_MAX_LABELS, a radius above IMSEGM_MORPH_MAX_RADIUS; -1 with a message for null arguments,
+ * sizes below 1, negative radii and seeds outside the map.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_WATERSHED_MAX_LABELS 1024       /* labels 1 .. 1024: a label and the claim bit share a word of the flood's state */
+/* morphology.watershed(keys, markers, mask=mask) (:259) as the round flood, 4-connected: mask (uint8, non-zero: inside), keys (int32
+ * per pixel in [-2^31 + 1, 2^31 - 2]; NULL: minus the exact squared distance to the nearest zero of mask, :253 squared), the
+ * non-zero markers inside the mask as n_seeds (pixel index, label) pairs with distinct pixels.  segm_out (int32): the label that
+ * arrives, 0 outside the mask and where none does.  One workgroup floods one component of the mask. */
+IMSEGM_API int imsegm_watershed_markers(imsegm_ctx *ctx, const uint8_t *mask, int height, int width, const int32_t *keys,
+                                        const int32_t *seed_pixels, const int32_t *seed_labels, int n_seeds, int32_t *segm_out);
+/* The clean-up loop :265-274: for every label 1 .. max_label in ascending order segm == label closed with disk(radius_close)
+ * (binary_closing: dilation with clear pixels outside the image, erosion with set ones), its holes filled (binary_fill_holes), opened
+ * with disk(radius_open) (binary_opening: erosion, dilation) and painted over the earlier labels into clean_out (int32).  A radius of
+ * 0 leaves its step out.  Every stage is one launch over all labels, each inside the plane of its bounding box padded by
+ * radius_close + 1; planes that together exceed the scratch of the call (boxes that overlap heavily) give IMSEGM_E_OBJECT_CAPS. */
+IMSEGM_API int imsegm_watershed_post_morph(imsegm_ctx *ctx, const int32_t *segm, int height, int width, int max_label, int radius_close,
+                                           int radius_open, int32_t *clean_out);
+/* segment_watershed :249-275 in one call: seg (uint8, the bytes of seg > 0), binary_fill_holes (:250), the squared
+ * distance_transform_edt (:253), markers[row, col] = i + 1 for centre i of centres (int32 [2 n_centres], rows and columns inside the
+ * map; a later centre replaces an earlier one on the same pixel, :255-256), the flood (:259) and, with post_morph, the clean-up with
+ * radii[0], radii[1] (NULL: 5 and 15, the reference's).  One upload, one chain of launches, one download. */
+IMSEGM_API int imsegm_watershed(imsegm_ctx *ctx, const uint8_t *seg, int height, int width, const int32_t *centres, int n_centres,
+                                int post_morph, const int32_t *radii, int32_t *segm_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the
  * nearest exactly-coloured pixel (imsegm/annotation.py, the module behind handling_annotations/run_image_color_quantization.py,
  * run_image_convert_label_color.py, run_overlap_images_segms.py and run_segm_annot_inpaint.py); csrc/annotation.hip.  Integers

@@ -236,6 +236,9 @@ _SIGNATURES = {
     'imsegm_center_levels': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     'imsegm_debug_center_distances': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     'imsegm_create_annot_centers': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _ip, _vp, _vp]),
+    'imsegm_watershed_markers': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    'imsegm_watershed_post_morph': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_watershed': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
@@ -2298,6 +2301,76 @@ def create_annot_centers(img, sel_radius, min_size, levels, ctx=None):
     _check(status)
     n = n_labels.value
     return out, counts[1:n + 1], centres[1:n + 1]
+
+
+#: ``IMSEGM_WATERSHED_MAX_LABELS``
+WATERSHED_MAX_LABELS = 1024
+
+
+def _mask_bytes(mask):
+    if mask.ndim != 2 or mask.size == 0:
+        raise ValueError('the mask must be a non-empty 2-D array')
+    return np.ascontiguousarray(mask != 0).view(np.uint8)
+
+
+def watershed_markers(mask, seed_pixels, seed_labels, keys=None, ctx=None):
+    """``imsegm_watershed_markers`` on a 2-D mask, the (pixel index, label) pairs of its markers (distinct pixels) and int32 keys of
+    the mask's shape (None: minus the squared distances to the background): the flooded map int32 H x W, or None for a request
+    outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    mask = _mask_bytes(mask)
+    seed_pixels = np.ascontiguousarray(seed_pixels, dtype=np.int32).ravel()
+    seed_labels = np.ascontiguousarray(seed_labels, dtype=np.int32).ravel()
+    if len(seed_pixels) != len(seed_labels):
+        raise ValueError('one label per seed')
+    if keys is not None:
+        keys = np.ascontiguousarray(keys, dtype=np.int32)
+        if keys.shape != mask.shape:
+            raise ValueError('mask and keys differ in shape')
+    out = np.empty(mask.shape, dtype=np.int32)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_watershed_markers(ctx._h, _ptr(mask), mask.shape[0], mask.shape[1], _ptr(keys), _ptr(seed_pixels),
+                                                     _ptr(seed_labels), len(seed_pixels), _ptr(out))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out
+
+
+def watershed_post_morph(segm, radius_close, radius_open, ctx=None):
+    """``imsegm_watershed_post_morph`` on a 2-D integer label map: the cleaned map int32 H x W, or None for a request outside the
+    caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    if segm.ndim != 2 or segm.size == 0:
+        raise ValueError('the label map must be a non-empty 2-D array')
+    top = int(segm.max())
+    if top > WATERSHED_MAX_LABELS:
+        return None
+    segm = np.ascontiguousarray(segm, dtype=np.int32)
+    out = np.empty(segm.shape, dtype=np.int32)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_watershed_post_morph(ctx._h, _ptr(segm), segm.shape[0], segm.shape[1], max(top, 0), int(radius_close),
+                                                        int(radius_open), _ptr(out))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out
+
+
+def watershed(seg_binary, centres, post_morph, radii=None, ctx=None):
+    """``imsegm_watershed`` on the 2-D boolean map ``seg > 0`` and the centres as int32 (row, column) rows inside the map, centre
+    ``i`` for label ``i + 1``: the segmentation int32 H x W, or None for a request outside the caps (``IMSEGM_E_OBJECT_CAPS``) --
+    no error"""
+    seg = _mask_bytes(seg_binary)
+    centres = np.ascontiguousarray(centres, dtype=np.int32).reshape(-1, 2)
+    n = len(centres)
+    radii = None if radii is None else np.ascontiguousarray(radii, dtype=np.int32)
+    out = np.empty(seg.shape, dtype=np.int32)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_watershed(ctx._h, _ptr(seg), seg.shape[0], seg.shape[1], _ptr(centres), n, int(bool(post_morph)),
+                                             _ptr(radii), _ptr(out))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out
 
 
 #: ``IMSEGM_DBSCAN_MAX_POINTS`` / ``IMSEGM_DBSCAN_MAX_SETS`` / ``IMSEGM_DBSCAN_MAX_TOTAL``

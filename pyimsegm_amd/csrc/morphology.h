@@ -27,8 +27,15 @@ struct MorphLabels {
     const int32_t *labels = nullptr;
     const int32_t *radius = nullptr;
     int level = 0, max_label = 0;
+    const int32_t *boxes = nullptr;                    // (launch_disc_morph_boxed only)
 };
 int launch_disc_morph_labelled(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, const MorphLabels &ml, hipStream_t st);
+// launch_disc_morph for n_boxes planes at once: plane b = 1 .. n_boxes has the height, width and pixel offset in `in` and `out` of
+// row b of `boxes` (MORPH_BOX_WORDS words per row: first row, first column, height, width, offset; row 0 is not used; a height or
+// width of 0: no plane).  H, W: no plane is larger.  One launch, plane = blockIdx.z + 1.
+constexpr int MORPH_BOX_WORDS = 8;
+int launch_disc_morph_boxed(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, const int32_t *boxes, int n_boxes,
+                            hipStream_t st);
 // rays of P positions on seg_bg with edge 'up' into rays_bg and on seg_fg with edge 'down' into rays_fg (P x A float32 each, either
 // may be null), one launch
 int launch_boundary_rays(const uint8_t *seg_bg, const uint8_t *seg_fg, int H, int W, const int32_t *positions, int P, const float *grad,

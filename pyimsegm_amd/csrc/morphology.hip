@@ -81,11 +81,23 @@ template <int TARGET, bool LABELLED> __device__ __forceinline__ int morph_step(i
     return min(d + 1, cap);
 }
 
-template <int TARGET, bool LABELLED>
+//
+// BOXED: the plain tiles for many small planes at once (the clean-up of watershed.hip): plane blockIdx.z + 1 has the height, width
+// and pixel offset of its row in ml.boxes (MORPH_BOX_WORDS words per row: first row, first column, height, width, offset) and lies
+// at that offset in `in` and `out`; the grid covers the largest plane and a workgroup outside its own plane leaves at once.
+template <int TARGET, bool LABELLED, bool BOXED = false>
 __global__ void __launch_bounds__(256) k_disc_morph(const uint8_t *__restrict__ in, int H, int W, int r, uint8_t *__restrict__ out,
                                                     MorphLabels ml)
 {
     extern __shared__ uint8_t morph_lds[];
+    if (BOXED) {
+        const int32_t *box = ml.boxes + (size_t)(blockIdx.z + 1) * MORPH_BOX_WORDS;
+        H = min(box[2], H);
+        W = min(box[3], W);
+        if ((int)blockIdx.x * MO_TILE >= W || (int)blockIdx.y * MO_TILE >= H) return;       // (uniform over the workgroup)
+        in += box[4];
+        out += box[4];
+    }
     const int LW = MO_TILE + 2 * r;
     uint8_t *hit = morph_lds;                          // [LW][LW]
     uint8_t *run = morph_lds + LW * LW;                // [MO_TILE][LW]
@@ -210,6 +222,26 @@ int launch_fill_holes_split(const int32_t *segm, int H, int W, int32_t *parent, 
     hipLaunchKernelGGL(k_holes_merge, rows, 256, 0, st, segm, parent, W);
     hipLaunchKernelGGL(k_holes_touch, cdiv(2L * W + 2L * H, 256), 256, 0, st, segm, parent, H, W, touches);
     hipLaunchKernelGGL(k_holes_write, cdiv(n, 256), 256, 0, st, segm, parent, touches, n, seg_bg, seg_fg);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_disc_morph_boxed(const uint8_t *in, int H, int W, int r, int dilate, uint8_t *out, const int32_t *boxes, int n_boxes,
+                            hipStream_t st)
+{
+    if (r < 1 || r > MORPH_MAX_RADIUS || n_boxes < 1 || n_boxes > 65535) {
+        set_error("disc morphology: the radius must lie in [1, IMSEGM_MORPH_MAX_RADIUS] and the planes number 1 .. 65535");
+        return -1;
+    }
+    const int LW = MO_TILE + 2 * r;
+    const size_t lds = (size_t)LW * LW + (size_t)MO_TILE * LW;
+    const dim3 grid(cdiv(W, MO_TILE), cdiv(H, MO_TILE), n_boxes);
+    MorphLabels ml;
+    ml.boxes = boxes;
+    if (dilate)
+        hipLaunchKernelGGL((k_disc_morph<1, false, true>), grid, 256, lds, st, in, H, W, r, out, ml);
+    else
+        hipLaunchKernelGGL((k_disc_morph<0, false, true>), grid, 256, lds, st, in, H, W, r, out, ml);
     HIP_TRY(hipGetLastError());
     return 0;
 }
