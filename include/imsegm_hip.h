@@ -933,6 +933,34 @@ IMSEGM_API int imsegm_watershed(imsegm_ctx *ctx, const uint8_t *seg, int height,
                                 int post_morph, const int32_t *radii, int32_t *segm_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Orientation of egg cut-outs (experiments_ovary_detect/run_egg_swap_orientation.py of the reference: compute_mean_image :92-98,
+ * condition_swap_correl :77-80, condition_swap_density :65-74, perform_orientation_swap :39-62, main :101-128);
+ * csrc/egg_orientation.hip.  Integers only: same call, same bytes as the statements of pyimsegm_amd/egg_orientation.py
+ * (stack_median2_host, orientation_sums_host; DESIGN.md section 4 "Egg orientation").  A stack is n_images uint8 images
+ * [height, width, channels], C-contiguous, already cropped to one size; `channel` is the one both tests read (the reference's
+ * IMAGE_CHANNEL = 0).  All arrays are host arrays.  Both entries return IMSEGM_E_OBJECT_CAPS -- no message, the caller evaluates on
+ * the host -- for more than IMSEGM_ORIENT_MAX_IMAGES images (the counters of the median are 16 bits wide), more than 4 channels,
+ * more than 2^30 pixels per image or a stack above 2^31 - 1 bytes; -1 with a message for null arguments, sizes below 1, a channel
+ * outside the image, an unknown mode and a given template above 510.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_ORIENT_MAX_IMAGES 65535
+#define IMSEGM_ORIENT_SUM_WORDS 9              /* A = sum a, min a, max a, P, Pf, cnt, S, L, R */
+/* template2_out (uint16 [height, width]) = s[(n - 1) / 2] + s[n / 2] of the n channel values of every pixel sorted: exactly
+ * 2 * np.median(stack[..., channel], axis=0) (:97).  One lane per pixel, radix selection in two passes of 16 bins. */
+IMSEGM_API int imsegm_stack_median_u8(imsegm_ctx *ctx, const uint8_t *stack, int n_images, int height, int width, int channels,
+                                      int channel, uint16_t *template2_out);
+/* main :114-128 in one call.  template2_in: twice the template as uint16 in 0 .. 510, or NULL for the median of the stack; it is
+ * written to template2_out either way.  sums_out (int64 [n_images, 9]), with a the channel of an image, t the template2 and m = min a:
+ * A = sum a, min a, max a, P = sum a t, Pf = sum a[h - 1 - r, w - 1 - c] t[r, c], cnt = #{a > m}, S = sum of the a > m, and with
+ * g = [a cnt > S] and part = width / 3: L = sum g[:, :part], R = sum g[:, width - part:] (part = 0: the sum of all of g, as the
+ * reference's img[:, -0:]).  flags_out (uint8 [n_images]): mode 0 (correlation) = min a != max a and min t != max t and P < Pf;
+ * mode 1 (density) = L > R.  turned_out (the size of stack; may be stack itself): every image, as img[::-1, ::-1, :] where its
+ * flag is set.  The stack goes up once; the template, the sums, the flags and only the turned images come down. */
+IMSEGM_API int imsegm_orient_stack(imsegm_ctx *ctx, const uint8_t *stack, int n_images, int height, int width, int channels, int channel,
+                                   int mode, const uint16_t *template2_in, uint16_t *template2_out, uint8_t *flags_out,
+                                   int64_t *sums_out, uint8_t *turned_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the
  * nearest exactly-coloured pixel (imsegm/annotation.py, the module behind handling_annotations/run_image_color_quantization.py,
  * run_image_convert_label_color.py, run_overlap_images_segms.py and run_segm_annot_inpaint.py); csrc/annotation.hip.  Integers

@@ -239,6 +239,8 @@ _SIGNATURES = {
     'imsegm_watershed_markers': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     'imsegm_watershed_post_morph': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'imsegm_watershed': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'imsegm_stack_median_u8': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    'imsegm_orient_stack': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
@@ -2371,6 +2373,59 @@ def watershed(seg_binary, centres, post_morph, radii=None, ctx=None):
         return None
     _check(status)
     return out
+
+
+#: ``IMSEGM_ORIENT_MAX_IMAGES`` / ``IMSEGM_ORIENT_SUM_WORDS``
+ORIENT_MAX_IMAGES, ORIENT_SUM_WORDS = 65535, 9
+#: modes of ``imsegm_orient_stack``
+ORIENT_MODES = {'cc': 0, 'density': 1}
+
+
+def _orient_stack(stack, channel):
+    if stack.dtype != np.uint8 or stack.ndim != 4 or stack.size == 0 or not stack.flags.c_contiguous:
+        raise ValueError('the stack must be a non-empty C-contiguous uint8 array [N, h, w, C]')
+    if not 0 <= int(channel) < stack.shape[3]:
+        raise ValueError('channel %r of %d' % (channel, stack.shape[3]))
+    return stack
+
+
+def stack_median(stack, channel=0, ctx=None):
+    """``imsegm_stack_median_u8`` on a C-contiguous uint8 stack [N, h, w, C]: twice the per-pixel median of ``stack[..., channel]``
+    over the N images as uint16 [h, w], or None for a stack outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    stack = _orient_stack(stack, channel)
+    n, h, w, c = stack.shape
+    out = np.empty((h, w), dtype=np.uint16)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_stack_median_u8(ctx._h, _ptr(stack), n, h, w, c, int(channel), _ptr(out))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out
+
+
+def orient_stack(stack, channel=0, mode='cc', template2=None, ctx=None, in_place=False):
+    """``imsegm_orient_stack`` on a C-contiguous uint8 stack [N, h, w, C]; ``mode`` 'cc' or 'density'; ``template2``: twice the
+    template as integers 0 .. 510 [h, w], or None for the median of the stack.  Returns (template2 uint16 [h, w], flags bool [N],
+    sums int64 [N, 9], the stack with the flagged images turned by 180 degrees -- a new array, or ``stack`` itself with
+    ``in_place``), or None for a stack outside the caps
+    (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    stack = _orient_stack(stack, channel)
+    n, h, w, c = stack.shape
+    if template2 is not None:
+        template2 = np.ascontiguousarray(template2, dtype=np.uint16)
+        if template2.shape != (h, w):
+            raise ValueError('template2 %r and the images %r differ in size' % (template2.shape, (h, w)))
+    out = np.empty((h, w), dtype=np.uint16)
+    flags = np.empty(n, dtype=np.uint8)
+    sums = np.empty((n, ORIENT_SUM_WORDS), dtype=np.int64)
+    turned = stack if in_place else np.empty_like(stack)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_orient_stack(ctx._h, _ptr(stack), n, h, w, c, int(channel), ORIENT_MODES[mode], _ptr(template2),
+                                                _ptr(out), _ptr(flags), _ptr(sums), _ptr(turned))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out, flags != 0, sums, turned
 
 
 #: ``IMSEGM_DBSCAN_MAX_POINTS`` / ``IMSEGM_DBSCAN_MAX_SETS`` / ``IMSEGM_DBSCAN_MAX_TOTAL``
