@@ -961,6 +961,52 @@ IMSEGM_API int imsegm_orient_stack(imsegm_ctx *ctx, const uint8_t *stack, int n_
                                    int64_t *sums_out, uint8_t *turned_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cut-outs of ellipse-annotated eggs scaled to the normal size of their stage (experiments_ovary_detect/run_ellipse_cut_scale.py
+ * of the reference: extract_ellipse_object :46-72, whose output run_egg_swap_orientation.py reads); csrc/resize.hip, the ellipse
+ * masks of csrc/cut_objects.hip and the inside test of csrc/ellipse_place.h.  Same call, same bytes as the statements of
+ * pyimsegm_amd/ellipse_cut_scale.py (resize_image_host, export_image_array, extract_ellipse_objects_host; DESIGN.md section 4 "Cut
+ * and scale").  All arrays are host arrays.  Both entries return IMSEGM_E_OBJECT_CAPS -- no message, the caller evaluates on the
+ * host -- for more than IMSEGM_RESIZE_MAX_CROPS crops, more than IMSEGM_CUT_OBJECTS_MAX_CHANNELS channels, a blur radius above
+ * IMSEGM_RESIZE_MAX_RADIUS, a side of a crop or of the output above 32768, more than 2^30 bytes of crops or more than 2^28 output
+ * values; -1 with a message for null arguments, sizes below 1, negative radii and what a hook refuses.
+ * ------------------------------------------------------------------------------------------- */
+#define IMSEGM_RESIZE_MAX_RADIUS 64            /* a 16 x 64 pixel tile of 4 channels with a halo of 64 rows on both sides: 36 KiB of LDS */
+#define IMSEGM_RESIZE_MAX_CROPS 1024           /* crops of one call (IMSEGM_CUT_OBJECTS_MAX_LABELS: the chain cuts what it resizes) */
+/* skimage.transform.resize(crop, (out_h, out_w)) of scikit-image 0.18.3 (run_ellipse_cut_scale.py :69; order 1, mode 'reflect',
+ * anti-aliasing, clip) for n uint8 crops of unequal sizes, and the array half of export_image (imsegm/utilities/data_io.py :459-462,
+ * called at :72).  Crop k is sizes[2 k] x sizes[2 k + 1] x channels bytes at packed + offsets[k] (offsets: n + 1 running sums).
+ * The blur is scipy.ndimage.gaussian_filter on the uint8 crop, down the rows and then along them with a uint8 intermediate, each
+ * byte (uint8)tmp with tmp = x[0] w[0], then tmp += (x[-j] + x[+j]) w[j] for j = radius .. 1 in fp64, mirrored edges.  radii[2 k + a]
+ * and weights[(2 k + a) * (IMSEGM_RESIZE_MAX_RADIUS + 1) + j] (the weight at distance j) for axis a of crop k are COMPUTED BY THE
+ * CALLER exactly as scipy does -- exp(-0.5 / sigma^2 * x^2) over arange(-r, r + 1) divided by its sum, r = int(4 sigma + 0.5),
+ * sigma = max(0, (in / out - 1) / 2); an axis that is not shrunk has radius 0 and weight 1 -- so that no kernel evaluates exp.
+ * Then byte * (1. / 255), the bilinear lookup at r = (H / h)(y + 0.5) - 0.5, c = (W / w)(x + 0.5) - 0.5 (a 1 x 1 output: the centre)
+ * with mirrored neighbours, clipped to the range of the blurred crop -> out (float64 [n, out_h, out_w, channels]; may be NULL when
+ * out_u8 is given).  out_u8 (may be NULL): (uint8)(v / max * 255) with the maximum of every image, (uint8)v for an image of
+ * zeros. */
+IMSEGM_API int imsegm_resize_crops(imsegm_ctx *ctx, const uint8_t *packed, const int64_t *offsets, const int32_t *sizes, int n,
+                                   int channels, int out_h, int out_w, const int32_t *radii, const double *weights, double *out,
+                                   uint8_t *out_u8);
+/* The weights of the blur for n crops of sizes[2 k] x sizes[2 k + 1] and the output size, as above, supplied by the caller of
+ * imsegm_ellipse_cut_scale because the crop sizes only exist in the middle of that call: to fill radii_out (n x 2) and weights_out
+ * (n x 2 x (IMSEGM_RESIZE_MAX_RADIUS + 1), zeroed).  A radius above the cap in radii_out ends the call with IMSEGM_E_OBJECT_CAPS, a
+ * return value other than 0 with -1. */
+typedef int (*imsegm_blur_taps_fn)(void *user, int n, const int32_t *sizes, int out_h, int out_w, int32_t *radii_out,
+                                   double *weights_out);
+/* The loop of extract_ellipse_object :62-72 over the n ellipses of one image (uint8, height x width x channels interleaved, uploaded
+ * once), the ellipses in the geom / sincos form of imsegm_ellipse_place.  Per ellipse: the mask of add_overlap_ellipse(zeros, ell, 1)
+ * (:63) -- never rasterised: its moments come from the ellipse expression inside the clipped box, so ellipses may overlap --, the
+ * `geometry` hook of imsegm_cut_objects, cut_object(img, mask, 0, use_mask=True) (:66; the mask is an int64 map, so a canvas pixel
+ * from outside the turned frame keeps its 0 instead of bg_color), the resize (:69) with the weights of `taps`, and the export (:72).
+ * The crops stay on the device between the cut and the resize; the stack comes down by one copy.  out / out_u8 as in
+ * imsegm_resize_crops.  *first_empty_out = -1, or the first ellipse whose turned mask has no pixel: then nothing else is written.
+ * An ellipse without a pixel at all is the hook's to refuse (count 0).  Ellipses are checked as in imsegm_ellipse_place. */
+IMSEGM_API int imsegm_ellipse_cut_scale(imsegm_ctx *ctx, const uint8_t *image, int height, int width, int channels, int n,
+                                        const int32_t *geom, const double *sincos, const uint8_t *bg_color, int out_h, int out_w,
+                                        imsegm_cut_geometry_fn geometry, imsegm_blur_taps_fn taps, void *user, double *out,
+                                        uint8_t *out_u8, int *first_empty_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Annotation colours: RGB annotation images <-> integer label maps, colour counts and the quantisation of a painted image to the
  * nearest exactly-coloured pixel (imsegm/annotation.py, the module behind handling_annotations/run_image_color_quantization.py,
  * run_image_convert_label_color.py, run_overlap_images_segms.py and run_segm_annot_inpaint.py); csrc/annotation.hip.  Integers

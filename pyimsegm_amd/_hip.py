@@ -241,6 +241,9 @@ _SIGNATURES = {
     'imsegm_watershed': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     'imsegm_stack_median_u8': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     'imsegm_orient_stack': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'imsegm_resize_crops': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    'imsegm_ellipse_cut_scale': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp,
+                                           _vp, _vp, _ip]),
     'imsegm_annot_color_hist': (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _ip, _vp, _vp]),
     'imsegm_annot_nearest_valid': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     'imsegm_annot_quantize_nearest_pixel': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
@@ -2167,6 +2170,27 @@ CUT_GEOMETRY_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, 
                               C.POINTER(C.c_int32))
 
 
+def _geometry_callback(geometry, raised):
+    """``geometry(moments_row, (H, W), allow_rotate)`` as an ``imsegm_cut_geometry_fn``; what it raises is kept in ``raised``"""
+
+    def hook(user, n_labels, rotate, hook_height, hook_width, moments, geometry_out, frames_out):
+        try:
+            for k in range(n_labels):
+                g = geometry([int(moments[10 * k + i]) for i in range(10)], (hook_height, hook_width), bool(rotate))
+                row = (g['shift'][0], g['shift'][1], g['matrix'][0, 0], g['matrix'][0, 1], g['matrix'][1, 0], g['matrix'][1, 1],
+                       g['offset'][0], g['offset'][1])
+                for i, value in enumerate(row):
+                    geometry_out[8 * k + i] = float(value)
+                for i, value in enumerate(tuple(g['canvas']) + tuple(g['window'])):
+                    frames_out[6 * k + i] = int(value)
+            return 0
+        except BaseException as ex:                    # (an exception must not cross the C frames)
+            raised.append(ex)
+            return 1
+
+    return CUT_GEOMETRY_FN(hook)
+
+
 def cut_objects(image, segm, labels, padding, use_mask, bg_color, allow_rotate, geometry, ctx=None):
     """``imsegm_cut_objects``: the crops of all ``labels`` (strictly ascending int32) of the C-contiguous int32 map ``segm`` [H, W] out
     of the C-contiguous uint8 ``image`` [H, W, C] in one call: (crops -- a list of uint8 arrays [h, w, C] --, moments int64 [n, 10],
@@ -2184,26 +2208,10 @@ def cut_objects(image, segm, labels, padding, use_mask, bg_color, allow_rotate, 
     bg = np.zeros(max(channels, 1), dtype=np.uint8)
     bg[...] = bg_color
     raised = []
-
-    def hook(user, n_labels, rotate, hook_height, hook_width, moments, geometry_out, frames_out):
-        try:
-            for k in range(n_labels):
-                g = geometry([int(moments[10 * k + i]) for i in range(10)], (hook_height, hook_width), bool(rotate))
-                row = (g['shift'][0], g['shift'][1], g['matrix'][0, 0], g['matrix'][0, 1], g['matrix'][1, 0], g['matrix'][1, 1],
-                       g['offset'][0], g['offset'][1])
-                for i, value in enumerate(row):
-                    geometry_out[8 * k + i] = float(value)
-                for i, value in enumerate(tuple(g['canvas']) + tuple(g['window'])):
-                    frames_out[6 * k + i] = int(value)
-            return 0
-        except BaseException as ex:                    # (an exception must not cross the C frames)
-            raised.append(ex)
-            return 1
-
     moments, boxes = np.zeros((n, 10), dtype=np.int64), np.zeros((n, 4), dtype=np.int32)
     offsets, packed, first_empty = np.zeros(n + 1, dtype=np.int64), _vp(), C.c_int(-1)
     ctx = ctx or default_context()
-    callback = CUT_GEOMETRY_FN(hook)                   # (alive until the call returns)
+    callback = _geometry_callback(geometry, raised)    # (alive until the call returns)
     status = load_library().imsegm_cut_objects(ctx._h, _ptr(image), _ptr(segm), height, width, channels, _ptr(labels), n, int(padding),
                                                int(bool(use_mask)), _ptr(bg), int(bool(allow_rotate)), C.cast(callback, _vp),
                                                None, _ptr(moments), _ptr(boxes), _ptr(offsets), C.byref(packed), C.byref(first_empty))
@@ -2221,6 +2229,95 @@ def cut_objects(image, segm, labels, padding, use_mask, bg_color, allow_rotate, 
             shape = (int(boxes[k, 2] - boxes[k, 0]), int(boxes[k, 3] - boxes[k, 1]), channels)
             crops.append(flat[offsets[k]:offsets[k + 1]].reshape(shape).copy())
     return crops, moments, boxes
+
+
+#: ``IMSEGM_RESIZE_MAX_RADIUS``: the largest blur radius of csrc/resize.hip (a shrink by a factor of about 33)
+RESIZE_MAX_RADIUS = 64
+#: ``imsegm_blur_taps_fn``
+BLUR_TAPS_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double))
+
+
+def _resize_outputs(n, out_shape, channels, want_u8):
+    h, w = int(out_shape[0]), int(out_shape[1])
+    out = None if want_u8 else np.empty((n, h, w, channels), dtype=np.float64)
+    out_u8 = np.empty((n, h, w, channels), dtype=np.uint8) if want_u8 else None
+    return h, w, out, out_u8
+
+
+def resize_crops(crops, out_shape, radii, weights, want_u8=False, ctx=None):
+    """``imsegm_resize_crops``: the C-contiguous uint8 ``crops`` [H_i, W_i, C] (a list, one channel count) resized to ``out_shape``
+    with the blur taps ``radii`` int32 [n, 2] / ``weights`` float64 [n, 2, RESIZE_MAX_RADIUS + 1] of
+    ``ellipse_cut_scale.blur_taps``: (float64 [n, h, w, C], None), or with ``want_u8`` (None, the exported uint8 stack); None for
+    a request outside the caps (``IMSEGM_E_OBJECT_CAPS``) -- no error"""
+    n = len(crops)
+    channels = crops[0].shape[2]
+    for crop in crops:
+        if crop.dtype != np.uint8 or crop.ndim != 3 or crop.shape[2] != channels or crop.size == 0 or not crop.flags.c_contiguous:
+            raise ValueError('the crops must be non-empty C-contiguous uint8 arrays [H, W, C] of one channel count')
+    sizes = np.array([crop.shape[:2] for crop in crops], dtype=np.int32)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([crop.size for crop in crops], out=offsets[1:])
+    packed = np.concatenate([crop.ravel() for crop in crops])
+    radii = np.ascontiguousarray(radii, dtype=np.int32)
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    if radii.shape != (n, 2) or weights.shape != (n, 2, RESIZE_MAX_RADIUS + 1):
+        raise ValueError('radii [n, 2] and weights [n, 2, %d] are expected' % (RESIZE_MAX_RADIUS + 1))
+    h, w, out, out_u8 = _resize_outputs(n, out_shape, channels, want_u8)
+    ctx = ctx or default_context()
+    status = load_library().imsegm_resize_crops(ctx._h, _ptr(packed), _ptr(offsets), _ptr(sizes), n, channels, h, w, _ptr(radii),
+                                                _ptr(weights), _ptr(out), _ptr(out_u8))
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    return out, out_u8
+
+
+def ellipse_cut_scale(image, geom, sincos, bg_color, out_shape, geometry, taps, want_u8=True, ctx=None):
+    """``imsegm_ellipse_cut_scale``: every ellipse ``geom`` int32 [n, 8] / ``sincos`` float64 [n, 2] (``ellipse_fitting.
+    ellipse_geometry``) cut out of the C-contiguous uint8 ``image`` [H, W, C] under its own mask, resized to ``out_shape`` and, with
+    ``want_u8``, exported: uint8 (or float64) [n, h, w, C].  ``geometry`` as in :func:`cut_objects`; ``taps(sizes)`` returns the
+    (radii, weights) of ``imsegm_resize_crops`` for crops of ``sizes`` [n, 2], or None for a radius above the cap.  An ellipse
+    without a pixel raises ``IndexError``.  A request outside the caps (``IMSEGM_E_OBJECT_CAPS``) gives None -- no error."""
+    if image.dtype != np.uint8 or image.ndim != 3 or not image.flags.c_contiguous or image.size == 0:
+        raise ValueError('the image must be a non-empty C-contiguous uint8 array [H, W, C]')
+    height, width, channels = image.shape
+    geom = np.ascontiguousarray(geom, dtype=np.int32).reshape(-1, 8)
+    sincos = np.ascontiguousarray(sincos, dtype=np.float64).reshape(-1, 2)
+    if len(geom) != len(sincos):
+        raise ValueError('one (sin, cos) pair per ellipse')
+    n = len(geom)
+    bg = np.zeros(max(channels, 1), dtype=np.uint8)
+    bg[...] = bg_color
+    raised = []
+
+    def taps_hook(user, n_crops, sizes, out_h, out_w, radii_out, weights_out):
+        try:
+            got = taps([(sizes[2 * k], sizes[2 * k + 1]) for k in range(n_crops)])
+            if got is None:
+                radii_out[0] = RESIZE_MAX_RADIUS + 1           # (the entry answers IMSEGM_E_OBJECT_CAPS)
+                return 0
+            C.memmove(radii_out, _ptr(np.ascontiguousarray(got[0], dtype=np.int32)), n_crops * 2 * 4)
+            C.memmove(weights_out, _ptr(np.ascontiguousarray(got[1], dtype=np.float64)), n_crops * 2 * (RESIZE_MAX_RADIUS + 1) * 8)
+            return 0
+        except BaseException as ex:                    # (an exception must not cross the C frames)
+            raised.append(ex)
+            return 1
+
+    h, w, out, out_u8 = _resize_outputs(n, out_shape, channels, want_u8)
+    first_empty = C.c_int(-1)
+    ctx = ctx or default_context()
+    geometry_cb, taps_cb = _geometry_callback(geometry, raised), BLUR_TAPS_FN(taps_hook)       # (alive until the call returns)
+    status = load_library().imsegm_ellipse_cut_scale(ctx._h, _ptr(image), height, width, channels, n, _ptr(geom), _ptr(sincos), _ptr(bg),
+                                                     h, w, C.cast(geometry_cb, _vp), C.cast(taps_cb, _vp), None, _ptr(out),
+                                                     _ptr(out_u8), C.byref(first_empty))
+    if raised:
+        raise raised[0]
+    if status == IMSEGM_E_OBJECT_CAPS:
+        return None
+    _check(status)
+    if first_empty.value >= 0:
+        raise IndexError('list index out of range')         # regionprops(...)[0] of the reference on the turned mask
+    return out_u8 if want_u8 else out
 
 
 #: ``IMSEGM_CENTER_ANNOT_MAX_LABELS`` / ``IMSEGM_CENTER_ANNOT_MAX_LEVELS``

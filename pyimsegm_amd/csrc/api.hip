@@ -204,6 +204,7 @@ void imsegm_ctx_destroy(imsegm_ctx *ctx)
     for (auto e : ctx->pool) (void)hipEventDestroy(e);
     ctx->gc_buf.release();
     ctx->aux_buf.release();
+    ctx->resize_buf.release();
     ctx->fit_table.release();
     ctx->fit_work.release();
     if (ctx->pinned_ev) (void)hipEventDestroy(ctx->pinned_ev);

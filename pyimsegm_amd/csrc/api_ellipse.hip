@@ -14,9 +14,8 @@ static_assert(ELLIPSE_PLACE_LABELS == IMSEGM_ELLIPSE_PLACE_LABELS, "LDS budget o
 
 namespace imsegm {
 
-// the arguments both ellipse_place calls share; *max_box_rows: the tallest clipped box (0: no ellipse has a pixel)
-static int check_ellipses(const char *who, const int32_t *segm, int H, int W, int n, const int32_t *geom, const double *sincos,
-                          int *max_box_rows)
+// the arguments the calls that walk ellipse boxes share (ellipse_place.h)
+int check_ellipses(const char *who, const void *segm, int H, int W, int n, const int32_t *geom, const double *sincos, int *max_box_rows)
 {
     const std::string name(who);
     if (H < 1 || W < 1 || H > ELLIPSE_PLACE_MAX_COORD || W > ELLIPSE_PLACE_MAX_COORD || (long long)H * W >= (1ll << 31)) {

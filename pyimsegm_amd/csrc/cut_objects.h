@@ -38,4 +38,15 @@ int launch_cut_canvas_boxes(const int32_t *segm, int H, int W, const int32_t *la
 int launch_cut_write(const uint8_t *image, const int32_t *segm, int H, int W, int C, const int32_t *labels, const CutGeom *geom,
                      const CutCrop *crops, int n, int max_h, int max_w, int use_mask, uint32_t bg, uint8_t *out, hipStream_t st);
 
+// The same three steps for the masks of n ellipses in the geom / sincos form of ellipse_place.h, each mask on its own -- the int64
+// mask add_overlap_ellipse(zeros, ell, 1) of run_ellipse_cut_scale.py :63, which is never rasterised.  max_box_rows: the tallest
+// clipped box.  The crops are written with use_mask, and a canvas pixel from outside the turned frame keeps its 0: the reference's
+// ndimage.rotate(cval=nan) leaves INT64_MIN in an int64 mask there, which counts as a pixel of the mask.
+int launch_cut_ellipse_moments(const int32_t *ell_geom, const double *sincos, int n, int max_box_rows, unsigned long long *moments,
+                               int *box_min, int *box_max, hipStream_t st);
+int launch_cut_canvas_boxes_ellipses(const int32_t *ell_geom, const double *sincos, int H, int W, const CutGeom *geom, const CutFrame *frames,
+                                     int n, int max_h, int max_w, int *box_min, int *box_max, hipStream_t st);
+int launch_cut_write_ellipses(const uint8_t *image, const int32_t *ell_geom, const double *sincos, int H, int W, int C, const CutGeom *geom,
+                              const CutCrop *crops, int n, int max_h, int max_w, uint32_t bg, uint8_t *out, hipStream_t st);
+
 }  // namespace imsegm

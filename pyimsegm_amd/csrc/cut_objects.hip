@@ -9,11 +9,17 @@
 //             atomic min / max per wave and bound.
 //   write     every crop pixel through the two composed index maps; C bytes per pixel, lanes along crop rows.
 //
+// The mask of an object is a functor: LabelMask (segm == label, imsegm_cut_objects) or EllipseMask (the pixels of one ellipse inside
+// its clipped box by the inside test of ellipse_place.h, imsegm_ellipse_cut_scale -- no mask is rasterised or uploaded, and ellipses
+// may overlap one another).  The moments of the ellipse masks are summed pixel by pixel inside the boxes, per wave, with the same
+// integer atomics.
+//
 // Both index maps are scipy's order-0 lookups in mode 'constant' (ndimage.shift, ndimage.rotate -> affine_transform): a coordinate
 // below 0 or above n - 1 is outside the source, otherwise the index is floor(x + 0.5).  The rotation coordinate is
 // ((0 + i m0) + j m1) + offset, three fp64 operations in scipy's order; the file is built with -ffp-contract=off like all others, so
 // none of them is fused.  No kernel evaluates a transcendental: cosine and sine arrive in the matrix.
 #include "cut_objects.h"
+#include "ellipse_place.h"
 
 namespace imsegm {
 
@@ -71,22 +77,25 @@ k_cut_moments(const int32_t *__restrict__ segm, int H, int W, int chunks, const 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// canvas pixel (i, j) of an object -> its source pixel; false: outside the source at either step
+// the two kinds of masks
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool cut_source(const CutGeom &g, int H, int W, int i, int j, int &sr, int &sc)
-{
-    const double di = (double)i, dj = (double)j, top_r = (double)(H - 1), top_c = (double)(W - 1);
-    const double cr = ((0.0 + di * g.m00) + dj * g.m01) + g.off_r;
-    const double cc = ((0.0 + di * g.m10) + dj * g.m11) + g.off_c;
-    if (!(cr >= 0.0 && cr <= top_r && cc >= 0.0 && cc <= top_c)) return false;       // outside the shifted frame (and NaN)
-    const double xr = floor(cr + 0.5) + g.s_r, xc = floor(cc + 0.5) + g.s_c;
-    if (!(xr >= 0.0 && xr <= top_r && xc >= 0.0 && xc <= top_c)) return false;       // shifted in from outside the source
-    sr = (int)floor(xr + 0.5);                        // in [0, H - 1]: xr <= H - 1
-    sc = (int)floor(xc + 0.5);
-    return true;
-}
-
-constexpr int CUT_TILE_W = 64, CUT_TILE_H = 16;       // a workgroup of 64 x 4 lanes walks 4 rows down
+struct LabelMask {
+    const int32_t *segm, *labels;
+    int W;
+    typedef int32_t Object;
+    __device__ __forceinline__ Object object(int k) const { return labels[k]; }
+    __device__ __forceinline__ bool holds(const Object &label, int sr, int sc) const { return segm[(size_t)sr * W + sc] == label; }
+};
+struct EllipseMask {
+    const int32_t *geom;
+    const double *sincos;
+    typedef Ellipse Object;
+    __device__ __forceinline__ Object object(int k) const { return load_ellipse(geom, sincos, k); }
+    __device__ __forceinline__ bool holds(const Object &el, int sr, int sc) const
+    {
+        return sr >= el.r0 && sr <= el.r1 && sc >= el.c0 && sc <= el.c1 && inside_ellipse(el, sr, sc);
+    }
+};
 
 __device__ __forceinline__ int wave_min_i32(int v)
 {
@@ -101,9 +110,77 @@ __device__ __forceinline__ int wave_max_i32(int v)
     return v;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// moments of ellipse masks: a workgroup owns a band of CUT_ELL_BAND rows of one clipped box, 64 columns x 4 rows per step
+// ---------------------------------------------------------------------------------------------------
+constexpr int CUT_ELL_BAND = 32;
+
 __global__ void __launch_bounds__(256)
-k_cut_canvas_boxes(const int32_t *__restrict__ segm, int H, int W, const int32_t *__restrict__ labels, const CutGeom *__restrict__ geom,
-                   const CutFrame *__restrict__ frames, int *__restrict__ box_min, int *__restrict__ box_max)
+k_cut_ellipse_moments(const int32_t *__restrict__ geom, const double *__restrict__ sincos, unsigned long long *__restrict__ moments,
+                      int *__restrict__ box_min, int *__restrict__ box_max)
+{
+    const int k = blockIdx.y, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const Ellipse el = load_ellipse(geom, sincos, k);
+    const long long first = (long long)el.r0 + (long long)blockIdx.x * CUT_ELL_BAND;
+    if (first > el.r1 || el.c1 < el.c0) return;       // (uniform over the workgroup)
+    const int last = (int)min(first + CUT_ELL_BAND - 1, (long long)el.r1);
+    long long cnt = 0, s_r = 0, s_c = 0, s_rr = 0, s_cc = 0, s_rc = 0;
+    int lo_r = 0x7fffffff, hi_r = -1, lo_c = 0x7fffffff, hi_c = -1;
+    for (int row = (int)first + ty; row <= last; row += 4)
+        for (int col = el.c0 + tx; col <= el.c1; col += 64)
+            if (inside_ellipse(el, row, col)) {
+                const long long r = row, c = col;
+                ++cnt, s_r += r, s_c += c, s_rr += r * r, s_cc += c * c, s_rc += r * c;
+                lo_r = min(lo_r, row), hi_r = max(hi_r, row), lo_c = min(lo_c, col), hi_c = max(hi_c, col);
+            }
+    if (__ballot(cnt > 0) == 0) return;               // (uniform over the wave)
+    cnt = wave_sum_i64(cnt), s_r = wave_sum_i64(s_r), s_c = wave_sum_i64(s_c);
+    s_rr = wave_sum_i64(s_rr), s_cc = wave_sum_i64(s_cc), s_rc = wave_sum_i64(s_rc);
+    lo_r = wave_min_i32(lo_r), hi_r = wave_max_i32(hi_r), lo_c = wave_min_i32(lo_c), hi_c = wave_max_i32(hi_c);
+    if (tx == 0) {
+        unsigned long long *m = moments + (size_t)k * CUT_MOMENT_WORDS;
+        cut_add(m + 0, cnt);
+        cut_add(m + 1, s_r);
+        cut_add(m + 2, s_c);
+        cut_add(m + 3, s_rr);
+        cut_add(m + 4, s_cc);
+        cut_add(m + 5, s_rc);
+        atomicMin(box_min + 2 * k, lo_r);
+        atomicMax(box_max + 2 * k, hi_r);
+        atomicMin(box_min + 2 * k + 1, lo_c);
+        atomicMax(box_max + 2 * k + 1, hi_c);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// canvas pixel (i, j) of an object -> its source pixel; CUT_INSIDE, or outside the source at one of the two steps
+// ---------------------------------------------------------------------------------------------------
+enum { CUT_INSIDE = 0, CUT_OUTSIDE_TURN = 1, CUT_OUTSIDE_SHIFT = 2 };
+
+__device__ __forceinline__ int cut_source_step(const CutGeom &g, int H, int W, int i, int j, int &sr, int &sc)
+{
+    const double di = (double)i, dj = (double)j, top_r = (double)(H - 1), top_c = (double)(W - 1);
+    const double cr = ((0.0 + di * g.m00) + dj * g.m01) + g.off_r;
+    const double cc = ((0.0 + di * g.m10) + dj * g.m11) + g.off_c;
+    if (!(cr >= 0.0 && cr <= top_r && cc >= 0.0 && cc <= top_c)) return CUT_OUTSIDE_TURN;    // outside the shifted frame (and NaN)
+    const double xr = floor(cr + 0.5) + g.s_r, xc = floor(cc + 0.5) + g.s_c;
+    if (!(xr >= 0.0 && xr <= top_r && xc >= 0.0 && xc <= top_c)) return CUT_OUTSIDE_SHIFT;   // shifted in from outside the source
+    sr = (int)floor(xr + 0.5);                        // in [0, H - 1]: xr <= H - 1
+    sc = (int)floor(xc + 0.5);
+    return CUT_INSIDE;
+}
+
+__device__ __forceinline__ bool cut_source(const CutGeom &g, int H, int W, int i, int j, int &sr, int &sc)
+{
+    return cut_source_step(g, H, W, i, j, sr, sc) == CUT_INSIDE;
+}
+
+constexpr int CUT_TILE_W = 64, CUT_TILE_H = 16;       // a workgroup of 64 x 4 lanes walks 4 rows down
+
+template <typename Mask>
+__global__ void __launch_bounds__(256)
+k_cut_canvas_boxes(const Mask mask, int H, int W, const CutGeom *__restrict__ geom, const CutFrame *__restrict__ frames,
+                   int *__restrict__ box_min, int *__restrict__ box_max)
 {
     const int k = blockIdx.z;
     const CutFrame f = frames[k];
@@ -111,14 +188,14 @@ k_cut_canvas_boxes(const int32_t *__restrict__ segm, int H, int W, const int32_t
     const int i0 = f.r0 + blockIdx.y * CUT_TILE_H + (threadIdx.x >> 6);
     if (f.c0 + (int)blockIdx.x * CUT_TILE_W >= f.c1 || f.r0 + (int)blockIdx.y * CUT_TILE_H >= f.r1) return;   // (uniform over the workgroup)
     const CutGeom g = geom[k];
-    const int32_t label = labels[k];
+    const typename Mask::Object object = mask.object(k);
     int lo_i = 0x7fffffff, hi_i = -1, lo_j = 0x7fffffff, hi_j = -1;
     if (j < f.c1) {
 #pragma unroll
         for (int step = 0; step < CUT_TILE_H / 4; ++step) {
             const int i = i0 + 4 * step;
             int sr, sc;
-            if (i < f.r1 && cut_source(g, H, W, i, j, sr, sc) && segm[(size_t)sr * W + sc] == label) {
+            if (i < f.r1 && cut_source(g, H, W, i, j, sr, sc) && mask.holds(object, sr, sc)) {
                 lo_i = min(lo_i, i);
                 hi_i = max(hi_i, i);
                 lo_j = j;
@@ -139,10 +216,12 @@ k_cut_canvas_boxes(const int32_t *__restrict__ segm, int H, int W, const int32_t
     }
 }
 
-template <int C>
+// turn_outside_holds: a canvas pixel from outside the turned frame counts as a pixel of the mask -- what the reference makes of an
+// int64 mask, whose ndimage.rotate(cval=nan) stores INT64_MIN there (imsegm_ellipse_cut_scale; 0 for boolean masks)
+template <int C, typename Mask>
 __global__ void __launch_bounds__(256)
-k_cut_write(const uint8_t *__restrict__ image, const int32_t *__restrict__ segm, int H, int W, const int32_t *__restrict__ labels,
-            const CutGeom *__restrict__ geom, const CutCrop *__restrict__ crops, int use_mask, uint32_t bg, uint8_t *__restrict__ out)
+k_cut_write(const uint8_t *__restrict__ image, const Mask mask, int H, int W, const CutGeom *__restrict__ geom,
+            const CutCrop *__restrict__ crops, int use_mask, int turn_outside_holds, uint32_t bg, uint8_t *__restrict__ out)
 {
     const int k = blockIdx.z;
     const CutCrop crop = crops[k];
@@ -150,15 +229,16 @@ k_cut_write(const uint8_t *__restrict__ image, const int32_t *__restrict__ segm,
     const int y0 = blockIdx.y * CUT_TILE_H + (threadIdx.x >> 6);
     if ((int)blockIdx.x * CUT_TILE_W >= crop.w || (int)blockIdx.y * CUT_TILE_H >= crop.h || x >= crop.w) return;
     const CutGeom g = geom[k];
-    const int32_t label = labels[k];
+    const typename Mask::Object object = mask.object(k);
 #pragma unroll
     for (int step = 0; step < CUT_TILE_H / 4; ++step) {
         const int y = y0 + 4 * step;
         if (y >= crop.h) break;
         int sr, sc;
-        const bool inside = cut_source(g, H, W, crop.r0 + y, crop.c0 + x, sr, sc);
+        const int where = cut_source_step(g, H, W, crop.r0 + y, crop.c0 + x, sr, sc);
+        const bool inside = where == CUT_INSIDE;
         const size_t src = inside ? (size_t)sr * W + sc : 0;
-        const bool keep = !use_mask || (inside && segm[src] == label);
+        const bool keep = !use_mask || (inside && mask.holds(object, sr, sc)) || (turn_outside_holds && where == CUT_OUTSIDE_TURN);
         uint8_t *o = out + crop.offset + ((size_t)y * crop.w + x) * C;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
@@ -201,18 +281,46 @@ int launch_cut_canvas_boxes(const int32_t *segm, int H, int W, const int32_t *la
                             int max_h, int max_w, int *box_min, int *box_max, hipStream_t st)
 {
     if (!cut_grid_ok(n, max_h, max_w)) return -1;
-    hipLaunchKernelGGL(k_cut_canvas_boxes, dim3(cdiv(max_w, CUT_TILE_W), cdiv(max_h, CUT_TILE_H), n), 256, 0, st, segm, H, W, labels, geom,
+    const LabelMask mask = { segm, labels, W };
+    hipLaunchKernelGGL(k_cut_canvas_boxes<LabelMask>, dim3(cdiv(max_w, CUT_TILE_W), cdiv(max_h, CUT_TILE_H), n), 256, 0, st, mask, H, W, geom,
                        frames, box_min, box_max);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int launch_cut_write(const uint8_t *image, const int32_t *segm, int H, int W, int C, const int32_t *labels, const CutGeom *geom,
-                     const CutCrop *crops, int n, int max_h, int max_w, int use_mask, uint32_t bg, uint8_t *out, hipStream_t st)
+int launch_cut_ellipse_moments(const int32_t *ell_geom, const double *sincos, int n, int max_box_rows, unsigned long long *moments,
+                               int *box_min, int *box_max, hipStream_t st)
+{
+    if (n < 1 || n > CUT_MAX_LABELS) {
+        set_error("ellipse_cut_scale: 1 to " + std::to_string(CUT_MAX_LABELS) + " ellipses");
+        return -1;
+    }
+    if (max_box_rows < 1) return 0;                   // no ellipse has a pixel: the prepared words are the answer
+    hipLaunchKernelGGL(k_cut_ellipse_moments, dim3(cdiv(max_box_rows, CUT_ELL_BAND), n), 256, 0, st, ell_geom, sincos, moments, box_min,
+                       box_max);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_cut_canvas_boxes_ellipses(const int32_t *ell_geom, const double *sincos, int H, int W, const CutGeom *geom, const CutFrame *frames,
+                                     int n, int max_h, int max_w, int *box_min, int *box_max, hipStream_t st)
+{
+    if (!cut_grid_ok(n, max_h, max_w)) return -1;
+    const EllipseMask mask = { ell_geom, sincos };
+    hipLaunchKernelGGL(k_cut_canvas_boxes<EllipseMask>, dim3(cdiv(max_w, CUT_TILE_W), cdiv(max_h, CUT_TILE_H), n), 256, 0, st, mask, H, W,
+                       geom, frames, box_min, box_max);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename Mask>
+static int cut_write(const uint8_t *image, const Mask &mask, int H, int W, int C, const CutGeom *geom, const CutCrop *crops, int n, int max_h,
+                     int max_w, int use_mask, int turn_outside_holds, uint32_t bg, uint8_t *out, hipStream_t st)
 {
     if (!cut_grid_ok(n, max_h, max_w)) return -1;
     const dim3 grid(cdiv(max_w, CUT_TILE_W), cdiv(max_h, CUT_TILE_H), n);
-#define CUT_WRITE(CH) hipLaunchKernelGGL(k_cut_write<CH>, grid, 256, 0, st, image, segm, H, W, labels, geom, crops, use_mask, bg, out)
+#define CUT_WRITE(CH) \
+    hipLaunchKernelGGL((k_cut_write<CH, Mask>), grid, 256, 0, st, image, mask, H, W, geom, crops, use_mask, turn_outside_holds, bg, out)
     if (C == 1)
         CUT_WRITE(1);
     else if (C == 2)
@@ -228,6 +336,20 @@ int launch_cut_write(const uint8_t *image, const int32_t *segm, int H, int W, in
 #undef CUT_WRITE
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int launch_cut_write(const uint8_t *image, const int32_t *segm, int H, int W, int C, const int32_t *labels, const CutGeom *geom,
+                     const CutCrop *crops, int n, int max_h, int max_w, int use_mask, uint32_t bg, uint8_t *out, hipStream_t st)
+{
+    const LabelMask mask = { segm, labels, W };
+    return cut_write(image, mask, H, W, C, geom, crops, n, max_h, max_w, use_mask, 0, bg, out, st);
+}
+
+int launch_cut_write_ellipses(const uint8_t *image, const int32_t *ell_geom, const double *sincos, int H, int W, int C, const CutGeom *geom,
+                              const CutCrop *crops, int n, int max_h, int max_w, uint32_t bg, uint8_t *out, hipStream_t st)
+{
+    const EllipseMask mask = { ell_geom, sincos };
+    return cut_write(image, mask, H, W, C, geom, crops, n, max_h, max_w, 1, 1, bg, out, st);
 }
 
 }  // namespace imsegm

@@ -28,6 +28,32 @@ __device__ __forceinline__ bool ellipse_inside_offsets(double a, double b, doubl
     return u * u + v * v < 1.0;
 }
 
+// one ellipse as the kernels hold it (ellipse_place.hip; the ellipse masks of cut_objects.hip)
+struct Ellipse {
+    int r, c, r_rad, c_rad, r0, c0, r1, c1;
+    double sn, cs;
+};
+
+__device__ __forceinline__ Ellipse load_ellipse(const int32_t *geom, const double *sincos, int e)
+{
+    const int32_t *g = geom + (size_t)e * ELLIPSE_GEOM_INTS;
+    Ellipse el;
+    el.r = g[0], el.c = g[1], el.r_rad = g[2], el.c_rad = g[3], el.r0 = g[4], el.c0 = g[5], el.r1 = g[6], el.c1 = g[7];
+    el.sn = sincos[2 * (size_t)e], el.cs = sincos[2 * (size_t)e + 1];
+    return el;
+}
+
+// the inside test above for the integer offsets of a pixel of the clipped box from the integer centre
+__device__ __forceinline__ bool inside_ellipse(const Ellipse &el, int row, int col)
+{
+    return ellipse_inside_offsets((double)(row - el.r), (double)(col - el.c), el.sn, el.cs, (double)el.r_rad, (double)el.c_rad);
+}
+
+// Host side (api_ellipse.hip): the arguments every call that walks ellipse boxes shares -- a map (or image) `segm` of H x W below 2^31
+// pixels, n >= 0 ellipses with radii >= 1, centres and radii within ELLIPSE_PLACE_MAX_COORD and boxes clipped to the map; -1 with a
+// message otherwise.  *max_box_rows: the tallest clipped box (0: no ellipse has a pixel).
+int check_ellipses(const char *who, const void *segm, int H, int W, int n, const int32_t *geom, const double *sincos, int *max_box_rows);
+
 // counts[v] += number of pixels with value v for 1 <= v < ELLIPSE_PLACE_LABELS (counts zeroed by the caller); *beyond = 1 when a
 // value >= ELLIPSE_PLACE_LABELS is met
 int launch_ellipse_label_counts(const int32_t *segm, size_t n_pixels, int32_t *counts, int32_t *beyond, hipStream_t st);

@@ -21,26 +21,6 @@ constexpr int PLACE_THREADS = 1024, PLACE_ROWS = PLACE_THREADS / 64;      // the
 constexpr int OVER_THREADS = 256, OVER_ROWS = OVER_THREADS / 64;          // the overlaps: 64 columns x 4 rows per step,
 constexpr int OVER_BAND = 32;                                             // one workgroup per band of 32 box rows
 
-struct Ellipse {
-    int r, c, r_rad, c_rad, r0, c0, r1, c1;
-    double sn, cs;
-};
-
-__device__ __forceinline__ Ellipse load_ellipse(const int32_t *geom, const double *sincos, int e)
-{
-    const int32_t *g = geom + (size_t)e * ELLIPSE_GEOM_INTS;
-    Ellipse el;
-    el.r = g[0], el.c = g[1], el.r_rad = g[2], el.c_rad = g[3], el.r0 = g[4], el.c0 = g[5], el.r1 = g[6], el.c1 = g[7];
-    el.sn = sincos[2 * (size_t)e], el.cs = sincos[2 * (size_t)e + 1];
-    return el;
-}
-
-// the inside test of ellipse_place.h for the integer offsets of a pixel from the integer centre
-__device__ __forceinline__ bool inside_ellipse(const Ellipse &el, int row, int col)
-{
-    return ellipse_inside_offsets((double)(row - el.r), (double)(col - el.c), el.sn, el.cs, (double)el.r_rad, (double)el.c_rad);
-}
-
 __global__ __launch_bounds__(256) void k_ellipse_label_counts(const int32_t *__restrict__ segm, size_t n_pixels,
                                                              int32_t *__restrict__ counts, int32_t *__restrict__ beyond)
 {

@@ -58,6 +58,7 @@ struct imsegm_ctx {
     int acc_n[PG_COUNT] = { 0 };
     DevBuf gc_buf;   // scratch of imsegm_cut_general_graph
     DevBuf aux_buf;  // small second scratch (border histogram of imsegm_assume_bg_on_boundary)
+    DevBuf resize_buf;  // scratch of csrc/resize.hip: the crops of imsegm_ellipse_cut_scale stay in aux_buf while it is carved
     // mixture fit on the device (csrc/mixture_fit.hip): the n x F table imsegm_kmeans_lloyd uploaded stays here for the
     // imsegm_mixture_em that follows, with the labels of its R restarts behind it in `fit_work`
     DevBuf fit_table, fit_work;
