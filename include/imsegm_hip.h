@@ -189,6 +189,11 @@ IMSEGM_API int imsegm_image2d_get_nearest(imsegm_image2d *img, int32_t *nearest_
 /* out[3] = { min, max of the uploaded image as the last imsegm_image2d_slic reduced them on the device, max |value| of its
  * pre-processed planes (what fixes the fixed-point format of the centroid sums) } */
 IMSEGM_API int imsegm_image2d_get_pre_scalars(imsegm_image2d *img, double out[3]);
+/* inspection: the centroid table of the last imsegm_image2d_slic as its last centroid update left it (no update follows the last
+ * sweep: after max_iter sweeps this is the table that went INTO sweep max_iter).  centroids_out: *n_centroids_out rows of
+ * (cy, cx, cL, ca, cb) float64; windows_out: as many integer search windows (y0, y1, x0, x1), empty (all zero) for a centroid that
+ * lost its last pixel, whose row keeps the values it last had.  Both NULL: only the count.  Reads the table, launches nothing. */
+IMSEGM_API int imsegm_image2d_get_centroids(imsegm_image2d *img, double *centroids_out, int32_t *windows_out, int *n_centroids_out);
 
 /* Replaces imsegm.features_cython.computeColorImage2dMean / Energy / Variance + normColorFeatures
  * (imsegm/features_cython.pyx:59-141) on the uploaded image and the current label map.

@@ -159,6 +159,7 @@ _SIGNATURES = {
     'imsegm_image2d_get_lab': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_get_nearest': (C.c_int, [_vp, _vp]),
     'imsegm_image2d_get_pre_scalars': (C.c_int, [_vp, _vp]),
+    'imsegm_image2d_get_centroids': (C.c_int, [_vp, _vp, _vp, _ip]),
     'imsegm_image2d_color_stats': (C.c_int, [_vp, _vp, _vp, _vp]),
     'imsegm_image2d_graph': (C.c_int, [_vp, _vp, C.c_int, _ip, _vp, _vp]),
     'imsegm_image2d_gather': (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp]),
@@ -1181,6 +1182,18 @@ class Image2D(object):
         out = np.empty(self.shape, dtype=np.int32)
         _check(load_library().imsegm_image2d_get_nearest(self._h, _ptr(out)))
         return out
+
+    def get_centroids(self):
+        """the centroid table of the last :meth:`slic` as its last centroid update left it -- no update follows the last sweep, so
+        after ``max_iter`` sweeps this is the table that went into sweep ``max_iter``: (K x 5 float64 rows of (cy, cx, cL, ca, cb),
+        K x 4 int32 search windows (y0, y1, x0, x1)); a centroid that lost its last pixel has an empty (all zero) window"""
+        lib = load_library()
+        count = C.c_int(0)
+        _check(lib.imsegm_image2d_get_centroids(self._h, None, None, C.byref(count)))
+        rows = np.empty((count.value, 5), dtype=np.float64)
+        windows = np.empty((count.value, 4), dtype=np.int32)
+        _check(lib.imsegm_image2d_get_centroids(self._h, _ptr(rows), _ptr(windows), C.byref(count)))
+        return rows, windows
 
     def color_stats(self, mean=True, energy=True, var=True):
         k = self.n_labels

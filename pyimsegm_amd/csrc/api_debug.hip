@@ -80,6 +80,7 @@ int imsegm_debug_image2d_poison(imsegm_image2d *im, uint32_t word, size_t *bytes
     im->feat_F = 0;
     im->place_F = 0;
     im->place_col = 0;
+    im->slic_K = 0;
     im->slic_ran = false;                                  // nothing for get_lab / get_nearest / get_pre_scalars to report
     im->small_zeroed = false;                              // the page of reduction words is cleared again where it is next needed
     if (im->slic_exec) {

@@ -277,6 +277,7 @@ int imsegm_image2d_slic(imsegm_image2d *im, int minmax_normalize, int n_segments
     }
     ctx->end(sp_all);
     im->slic_ran = true;
+    im->slic_K = K;
     im->n_labels = n_labels;
     im->have_labels = true;
     im->labels_connected = false;
@@ -415,6 +416,35 @@ int imsegm_image2d_get_nearest(imsegm_image2d *im, int32_t *nearest_out)
     }
     HIP_TRY(hipMemcpyAsync(nearest_out, im->nearest.p, im->n * 4, hipMemcpyDeviceToHost, im->ctx->stream));
     HIP_TRY(hipStreamSynchronize(im->ctx->stream));
+    return 0;
+}
+
+// inspection: the centroid table as the last centroid update of imsegm_image2d_slic left it (no update follows the last sweep).
+// One copy of the SoA block cy | cx | cL | ca | cb | win out of `cent` (slic_place_state) behind a stream synchronisation, turned
+// into rows on the host; nothing on the path of the sweeps
+int imsegm_image2d_get_centroids(imsegm_image2d *im, double *centroids_out, int32_t *windows_out, int *n_centroids_out)
+{
+    if (!im || bind(im->ctx)) return -1;
+    if (wrong_kind(im, false)) return -1;
+    const size_t K = (size_t)im->slic_K;
+    if (!im->slic_ran || K < 1 || im->cent.cap < slic_cent_bytes((int)K)) {
+        set_error("slic has not been run");
+        return -1;
+    }
+    if (n_centroids_out) *n_centroids_out = (int)K;
+    hipStream_t st = im->ctx->stream;
+    if (centroids_out || windows_out) {
+        std::vector<unsigned char> host(K * (5 * 8 + 16));
+        HIP_TRY(hipMemcpyAsync(host.data(), im->cent.as<unsigned char>() + K * 9 * 8, host.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const double *col = reinterpret_cast<const double *>(host.data());
+        if (centroids_out)
+            for (size_t k = 0; k < K; ++k)
+                for (int j = 0; j < 5; ++j) centroids_out[k * 5 + j] = col[(size_t)j * K + k];
+        if (windows_out) memcpy(windows_out, host.data() + K * 5 * 8, K * 16);
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     return 0;
 }
 

@@ -176,6 +176,7 @@ struct imsegm_image2d {
     bool tex_ready = false;
     bool small_zeroed = false;                  // `small` has been cleared since it was allocated (ensure_small)
     bool slic_ran = false;                      // a SLIC of this session has left its planes, assignment and scalars (the get_* of them)
+    int slic_K = 0;                             // centroids of the last imsegm_image2d_slic: rows of the table in `cent` (imsegm_image2d_get_centroids)
     bool is_volume = false;
     double vol_off = 0.0, vol_scale = 1.0;      // intensity seen by the volume SLIC = (v + off) * scale
     int vol_pre_dtype = -1, vol_K = 0;          // the last imsegm_volume_slic: type of its plane in labB (IMSEGM_F32 / IMSEGM_F64), centroids
