@@ -660,6 +660,23 @@ IMSEGM_API int imsegm_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_componen
                                  double reg_covar, double tol, int max_iter, double *weights_out, double *means_out,
                                  double *covariances_out, double *prec_chol_out, double *lower_bound_out, int32_t *n_iter_out,
                                  int32_t *converged_out, int32_t *not_pd_out);
+/* Replaces the variational loop of sklearn.mixture.BayesianGaussianMixture(covariance_type='full') (sklearn/mixture/_base.py
+ * fit_predict with _bayesian_mixture.py _initialize, _m_step, _estimate_log_prob, _estimate_log_weights, _compute_lower_bound) on
+ * the resident table, from one-hot responsibilities: `labels` (n_restarts x n_rows int32, host) or else (NULL) the labels the last
+ * imsegm_kmeans_lloyd left on the device.  prior_type: 0 dirichlet_process, 1 dirichlet_distribution; the priors are the
+ * estimator's checked ones (weight_concentration_prior_, mean_precision_prior_, mean_prior_ [n_features],
+ * degrees_of_freedom_prior_, covariance_prior_ [n_features x n_features]).  A restart stops when |lower bound - previous| < tol or
+ * after max_iter iterations (tol = 0: exactly max_iter) and is frozen from then on.  Outputs per restart (each may be NULL):
+ * weight_concentration_out n_restarts x 2 x n_components (rows a, b of the process; row 0 of the distribution, row 1 zero),
+ * mean_precision_out, means_out, degrees_of_freedom_out, covariances_out, prec_chol_out, last lower bound, iterations, converged
+ * flag, not_pd_out (1: a covariance was not positive definite -- the restart stopped there).  Caps and status: imsegm_mixture_em's. */
+IMSEGM_API int imsegm_bayes_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_components, const int32_t *labels, int prior_type,
+                                       double weight_concentration_prior, double mean_precision_prior, const double *mean_prior,
+                                       double degrees_of_freedom_prior, const double *covariance_prior, double reg_covar,
+                                       double tol, int max_iter, double *weight_concentration_out, double *mean_precision_out,
+                                       double *means_out, double *degrees_of_freedom_out, double *covariances_out,
+                                       double *prec_chol_out, double *lower_bound_out, int32_t *n_iter_out,
+                                       int32_t *converged_out, int32_t *not_pd_out);
 /* The same two calls for WIDE tables, 17 <= n_features <= 256 (csrc/mixture_fit_wide.hip: fp64 matrix-instruction tiles instead
  * of a table row in registers): argument lists, outputs and status conventions are those of imsegm_kmeans_lloyd and
  * imsegm_mixture_em; the table imsegm_kmeans_lloyd_wide uploaded stays in the context for the imsegm_mixture_em_wide that

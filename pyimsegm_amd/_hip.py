@@ -201,6 +201,8 @@ _SIGNATURES = {
     'imsegm_kmeans_lloyd': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'imsegm_mixture_em': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
+    'imsegm_bayes_mixture_em': (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, C.c_double, _vp,
+                                          C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'imsegm_kmeans_lloyd_wide': (C.c_int, [_vp, _vp, C.c_long, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                            _vp]),
     'imsegm_mixture_em_wide': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
@@ -586,6 +588,42 @@ def _mixture_em(entry, max_features, n_restarts, n_components, n_features, label
                                            _ptr(converged), _ptr(not_pd)))
     return dict(weights=weights, means=means, covariances=cov, precisions_cholesky=prec, lower_bound=bound, n_iter=n_iter,
                 converged=converged.astype(bool), not_pd=not_pd.astype(bool))
+
+
+#: ``weight_concentration_prior_type`` of scikit-learn's BayesianGaussianMixture -> ``prior_type`` of ``imsegm_bayes_mixture_em``
+BAYES_PRIOR_TYPES = {'dirichlet_process': 0, 'dirichlet_distribution': 1}
+
+
+def bayes_mixture_em(n_restarts, n_components, n_features, prior_type, weight_concentration_prior, mean_precision_prior, mean_prior,
+                     degrees_of_freedom_prior, covariance_prior, labels=None, reg_covar=1e-6, tol=1e-3, max_iter=100, ctx=None):
+    """``imsegm_bayes_mixture_em``: the variational fit of ``BayesianGaussianMixture(covariance_type='full')``, all restarts at
+    once, on the table the last :func:`kmeans_lloyd` of ``ctx`` uploaded.  Start: one-hot responsibilities from ``labels`` (R x n
+    int32) or -- None -- from the labels that call left on the device.  ``prior_type`` is scikit-learn's name (a key of
+    ``BAYES_PRIOR_TYPES``); the priors are the estimator's checked ones (``weight_concentration_prior_`` ...).  Returns a dict:
+    weight_concentration (R x 2 x C: rows a, b of the process; row 0 of the distribution), mean_precision, means,
+    degrees_of_freedom, covariances, precisions_cholesky, lower_bound, n_iter, converged, not_pd (R flags: a covariance was not
+    positive definite, the restart stopped there).  Raises :class:`HipFitCapsError` outside F <= 16, C <= 8, R <= 16."""
+    ctx = ctx or default_context()
+    R, K, F = int(n_restarts), int(n_components), int(n_features)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(R, -1)
+    mean_prior = np.ascontiguousarray(mean_prior, dtype=np.float64)
+    covariance_prior = np.ascontiguousarray(covariance_prior, dtype=np.float64)
+    if mean_prior.shape != (F, ) or covariance_prior.shape != (F, F):
+        raise ValueError('the mean prior is F, the covariance prior F x F')
+    safe = (min(R, 16), min(K, 8), min(F, 16))          # (beyond the caps the call writes nothing)
+    concentration, precision, dof = np.zeros((safe[0], 2, safe[1])), np.zeros(safe[:2]), np.zeros(safe[:2])
+    means, cov, prec = np.zeros(safe), np.zeros(safe + (safe[2], )), np.zeros(safe + (safe[2], ))
+    bound = np.zeros(safe[0])
+    n_iter, converged, not_pd = (np.zeros(safe[0], dtype=np.int32) for _ in range(3))
+    _check(load_library().imsegm_bayes_mixture_em(
+        ctx._h, R, K, _ptr(labels), BAYES_PRIOR_TYPES[prior_type], float(weight_concentration_prior), float(mean_precision_prior),
+        _ptr(mean_prior), float(degrees_of_freedom_prior), _ptr(covariance_prior), float(reg_covar), float(tol), int(max_iter),
+        _ptr(concentration), _ptr(precision), _ptr(means), _ptr(dof), _ptr(cov), _ptr(prec), _ptr(bound), _ptr(n_iter),
+        _ptr(converged), _ptr(not_pd)))
+    return dict(weight_concentration=concentration, mean_precision=precision, means=means, degrees_of_freedom=dof, covariances=cov,
+                precisions_cholesky=prec, lower_bound=bound, n_iter=n_iter, converged=converged.astype(bool),
+                not_pd=not_pd.astype(bool))
 
 
 def mixture_em_wide(n_restarts, n_components, n_features, labels=None, start=None, reg_covar=1e-6, tol=1e-3, max_iter=100, ctx=None):

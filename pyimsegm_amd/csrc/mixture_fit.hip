@@ -16,6 +16,12 @@
 // fixed order (sixteen strided sub-sums, then those in order) and does the small dense algebra.  Every restart's arithmetic is
 // its own, so a restart gives the same bits alone and in a batch, and the same call gives the same bits every time.
 // A restart that is done (converged, out of iterations, flagged) is skipped by every kernel: its parameters and outputs freeze.
+//
+// The variational fit (imsegm_bayes_mixture_em; sklearn/mixture/_bayesian_mixture.py `_initialize`, `_m_step`, `_estimate_log_prob`,
+// `_estimate_log_weights`, `_compute_lower_bound` for covariance_type='full') is the template parameter BAYES of the two EM passes
+// and their finalisers: the row passes are the same, the finaliser of the covariance pass does the posterior updates, folds the
+// per-component constant of the E step (digamma, fit_digamma below) into the log-weight slot of `params` and forms the lower bound
+// (lgamma of the device library) from the entropy sum of the E step's pass.  The BAYES = false instantiations are what they were.
 #include "mixture_fit.h"
 
 #include <cmath>
@@ -43,6 +49,12 @@ struct FitArgs {
     int *done, *strict, *n_iter, *flags, *pending, *converged;      // [R] each
     double *bound, *inertia;    // [R] each
     double *out_w, *out_means, *out_cov, *out_prec;
+    // the variational fit (imsegm_bayes_mixture_em) only
+    int prior_type;             // 0: dirichlet_process, 1: dirichlet_distribution
+    double wc_prior, mp_prior, dof_prior;
+    const double *prior;        // mean_prior F | covariance_prior F F
+    double *bstate;             // [R][4 C]: weight concentration a C | b C | mean precision C | degrees of freedom C
+    double *entropy;            // [R]: sum over rows and components of resp log resp of the last E step
 };
 
 __host__ __device__ inline int fit_params_size(int C, int F) { return 2 * C + 2 * C * F + C * F * F; }
@@ -105,7 +117,24 @@ template <int FP> __device__ __forceinline__ int fit_nearest(const double (&x)[F
     return best;
 }
 
-template <int MODE, int FP> __global__ __launch_bounds__(256) void k_fit_pass(const FitArgs a)
+// digamma of a positive argument: the recurrence up to 10, then the asymptotic series through x^-16 (the next term is below
+// 4e-18 there)
+__device__ inline double fit_digamma(double x)
+{
+    double r = 0.0;
+    while (x < 10.0) {
+        r -= 1.0 / x;
+        x += 1.0;
+    }
+    const double i = 1.0 / x, i2 = i * i;
+    const double s = i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132 - i2 * (691.0 / 32760
+                     - i2 * (1.0 / 12 - i2 * (3617.0 / 8160))))))));
+    return r + ((log(x) - 0.5 * i) - s);
+}
+
+// BAYES: the variational fit of BayesianGaussianMixture -- the same row passes; the per-row extra of the E step is the entropy
+// term sum_k resp log resp instead of log_prob_norm (sklearn/mixture/_bayesian_mixture.py `_compute_lower_bound`)
+template <int MODE, int FP, bool BAYES = false> __global__ __launch_bounds__(256) void k_fit_pass(const FitArgs a)
 {
     extern __shared__ double fit_lds[];
     const int tid = threadIdx.x;
@@ -190,7 +219,15 @@ template <int MODE, int FP> __global__ __launch_bounds__(256) void k_fit_pass(co
                 const double lpn = top + log(sum);
 #pragma unroll
                 for (int c = 0; c < FIT_MAX_C; ++c) resp[c] = (valid && c < C) ? exp(lp[c] - lpn) : 0.0;
-                if (MODE == FIT_EM_SUMS && valid) extra = lpn;
+                if constexpr (BAYES) {
+                    if (MODE == FIT_EM_SUMS && valid) {
+#pragma unroll
+                        for (int c = 0; c < FIT_MAX_C; ++c)
+                            if (c < C) extra += resp[c] * (lp[c] - lpn);
+                    }
+                } else {
+                    if (MODE == FIT_EM_SUMS && valid) extra = lpn;
+                }
             }
 
             if (MODE != FIT_KM_FINAL) {
@@ -248,7 +285,9 @@ template <int MODE, int FP> __global__ __launch_bounds__(256) void k_fit_pass(co
 }
 
 // one workgroup per restart: the slots of `partial` in a fixed order, then what the pass was for
-template <int MODE> __global__ __launch_bounds__(256) void k_fit_final(const FitArgs a)
+// BAYES (FIT_EM_SUMS, FIT_EM_COV): the posterior updates of `_m_step`, the per-component constant of `_estimate_log_prob` +
+// `_estimate_log_weights` folded into the log-weight slot of `params`, and the lower bound with the parameters after the M step
+template <int MODE, bool BAYES = false> __global__ __launch_bounds__(256) void k_fit_final(const FitArgs a)
 {
     __shared__ double tot[FIT_MAX_C * 144 + 16];
     __shared__ double tmp[256];
@@ -317,21 +356,40 @@ template <int MODE> __global__ __launch_bounds__(256) void k_fit_final(const Fit
             a.nk[r * C + c] = nk;
             for (int f = 0; f < F; ++f) a.means_new[((size_t)r * C + c) * F + f] = tot[c * NG16 + 1 + f] / nk;
         }
-        if (tid == 0 && !a.from_labels) {
+        if constexpr (BAYES) {
+            if (tid == 0 && !a.from_labels) a.entropy[r] = tot[C * NG16];
+        } else if (tid == 0 && !a.from_labels) {
             const double now = tot[C * NG16] / (double)a.n;
             a.pending[r] = fabs(now - a.bound[r]) < a.tol;
             a.bound[r] = now;
         }
     } else {
         double *par = a.params + (size_t)r * fit_params_size(C, F);
+        __shared__ double bc[4][FIT_MAX_C];      // BAYES: E-step constant | log Wishart norm | mean precision | degrees of freedom
         if (c < C) {
             double *A = mat[c][0], *Z = mat[c][1];
             const double nk = a.nk[r * C + c];
             double *cov = a.out_cov + ((size_t)r * C + c) * F * F;
+            double mp = 0.0, dof = 0.0, scale = 0.0;
+            if constexpr (BAYES) {
+                // `_estimate_means`: the posterior mean replaces the weighted mean the covariance pass was centred on; the
+                // difference to the prior mean waits in Z's first row for the covariance below
+                mp = a.mp_prior + nk;
+                dof = a.dof_prior + nk;
+                scale = nk * a.mp_prior / mp;
+                double *mn = a.means_new + ((size_t)r * C + c) * F;
+                for (int f = 0; f < F; ++f) {
+                    const double xk = mn[f];
+                    Z[f] = xk - a.prior[f];
+                    mn[f] = (a.mp_prior * a.prior[f] + nk * xk) / mp;
+                }
+            }
             for (int i = 0; i < F; ++i)
                 for (int j = 0; j <= i; ++j) {
                     double v = tot[c * NG16 + i * (i + 1) / 2 + j] / nk;
                     if (i == j) v += a.reg;
+                    if constexpr (BAYES)        // `_estimate_wishart_full`
+                        v = ((a.prior[F + i * F + j] + nk * v) + scale * (Z[i] * Z[j])) / dof;
                     A[i * FIT_MAX_F + j] = v;
                     cov[i * F + j] = v;
                     cov[j * F + i] = v;
@@ -383,6 +441,18 @@ template <int MODE> __global__ __launch_bounds__(256) void k_fit_final(const Fit
                     muproj[j] = s;
                 }
                 par[C + c] = logdet;
+                if constexpr (BAYES) {
+                    double dg = 0.0, lg = 0.0;
+                    for (int i = 0; i < F; ++i) {
+                        dg += fit_digamma(0.5 * (dof - i));
+                        lg += lgamma(0.5 * (dof - i));
+                    }
+                    const double half_f_log_dof = 0.5 * F * log(dof), ld = logdet - half_f_log_dof;
+                    bc[0][c] = -half_f_log_dof + 0.5 * ((F * 0.6931471805599453 + dg) - F / mp);
+                    bc[1][c] = -((dof * ld + dof * F * 0.5 * 0.6931471805599453) + lg);
+                    bc[2][c] = mp;
+                    bc[3][c] = dof;
+                }
             }
         }
         __syncthreads();
@@ -392,6 +462,55 @@ template <int MODE> __global__ __launch_bounds__(256) void k_fit_final(const Fit
             if (bad) {
                 a.flags[r] |= FIT_FLAG_NOT_PD;
                 a.done[r] = 1;
+            } else if constexpr (BAYES) {
+                double *bs = a.bstate + (size_t)r * 4 * C;
+                const double *nk = a.nk + r * C;
+                double log_norm_weight = 0.0, wishart = 0.0, log_mp = 0.0;
+                if (a.prior_type == 0) {        // stick breaking: `_estimate_weights`, `_estimate_log_weights`, -sum betaln
+                    double tail = 0.0, run = 0.0;
+                    for (int q = C - 1; q >= 0; --q) {
+                        bs[q] = 1.0 + nk[q];
+                        bs[C + q] = a.wc_prior + tail;
+                        tail += nk[q];
+                    }
+                    for (int q = 0; q < C; ++q) {
+                        const double wa = bs[q], wb = bs[C + q];
+                        const double dsum = fit_digamma(wa + wb), da = fit_digamma(wa), db = fit_digamma(wb);
+                        par[q] = bc[0][q] + ((da - dsum) + run);
+                        run += db - dsum;
+                        log_norm_weight -= (lgamma(wa) + lgamma(wb)) - lgamma(wa + wb);
+                    }
+                } else {
+                    double csum = 0.0, lsum = 0.0;
+                    for (int q = 0; q < C; ++q) {
+                        bs[q] = a.wc_prior + nk[q];
+                        bs[C + q] = 0.0;
+                        csum += bs[q];
+                        lsum += lgamma(bs[q]);
+                    }
+                    const double dsum = fit_digamma(csum);
+                    for (int q = 0; q < C; ++q) par[q] = bc[0][q] + (fit_digamma(bs[q]) - dsum);
+                    log_norm_weight = lgamma(csum) - lsum;
+                }
+                for (int q = 0; q < C; ++q) {
+                    bs[2 * C + q] = bc[2][q];
+                    bs[3 * C + q] = bc[3][q];
+                    wishart += bc[1][q];
+                    log_mp += log(bc[2][q]);
+                }
+                if (!a.from_labels) {
+                    const double now = ((-a.entropy[r] - wishart) - log_norm_weight) - 0.5 * F * log_mp;
+                    const bool settled = fabs(now - a.bound[r]) < a.tol;
+                    a.bound[r] = now;
+                    const int it = a.n_iter[r] + 1;
+                    a.n_iter[r] = it;
+                    if (settled) {
+                        a.converged[r] = 1;
+                        a.done[r] = 1;
+                    } else if (it >= a.max_iter) {
+                        a.done[r] = 1;
+                    }
+                }
             } else {
                 double w[FIT_MAX_C], wsum = 0.0;
                 for (int q = 0; q < C; ++q) {
@@ -448,7 +567,7 @@ __global__ void k_fit_set_params(const FitArgs a)
 namespace {
 
 struct FitLayout {
-    size_t o_labels, o_centres, o_params, o_means_new, o_nk, o_partial, o_ints, o_dbl, o_w, o_means, o_cov, o_prec, bytes;
+    size_t o_labels, o_centres, o_params, o_means_new, o_nk, o_partial, o_ints, o_dbl, o_w, o_means, o_cov, o_prec, o_bayes, bytes;
     int G, L, ps_max;
 };
 
@@ -481,6 +600,7 @@ FitLayout fit_layout(int n, int F, int C, int R)
     lay.o_means = take((size_t)R * C * F * 8);
     lay.o_cov = take((size_t)R * C * F * F * 8);
     lay.o_prec = take((size_t)R * C * F * F * 8);
+    lay.o_bayes = take(((size_t)R * (4 * C + 1) + F + F * F) * 8);      // state R 4 C | entropy R | priors F + F F
     lay.bytes = at;
     return lay;
 }
@@ -517,10 +637,13 @@ FitArgs fit_args(imsegm_ctx *ctx, const FitLayout &lay, int C, int R)
     a.out_means = reinterpret_cast<double *>(w + lay.o_means);
     a.out_cov = reinterpret_cast<double *>(w + lay.o_cov);
     a.out_prec = reinterpret_cast<double *>(w + lay.o_prec);
+    a.bstate = reinterpret_cast<double *>(w + lay.o_bayes);
+    a.entropy = a.bstate + (size_t)R * 4 * C;
+    a.prior = a.entropy + R;
     return a;
 }
 
-template <int MODE> int fit_pass(FitArgs a, hipStream_t st)
+template <int MODE, bool BAYES = false> int fit_pass(FitArgs a, hipStream_t st)
 {
     const int F = a.F, C = a.C;
     const int values = MODE == FIT_KM_FINAL ? 0 : MODE == FIT_EM_COV ? F * (F + 1) / 2 : 1 + F;
@@ -534,14 +657,14 @@ template <int MODE> int fit_pass(FitArgs a, hipStream_t st)
         a.r1 = std::min(a.R, r0 + block);
         const size_t lds = (size_t)(a.r1 - a.r0) * per_restart + red_bytes;
         if (F <= 4)
-            hipLaunchKernelGGL((k_fit_pass<MODE, 4>), dim3(a.G), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_fit_pass<MODE, 4, BAYES>), dim3(a.G), dim3(256), lds, st, a);
         else if (F <= 8)
-            hipLaunchKernelGGL((k_fit_pass<MODE, 8>), dim3(a.G), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_fit_pass<MODE, 8, BAYES>), dim3(a.G), dim3(256), lds, st, a);
         else
-            hipLaunchKernelGGL((k_fit_pass<MODE, 16>), dim3(a.G), dim3(256), lds, st, a);
+            hipLaunchKernelGGL((k_fit_pass<MODE, 16, BAYES>), dim3(a.G), dim3(256), lds, st, a);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL((k_fit_final<MODE>), dim3(a.R), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_fit_final<MODE, BAYES>), dim3(a.R), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -674,6 +797,89 @@ int imsegm_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_components, const i
     if (prec_chol_out) HIP_TRY(hipMemcpyAsync(prec_chol_out, a.out_prec, (size_t)R * C * F * F * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int r = 0; r < R; ++r) {
+        if (lower_bound_out) lower_bound_out[r] = bounds[r];
+        if (n_iter_out) n_iter_out[r] = ints[2 * R + r];
+        if (converged_out) converged_out[r] = ints[5 * R + r];
+        if (not_pd_out) not_pd_out[r] = (ints[3 * R + r] & FIT_FLAG_NOT_PD) != 0;
+    }
+    return 0;
+}
+
+int imsegm_bayes_mixture_em(imsegm_ctx *ctx, int n_restarts, int n_components, const int32_t *labels, int prior_type,
+                            double weight_concentration_prior, double mean_precision_prior, const double *mean_prior,
+                            double degrees_of_freedom_prior, const double *covariance_prior, double reg_covar, double tol,
+                            int max_iter, double *weight_concentration_out, double *mean_precision_out, double *means_out,
+                            double *degrees_of_freedom_out, double *covariances_out, double *prec_chol_out, double *lower_bound_out,
+                            int32_t *n_iter_out, int32_t *converged_out, int32_t *not_pd_out)
+{
+    if (bind(ctx)) return -1;
+    if (ctx->fit_n < 1) {
+        set_error("bayes_mixture_em: no resident table (imsegm_kmeans_lloyd uploads it)");
+        return -1;
+    }
+    const int n = ctx->fit_n, F = ctx->fit_F, C = n_components, R = n_restarts;
+    if (const int rc = fit_caps("bayes_mixture_em", n, F, C, R)) return rc;
+    if (max_iter < 0 || !mean_prior || !covariance_prior || (prior_type != 0 && prior_type != 1)) {
+        set_error("bayes_mixture_em: bad arguments (the priors are given, the prior type is 0 or 1)");
+        return -1;
+    }
+    if (!labels && (ctx->fit_label_restarts != R || ctx->fit_label_classes != C)) {
+        set_error("bayes_mixture_em: no resident labels of that many restarts and classes (imsegm_kmeans_lloyd leaves them)");
+        return -1;
+    }
+    hipStream_t st = ctx->stream;
+    const FitLayout lay = fit_layout(n, F, C, R);
+    if (!labels && ctx->fit_work.cap < lay.bytes) {
+        set_error("bayes_mixture_em: the resident labels are gone");
+        return -1;
+    }
+    if (labels) ctx->fit_label_restarts = 0;           // (host labels overwrite the resident ones)
+    if (ctx->fit_work.ensure(lay.bytes)) return -1;
+    FitArgs a = fit_args(ctx, lay, C, R);
+    a.max_iter = max_iter;
+    a.tol = tol;
+    a.reg = reg_covar;
+    a.prior_type = prior_type;
+    a.wc_prior = weight_concentration_prior;
+    a.mp_prior = mean_precision_prior;
+    a.dof_prior = degrees_of_freedom_prior;
+    unsigned char *w = ctx->fit_work.as<unsigned char>();
+    double *prior = a.entropy + R;
+    HIP_TRY(hipMemsetAsync(w + lay.o_ints, 0, (size_t)6 * R * 4, st));
+    double start[2 * FIT_MAX_R];
+    for (int r = 0; r < 2 * R; ++r) start[r] = r < R ? -std::numeric_limits<double>::infinity() : 0.0;
+    HIP_TRY(hipMemcpyAsync(w + lay.o_dbl, start, (size_t)2 * R * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(a.out_cov, 0, (size_t)R * C * F * F * 8, st));
+    HIP_TRY(hipMemsetAsync(a.bstate, 0, (size_t)R * (4 * C + 1) * 8, st));
+    HIP_TRY(hipMemcpyAsync(prior, mean_prior, (size_t)F * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(prior + F, covariance_prior, (size_t)F * F * 8, hipMemcpyHostToDevice, st));
+    if (labels) HIP_TRY(hipMemcpyAsync(a.labels, labels, (size_t)R * n * 4, hipMemcpyHostToDevice, st));
+    a.from_labels = 1;          // `_initialize`: the M step from the one-hot responsibilities, no iteration counted, no bound
+    if (fit_pass<FIT_EM_SUMS, true>(a, st) || fit_pass<FIT_EM_COV, true>(a, st)) return -1;
+    a.from_labels = 0;
+    HIP_TRY(hipStreamSynchronize(st));          // (pageable sources are free again)
+    if (fit_iterate(a.done, a.R, max_iter, st,
+                    [&]() { return fit_pass<FIT_EM_SUMS, true>(a, st) || fit_pass<FIT_EM_COV, true>(a, st) ? -1 : 0; }))
+        return -1;
+    int ints[6 * FIT_MAX_R];
+    double bounds[2 * FIT_MAX_R], state[FIT_MAX_R * 4 * FIT_MAX_C];
+    HIP_TRY(hipMemcpyAsync(ints, w + lay.o_ints, (size_t)6 * R * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(bounds, w + lay.o_dbl, (size_t)2 * R * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(state, a.bstate, (size_t)R * 4 * C * 8, hipMemcpyDeviceToHost, st));
+    if (means_out) HIP_TRY(hipMemcpyAsync(means_out, a.out_means, (size_t)R * C * F * 8, hipMemcpyDeviceToHost, st));
+    if (covariances_out) HIP_TRY(hipMemcpyAsync(covariances_out, a.out_cov, (size_t)R * C * F * F * 8, hipMemcpyDeviceToHost, st));
+    if (prec_chol_out) HIP_TRY(hipMemcpyAsync(prec_chol_out, a.out_prec, (size_t)R * C * F * F * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int r = 0; r < R; ++r) {
+        const double *s = state + (size_t)r * 4 * C;
+        for (int q = 0; q < C; ++q) {
+            if (weight_concentration_out) {
+                weight_concentration_out[(r * 2 + 0) * C + q] = s[q];
+                weight_concentration_out[(r * 2 + 1) * C + q] = s[C + q];
+            }
+            if (mean_precision_out) mean_precision_out[r * C + q] = s[2 * C + q];
+            if (degrees_of_freedom_out) degrees_of_freedom_out[r * C + q] = s[3 * C + q];
+        }
         if (lower_bound_out) lower_bound_out[r] = bounds[r];
         if (n_iter_out) n_iter_out[r] = ints[2 * R + r];
         if (converged_out) converged_out[r] = ints[5 * R + r];

@@ -528,6 +528,91 @@ def _fit_mixture_with(kmeans_lloyd, mixture_em, mixture, table, ctx):
     return mixture
 
 
+def _device_bayes_fit_refusal(mixture, table):
+    """why this Bayesian mixture / table is fitted on the host although the device was asked for, or None"""
+    from sklearn.mixture import BayesianGaussianMixture
+    if type(mixture) is not BayesianGaussianMixture:
+        return 'the device\'s variational fit is for plain BayesianGaussianMixture only, not %s' % type(mixture).__name__
+    if mixture.covariance_type != 'full' or mixture.init_params != 'kmeans':
+        return 'the device fits full covariances from a k-means initialisation only'
+    if mixture.warm_start:
+        return 'warm starts are fitted on the host'
+    if table.dtype != np.float64:
+        return 'a %s table is fitted on the host' % table.dtype
+    if table.shape[1] > 16:
+        return 'a Bayesian mixture on more than 16 features (%d) is fitted on the host' % table.shape[1]
+    if len(table) < mixture.n_components:
+        return 'fewer rows than components'
+    return None
+
+
+def fit_bayes_mixture_device(mixture, table, ctx=None):
+    """ ``mixture.fit(table)`` for ``BayesianGaussianMixture(covariance_type='full', init_params='kmeans')`` with the Lloyd and
+    variational iterations of all ``n_init`` restarts on the device (``csrc/mixture_fit.hip``: ``imsegm_kmeans_lloyd``,
+    ``imsegm_bayes_mixture_em``), either kind of weight concentration prior.
+
+    The priors are scikit-learn's own (``_check_parameters``: user-given ones are supported, with scikit-learn's errors); seeds,
+    Lloyd and the pick of the restart with the first largest lower bound are those of :func:`fit_mixture_device`.  The six
+    posterior parameters of the winner go through ``mixture._set_parameters``, so ``weights_`` and ``precisions_`` are
+    scikit-learn's arithmetic.  The sums run in another order than scikit-learn's: last digits differ from a host fit from the
+    same seeds, and the seeds are not the ones ``mixture.fit`` draws.
+
+    Whatever the device does not fit goes to :func:`fit_mixture_restarts`, on the random stream as it stood, with the reason
+    logged at INFO: more than 16 features / 8 components / 16 restarts, an empty k-means cluster, a covariance that is not
+    positive definite, another kind of mixture or covariance, a warm start, a float32 table.
+    """
+    import warnings
+    from sklearn.exceptions import ConvergenceWarning
+    from sklearn.utils import check_array, check_random_state
+    table = np.asarray(table)
+    reason = _device_bayes_fit_refusal(mixture, table) if table.ndim == 2 else 'the table is not two-dimensional'
+    if reason is None:
+        check_array(table, dtype=[np.float64], ensure_min_samples=2)        # (NaN / inf: ValueError before anything is uploaded)
+        ctx = ctx or _hip.default_context()                                # (HipUnavailableError without a library or a GPU)
+        stream = check_random_state(mixture.random_state)
+        stream_state = stream.get_state()
+        given, table = table, np.ascontiguousarray(table)                   # (the host fit gets the caller's array: a strided one sums differently)
+        n_init, n_comp = int(mixture.n_init), int(mixture.n_components)
+        mixture._validate_params()
+        mixture._check_parameters(table)                                   # (the priors; scikit-learn's errors for bad ones)
+        try:
+            seeds = device_fit_seeds(table, n_comp, n_init, stream)
+            lloyd = _hip.kmeans_lloyd(table, seeds, _KMEANS_MAX_ITER, _KMEANS_TOL * np.mean(np.var(table, axis=0)),
+                                      want_labels=False, ctx=ctx)
+            if lloyd['empty'].any():
+                reason = 'k-means left a cluster empty in restart %d' % int(np.argmax(lloyd['empty']))
+            else:
+                fit = _hip.bayes_mixture_em(n_init, n_comp, table.shape[1], mixture.weight_concentration_prior_type,
+                                            mixture.weight_concentration_prior_, mixture.mean_precision_prior_, mixture.mean_prior_,
+                                            mixture.degrees_of_freedom_prior_, mixture.covariance_prior_,
+                                            reg_covar=mixture.reg_covar, tol=mixture.tol, max_iter=mixture.max_iter, ctx=ctx)
+                if fit['not_pd'].any():
+                    reason = 'a covariance of restart %d is not positive definite' % int(np.argmax(fit['not_pd']))
+        except _hip.HipFitCapsError as ex:
+            reason = str(ex)
+        if reason is not None:
+            stream.set_state(stream_state)
+            table = given
+    if reason is not None:
+        logging.info('Bayesian mixture fit on the host: %s', reason)
+        return fit_mixture_restarts(mixture, table)
+    best = int(np.argmax(fit['lower_bound']))                   # (the first largest, as `fit_predict` keeps it)
+    concentration = fit['weight_concentration'][best]
+    if mixture.weight_concentration_prior_type == 'dirichlet_process':
+        concentration = (concentration[0].copy(), concentration[1].copy())
+    else:
+        concentration = concentration[0].copy()
+    mixture._set_parameters((concentration, fit['mean_precision'][best].copy(), fit['means'][best].copy(),
+                             fit['degrees_of_freedom'][best].copy(), fit['covariances'][best].copy(),
+                             fit['precisions_cholesky'][best].copy()))
+    mixture.converged_, mixture.n_iter_ = bool(fit['converged'][best]), int(fit['n_iter'][best])
+    mixture.lower_bound_, mixture.n_features_in_ = float(fit['lower_bound'][best]), table.shape[1]
+    if not mixture.converged_ and mixture.max_iter > 0:
+        warnings.warn('Best performing initialization did not converge. Try different init parameters, or increase max_iter, '
+                      'tol, or check for degenerate data.', ConvergenceWarning)
+    return mixture
+
+
 def _fit_place(fit_on):
     """'host', 'device' or 'device_wide' from the ``fit_on`` keyword; None: the environment variable IMSEGM_FIT_ON, unset: 'host'"""
     import os
@@ -550,7 +635,8 @@ def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, us
     (:func:`fit_mixture_device`: the same model from other seeds and with sums in another order -- last digits and the winning
     restart differ; tables of more than 16 features go to the host) or ``'device_wide'`` (:func:`fit_mixture_device_wide`:
     the device fit for tables of up to 256 features -- up to 16 features the same bytes as ``'device'``); ``None`` reads the
-    environment variable ``IMSEGM_FIT_ON``.
+    environment variable ``IMSEGM_FIT_ON``.  With ``estim_model='BGM'`` both device values mean
+    :func:`fit_bayes_mixture_device` (the variational fit, up to 16 features; wider tables go to the host).
     """
     from sklearn import decomposition, mixture, pipeline, preprocessing
     fit_on = _fit_place(fit_on)
@@ -571,7 +657,9 @@ def estim_class_model(features, nb_classes, estim_model='GMM', pca_coef=None, us
         table = table.astype(np.float64)
     for _, step in model.steps[:-1]:        # what Pipeline.fit does with the steps in front of the last one
         table = step.fit_transform(table)
-    if fit_on == 'device':
+    if fit_on != 'host' and type(model.steps[-1][1]) is mixture.BayesianGaussianMixture:
+        fit_bayes_mixture_device(model.steps[-1][1], table, ctx=_ctx)
+    elif fit_on == 'device':
         fit_mixture_device(model.steps[-1][1], table, ctx=_ctx)
     elif fit_on == 'device_wide':
         fit_mixture_device_wide(model.steps[-1][1], table, ctx=_ctx)
